@@ -1,6 +1,6 @@
 """Benchmark of the generator-forward hot path: rendered views / second.
 
-    python bench.py [--gpus N --steps K --warmup W] [--res 1024 --depth 2 --n-samples 24 --batch 1]
+    python bench.py [--gpus N --steps K --warmup W] [--res 1024 --depth 2 --n-samples 24 --batch 1] [--dump-outputs DIR] [--full]
 
 One step = one `Generator.forward` over one batch of synthetic views with inputs resident in HBM
 (mapping -> fused NeRF render -> decoder -> rgb in device memory), i.e. the loop body of the
@@ -14,9 +14,15 @@ reference's own multi-process scripts (exp/tests/test_cips3dpp.py:814-820, scrip
 Every rank renders its own batch per step and the images are gathered to rank 0 over RCCL inside the
 timed region (weak scaling).
 
-The timed region is K steps between (barrier + device synchronise) brackets, max over ranks; it is
-repeated `--repeats` times and the MEDIAN repeat is reported (all repeats are listed).  At N = 1 the other
-BASELINE.json configurations are timed after the headline and reported under "also" in the same line.
+The timed region is K steps between (barrier + device synchronise) brackets, max over ranks.  A plain run
+sets up, warms up (W steps, then untimed chunks of 32 steps until two agree within 1 %, at most 30), times
+ONE region of K steps and prints the line: `ms_per_step` is that region over K.  `--full` adds everything else the benchmark measures: untimed pre-roll regions until the clocks
+settle, `--repeats` regions (default 5) of which the MEDIAN is reported, the one-stream regions, the roofline
+and per-kernel tables, the fp32 equivalence check and, at N = 1, the other BASELINE.json configurations
+("also") and the CPU baseline.
+
+`--dump-outputs DIR` writes what the last timed step returned (the image batch; at N > 1 the frames gathered
+on rank 0) as DIR/<name>.npy; the inputs are seeded, so the same arguments give the same inputs every run.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
@@ -52,6 +58,10 @@ EVENT_STRIDE = 8                           # HIP events around the dominant kern
 TRAFFIC_FILES = {"headline": "pmc_all_kernels.json", "n64": "pmc_n64_traffic.json", "b4_bf16": "pmc_b4_traffic.json"}   # profiles/rNN_<name>, newest round first
 HBM_PEAK_TBS = 8.0                         # MI355X_MICROARCH.md: HBM3E spec peak (6.3 TB/s measured with a float4 copy)
 PREROLL_MAX = 10                           # untimed regions until two consecutive ones agree within 1 % (clocks / caches settled)
+SETTLE_STEPS, SETTLE_MAX = 32, 30          # a plain run's bounded pre-roll: chunks of 32 untimed steps, at most 30 of them
+SEED = 0                                   # torch's generators: the fresh noise and jitter of every step draw from them
+DUMP_LIMIT_BYTES = 64 * 2 ** 20            # --dump-outputs: at most this much in all ...
+DUMP_SAMPLE = 2 ** 22                      # ... else a fixed, seeded sample of this many elements of every larger output
 
 
 def dedupe_traffic(rows):
@@ -158,6 +168,7 @@ class ForwardWorkload:
             self.noise_bufs = [torch.randn(b.shape, device=dev, generator=g) for b in self.noise_bufs]
         self.pending = None
         self.last_gathered = None
+        self.keep_out, self.last_out = False, None      # keep_out: hold what the last timed step returned (--dump-outputs)
         # views in flight: consecutive (independent) steps alternate between `lanes` streams (pipeline.ViewPipeline); the timed
         # regions end with every lane drained and the device synchronised.  1 = every step on the one current stream.
         from cips_3dplusplus_amd.pipeline import ViewPipeline
@@ -234,21 +245,23 @@ class ForwardWorkload:
 
     keep_last = False
 
-    def measure(self, steps, warmup, repeats, kernel_events=True):
+    def measure(self, steps, warmup, repeats, kernel_events=True, preroll=True):
         """`repeats` timed regions of `steps` steps each (barrier + synchronise on both sides, max over ranks)."""
         from cips_3dplusplus_amd import hip
         for _ in range(warmup):
             self.step()
         # pre-roll: --warmup steps do not reach steady clocks (round 2's driver-form repeats fell monotonically by 8 %): run
-        # whole untimed regions until two consecutive ones agree within 1 %, then time
+        # whole untimed regions until two consecutive ones agree within 1 %, then time.  Without `preroll` (a plain run) the
+        # chunks are SETTLE_STEPS steps, at most SETTLE_MAX of them: a cost that does not grow with --steps
         self.preroll = []
-        for _ in range(PREROLL_MAX):
+        n_pre, pre_steps = (PREROLL_MAX, steps) if preroll else (SETTLE_MAX, max(1, min(steps, SETTLE_STEPS)))
+        for _ in range(n_pre):
             self.barrier()
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(pre_steps):
                 self.step()
             self.barrier()
-            dt = time.perf_counter() - t0
+            dt = (time.perf_counter() - t0) * steps / pre_steps          # (as a region of `steps` steps)
             if self.world > 1:
                 t = torch.tensor([dt], device=self.dev, dtype=torch.float64)
                 torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -259,19 +272,25 @@ class ForwardWorkload:
         # Short regions (the driver's --steps 20) time ONE launch per region, the one in the middle: every record drains the
         # queue (~6-10 us), and three of them in a 7 ms window are 0.4 % of it; long regions keep one launch in eight.
         stride = EVENT_STRIDE if steps >= 64 else max(1, steps)
-        hip.KERNEL_EVENTS_STRIDE = stride
-        hip.KERNEL_EVENTS_PHASE = stride // 2
-        hip._event_calls.pop("nerf_render", None)           # (the phase counts calls from here)
-        hip.prepare_event_pairs(repeats * (steps // stride + 2))
+        if kernel_events:
+            hip.KERNEL_EVENTS_STRIDE = stride
+            hip.KERNEL_EVENTS_PHASE = stride // 2
+            hip._event_calls.pop("nerf_render", None)           # (the phase counts calls from here)
+            hip.prepare_event_pairs(repeats * (steps // stride + 2))
         self.event_stride = stride
         events, elapsed = [], []
-        for _ in range(repeats):
+        for r in range(repeats):
+            torch.manual_seed(SEED)           # every timed region draws the same noise, however long the pre-roll ran
             self.barrier()
             if kernel_events:
                 hip.KERNEL_EVENTS["nerf_render"] = []
+            keep_at = steps - 1 if (self.keep_out and r == repeats - 1) else -1
             t0 = time.perf_counter()
-            for _ in range(steps):
-                self.step()
+            for i in range(steps):
+                if i == keep_at:
+                    self.last_out = self.step()
+                else:
+                    self.step()
             self.barrier()
             dt = time.perf_counter() - t0
             events += hip.KERNEL_EVENTS.pop("nerf_render", [])
@@ -556,19 +575,20 @@ def multiview_workload(dev, repeats, n_frames=8, n_samples=128, res=1024):
             "config": {"workload": f"ffhq_r{res}_nerf64x64x{n_samples}_D2_B1 x {n_frames} frames (multiview.sample_multi_view)"}}
 
 
-def measure_with_single_stream(wl, steps, warmup, repeats, batch, kernel_events=True, single_too=True):
+def measure_with_single_stream(wl, steps, warmup, repeats, batch, kernel_events=True, single_too=True, preroll=True):
     """The workload's timed regions (views in flight as configured), then -- when it runs more than one lane -- a few regions
     of the same steps on ONE stream: the quantity every earlier round reported, and where the dominant kernel's duration is taken
     (alone on the chip).  -> (median region s, region times, kernel ms for the roofline, events, kernel ms in flight | None,
     single-stream dict | None)."""
-    med, elapsed, kern_ms, n_ev = wl.measure(steps, warmup, repeats, kernel_events=kernel_events)
+    med, elapsed, kern_ms, n_ev = wl.measure(steps, warmup, repeats, kernel_events=kernel_events, preroll=preroll)
     if wl.pipe is None or not single_too:
         return med, elapsed, kern_ms, n_ev, None, None
     pipe, wl.pipe = wl.pipe, None
+    keep, wl.keep_out = wl.keep_out, False              # (the dumped output stays the headline regions' last step)
     try:
-        m1, e1, k1, n1 = wl.measure(steps, max(3, warmup // 4), min(3, repeats), kernel_events=kernel_events)
+        m1, e1, k1, n1 = wl.measure(steps, max(3, warmup // 4), min(3, repeats), kernel_events=kernel_events, preroll=preroll)
     finally:
-        wl.pipe = pipe
+        wl.pipe, wl.keep_out = pipe, keep
     single = {"value": steps * batch / m1, "unit": "views/s", "ms_per_step": m1 / steps * 1e3,
               "ms_per_step_repeats": [e / steps * 1e3 for e in e1],
               "what": "the same steps issued on one stream (views strictly one after the other): the `value` of rounds 1-5"}
@@ -680,6 +700,22 @@ def emit(line, detail_path):
     return text
 
 
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy, float32 (float64 stays float64).  When the arrays hold more than DUMP_LIMIT_BYTES
+    in all, every one larger than DUMP_SAMPLE elements is replaced by the same seeded sample of its flattened elements, whose
+    flat indices go beside it as <name>_index.npy (float64: exact below 2^53)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: (t.detach().double() if t.dtype == torch.float64 else t.detach().float()).cpu().numpy() for k, t in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    for k, v in host.items():
+        if total > DUMP_LIMIT_BYTES and v.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, DUMP_SAMPLE, replace=False))
+            np.save(os.path.join(out_dir, f"{k}_index.npy"), idx.astype(np.float64))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
 def spawn_ranks(a):
     """`--gpus N` without a launcher: start N fresh ranks (this process has not touched the GPU and never will)."""
     env = dict(os.environ)
@@ -701,7 +737,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default: 1; with --full 5)")
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--depth", type=int, default=2)
     ap.add_argument("--n-samples", type=int, default=24)
@@ -715,10 +752,22 @@ def main():
     ap.add_argument("--decoder-precision", default="fp32", choices=["fp32", "fp32_exact", "bf16", "bf16_storage"],
                     help="bf16 = BASELINE config 3 (decoder GEMMs on bf16 MFMA, fp32 accumulate; NeRF stays fp32); "
                          "bf16_storage = additionally the up-sampling stages' pre-FIR activations live in HBM as bf16")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="where rank 0 writes the full record (repeats, pre-roll, per-kernel bounds, provenance); '' = nowhere")
+    ap.add_argument("--detail", default=None,
+                    help="where rank 0 writes the full record (repeats, pre-roll, per-kernel bounds, provenance); '' = nowhere "
+                         "(default: bench_detail.json with --full, nowhere otherwise)")
     ap.add_argument("--dump-gathered", default=None, help="rank 0 saves the last step's gathered uint8 frames (torch.save)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float32): `rgb`, the image batch; "
+                         "at N > 1 `gathered_frames`, the uint8 frames gathered on rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: pre-roll to steady clocks, the median of --repeats regions, the one-stream "
+                         "regions, roofline and per-kernel tables, the fp32 equivalence check, the other BASELINE configurations and "
+                         "the CPU baseline (a plain run times one region of --steps steps after --warmup steps)")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    if a.detail is None:
+        a.detail = os.path.join(ROOT, "bench_detail.json") if a.full else ""
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a))
@@ -751,10 +800,16 @@ def main():
         else:
             dist.init_process_group(backend=backend)
 
+    torch.manual_seed(SEED)
     wl = ForwardWorkload(dev, rank, world, a.res, a.depth, a.n_samples, a.batch, a.decoder_precision, a.deterministic, lanes=a.lanes)
-    wl.keep_last = a.dump_gathered is not None
+    wl.keep_last = a.dump_gathered is not None or (a.dump_outputs is not None and world > 1)
+    wl.keep_out = a.dump_outputs is not None and world == 1
     med, elapsed, kern_ms, n_ev, kern_in_flight, single = measure_with_single_stream(
-        wl, a.steps, a.warmup, a.repeats, a.batch, kernel_events=not a.no_kernel_events, single_too=(world == 1))
+        wl, a.steps, a.warmup, a.repeats, a.batch, kernel_events=a.full and not a.no_kernel_events,
+        single_too=a.full and world == 1, preroll=a.full)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"rgb": wl.last_out} if world == 1 else {"gathered_frames": wl.last_gathered})
+        wl.last_out = None
     if a.dump_gathered and rank == 0:
         frames = wl.last_gathered if world > 1 else None
         if frames is None:
@@ -792,7 +847,7 @@ def main():
             line["roofline"]["measured_in"] = "the single-stream timed regions of this run (single_stream); in_flight_avg_launch_ms: the headline's regions"
         if single is not None:
             line["single_stream"] = single
-        if world == 1 and a.decoder_precision == "fp32":
+        if a.full and world == 1 and a.decoder_precision == "fp32":
             # the default arithmetic (split-fp16 products) against the fp32 matrix instruction on this run's own inputs
             try:
                 line["fp32_equivalence"] = wl.fp32_equivalence()
@@ -804,7 +859,7 @@ def main():
             line["ranks"] = torch.distributed.get_world_size()
             line["dist_backend"] = backend + (" (RCCL)" if backend == "nccl" else " (ranks share devices: not an RCCL measurement)")
             line["physical_gpus"] = n_dev
-        if world == 1 and not a.no_also and published_cfg:
+        if a.full and world == 1 and not a.no_also and published_cfg:
             # the other BASELINE.json configurations, same command, same box (each its own timed regions)
             also = []
             del wl
@@ -859,7 +914,7 @@ def main():
             except Exception as exc:           # noqa: BLE001
                 also.append({"tag": "config5_inversion_appearance", "what": "BASELINE config 5, appearance phase", "error": f"{type(exc).__name__}: {exc}"[:400]})
             line["also"] = also
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             from cips_3dplusplus_amd import configs
             try:
                 line["cpu_baseline"] = cpu_baseline(configs.ffhq_G_cfg(a.res, a.depth),

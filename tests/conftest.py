@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -26,16 +27,21 @@ def pytest_collection_modifyitems(config, items):
 
 
 class Fixture:
-    """npz fixture with torch access: fx['name'] -> tensor, fx.sub('prefix.') -> dict."""
+    """npz fixture with torch access: fx['name'] -> tensor, fx.sub('prefix.') -> dict.  A fixture larger than a committed file
+    may be stored in parts (name.npz, name.part2.npz, ...: tests/golden/make_golden.py), read here as one, keys in order."""
 
     def __init__(self, name):
-        self._z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+        paths = [os.path.join(GOLDEN, name + ".npz")]
+        paths += sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")), key=lambda p: int(p.split(".part")[-1][:-4]))
+        parts = [np.load(p, allow_pickle=False) for p in paths]
+        self._files = [k for z in parts for k in z.files]
+        self._part = {k: z for z in parts for k in z.files}
 
     def __contains__(self, k):
-        return k in self._z.files
+        return k in self._part
 
     def __getitem__(self, k):
-        a = self._z[k]
+        a = self._part[k][k]
         if a.dtype.kind in "US":
             return a
         if a.dtype == np.uint64:          # exact integer checksums
@@ -43,10 +49,10 @@ class Fixture:
         return torch.from_numpy(np.array(a))
 
     def keys(self):
-        return list(self._z.files)
+        return list(self._files)
 
     def sub(self, prefix):
-        return {k[len(prefix):]: self[k] for k in self._z.files if k.startswith(prefix)}
+        return {k[len(prefix):]: self[k] for k in self._files if k.startswith(prefix)}
 
 
 @pytest.fixture(scope="session")

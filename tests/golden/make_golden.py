@@ -7,8 +7,10 @@ Writes tests/golden/*.npz: inputs + expected outputs (data only, no reference so
 Every fixture records which reference entry point produced it (file:line in `_src`).
 """
 import argparse
+import glob
 import os
 import sys
+import zipfile
 
 import numpy as np
 import torch
@@ -32,10 +34,40 @@ def npy(d):
     return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in d.items()}
 
 
+PART_BYTES = 960 * 1024      # a committed file stays under 1 MiB: larger fixtures are written as name.npz + name.part2.npz, ...
+
+
+def split_parts(path):
+    """Splits the npz at `path` into consecutive runs of its members of at most PART_BYTES compressed each (the member bytes
+    are copied as they are: the arrays and their order are unchanged; tests/conftest.py reads the parts as one fixture)."""
+    base = path[:-len(".npz")]
+    for old in glob.glob(glob.escape(base) + ".part*.npz"):
+        os.remove(old)
+    if os.path.getsize(path) <= PART_BYTES:
+        return [path]
+    with zipfile.ZipFile(path) as src:
+        groups, size = [[]], 0
+        for info in src.infolist():
+            cost = info.compress_size + 2 * len(info.filename) + 100      # (+ the member's local and central headers)
+            if groups[-1] and size + cost > PART_BYTES:
+                groups.append([])
+                size = 0
+            groups[-1].append((info.filename, src.read(info.filename)))
+            size += cost
+    paths = [path] + [f"{base}.part{i}.npz" for i in range(2, len(groups) + 1)]
+    for p, members in zip(paths, groups):
+        with zipfile.ZipFile(p + ".tmp", "w", compression=zipfile.ZIP_DEFLATED) as dst:
+            for fn, data in members:
+                dst.writestr(fn, data)
+        os.replace(p + ".tmp", p)
+    return paths
+
+
 def save(name, **d):
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **npy(d))
-    print(f"{name}: {os.path.getsize(path) / 1024:.1f} KB")
+    for p in split_parts(path):
+        print(f"{os.path.basename(p)}: {os.path.getsize(p) / 1024:.1f} KB")
 
 
 # ---------------------------------------------------------------- 1. cameras

@@ -93,3 +93,30 @@ def test_replayed_traffic_stays_with_a_kernels_dominant_shape():
     out = bench.dedupe_traffic([dict(r) for r in rows])
     assert [r["traffic"] for r in out] == [9.6e6, 24.2e6, None, 24.6e6, 58.9e6, None, None]
     assert out[2]["traffic_source"].startswith("no counter pass")
+
+
+def test_dump_outputs_writes_float_arrays_and_a_seeded_sample_past_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per output, float32 (float64 kept); past DUMP_LIMIT_BYTES in all, every larger output
+    becomes the same seeded sample of its elements, with the sample's flat indices beside it."""
+    import numpy as np
+    import torch
+    small = {"rgb": torch.arange(12, dtype=torch.float32).reshape(1, 3, 2, 2) / 7, "frames": torch.arange(6, dtype=torch.uint8),
+             "depth": torch.full((2,), 1 / 3, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["depth.npy", "frames.npy", "rgb.npy"]
+    for k, v in small.items():
+        a = np.load(tmp_path / "a" / f"{k}.npy")
+        assert a.dtype == (np.float64 if k == "depth" else np.float32) and a.shape == tuple(v.shape)
+        assert np.array_equal(a, v.double().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    big = {"rgb": torch.randn(2, 3, 40, 40), "depth": torch.randn(50, dtype=torch.float64)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    assert sorted(os.listdir(tmp_path / "b")) == ["depth.npy", "rgb.npy", "rgb_index.npy"]
+    a, idx = np.load(tmp_path / "b" / "rgb.npy"), np.load(tmp_path / "b" / "rgb_index.npy")
+    assert a.shape == (100,) and a.dtype == np.float32 and idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a, big["rgb"].numpy().reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "depth.npy"), big["depth"].numpy())
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))

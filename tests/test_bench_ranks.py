@@ -99,6 +99,30 @@ def test_the_drivers_eight_rank_command_runs_end_to_end():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run: one timed region of exactly --steps steps, no secondary measurement, and --dump-outputs writes the image batch
+    the last timed step returned -- the same images in a second process with the same arguments (seeded inputs)."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / d)],
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.rstrip("\n").splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["repeats"] == 1 and len(line["ms_per_step_repeats"]) == 1
+        assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-4)
+        assert line["unit"] == "views/s" and line["higher_is_better"] is True and line["dtype"]
+        for k in ("also", "cpu_baseline", "single_stream", "split_vs_fp32_exact_max_abs"):
+            assert k not in line, k
+        assert line["roofline"] is None
+    assert sorted(os.listdir(tmp_path / "a")) == ["rgb.npy"]
+    a, b = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "b" / "rgb.npy")
+    assert a.dtype == np.float32 and a.shape == (1, 3, 1024, 1024) and np.isfinite(a).all() and a.std() > 0
+    assert np.array_equal(a, b)
+
+
+@pytest.mark.gpu
 def test_single_gpu_line_prices_every_big_kernel(tmp_path):
     """The N = 1 line as the driver reads it: the LAST stdout line, one compact JSON object under bench.LINE_LIMIT bytes, whose
     `roofline.kernels` prices the render kernel, the 64^2 chain GEMM and the four fused up-sampling stages -- each with an in-run
@@ -107,8 +131,8 @@ def test_single_gpu_line_prices_every_big_kernel(tmp_path):
     sys.path.insert(0, ROOT)
     import bench
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, BENCH, "--steps", "10", "--warmup", "3", "--repeats", "2", "--no-cpu-baseline", "--no-also",
-                        "--detail", detail], env=_env(), capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, BENCH, "--full", "--steps", "10", "--warmup", "3", "--repeats", "2", "--no-cpu-baseline",
+                        "--no-also", "--detail", detail], env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     last = r.stdout.rstrip("\n").splitlines()[-1]
     assert len(last) < bench.LINE_LIMIT, len(last)

@@ -249,7 +249,10 @@ def test_oracle_config5_at_stated_size(golden):
     loss.backward()
     assert abs(float(loss.detach()) - float(fx["loss"])) < 1e-5 * float(fx["loss"])
     for a, k in ((locs.grad, "g.locs"), (w_r.grad, "g.w_r"), (w_d.grad, "g.w_d")):
-        assert float((a - fx[k]).abs().max()) <= 2e-4 * float(fx[k].abs().max()) + 1e-8, k
+        # (or twice the reference's own fp32-vs-fp64 difference for that gradient, stored in the fixture: g.locs is a heavily
+        # cancelled sum whose fp32 value moves by about that much with the host's summation order -- thread count, vector width)
+        bound = max(2e-4 * float(fx[k].abs().max()), 2 * float(fx[k + "_floor"]))
+        assert float((a - fx[k]).abs().max()) <= bound + 1e-8, k
 
 
 def test_k3_upsample_identity(golden):
