@@ -230,10 +230,17 @@ _SIGS = {
     "cips3d_sizeof_plan": (c_i64, []),
     "cips3d_sizeof_io": (c_i64, []),
     "cips3d_sizeof_struct": (c_i64, [c_int]),
+    "cips3d_align_volume": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, C.c_double, C.c_double, C.c_void_p]),
+    "cips3d_marching_cubes_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "cips3d_marching_cubes_count": (c_int, [c_f32p, c_int, c_int, c_int, c_f32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_marching_cubes_emit": (c_int, [c_f32p, c_int, c_int, c_int, c_f32, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
+                                           c_int, c_int, C.c_void_p]),
+    "cips3d_mc_table_width": (c_int, []),
+    "cips3d_mc_case_table": (c_int, [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 30           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 31           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

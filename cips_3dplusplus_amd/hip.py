@@ -1330,3 +1330,67 @@ def sqdiff_pair_bwd(a0, b0, c0, a1, b1, c1, gloss):
                                      dev_ptr(b1, "b1", True), n1, float(c1), dev_ptr(d1, "d1", True), dev_ptr(gloss, "gloss"),
                                      stream_ptr()), "cips3d_sqdiff_pair_bwd")
     return d0, d1
+
+
+# ---------------------------------------------------------------------------------------------- geometry export (csrc/mesh.hip)
+def align_volume(volume, near=0.88, far=1.12, out=None):
+    """cips3d_align_volume: volume [B,h,w,d] fp32 -> the frustum-aligned volume of the same shape."""
+    lib = _lib.load()
+    if volume.dim() != 4:
+        raise RuntimeError("align_volume: volume must be [B, h, w, d]")
+    B, h, w, d = volume.shape
+    if out is None:
+        out = torch.empty_like(volume)
+    check(lib.cips3d_align_volume(dev_ptr(volume, "volume"), dev_ptr(out, "out"), B, h, w, d, float(near), float(far),
+                                  stream_ptr()), "cips3d_align_volume")
+    return out
+
+
+def marching_cubes_count(vol, level=0.0):
+    """cips3d_marching_cubes_count on vol [h,w,d] fp32 -> (workspace, totals: device int32 [2] = V, F), enqueued only."""
+    lib = _lib.load()
+    if vol.dim() != 3:
+        raise RuntimeError("marching_cubes: vol must be [h, w, d]")
+    h, w, d = vol.shape
+    ws_bytes = lib.cips3d_marching_cubes_workspace_bytes(h, w, d)
+    if ws_bytes < 0:
+        check(int(ws_bytes), "cips3d_marching_cubes_workspace_bytes")
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=vol.device)
+    totals = torch.empty(2, dtype=torch.int32, device=vol.device)
+    check(lib.cips3d_marching_cubes_count(dev_ptr(vol, "vol"), h, w, d, float(level), ws.data_ptr(), totals.data_ptr(),
+                                          stream_ptr()), "cips3d_marching_cubes_count")
+    return ws, totals
+
+
+def marching_cubes_emit(vol, level, ws, n_verts, n_faces, affine=None):
+    """cips3d_marching_cubes_emit after marching_cubes_count (same vol, level, workspace) -> (verts [V,3] fp32,
+    faces [F,3] int32).  `affine`: ((sx, ox), (sy, oy), (sz, oz)) per axis on index-space positions (None: index space)."""
+    lib = _lib.load()
+    h, w, d = vol.shape
+    verts = torch.empty(n_verts, 3, dtype=torch.float32, device=vol.device)
+    faces = torch.empty(n_faces, 3, dtype=torch.int32, device=vol.device)
+    aff = None if affine is None else (C.c_float * 6)(*[float(v) for pair in affine for v in pair])
+    check(lib.cips3d_marching_cubes_emit(dev_ptr(vol, "vol"), h, w, d, float(level), aff, ws.data_ptr(),
+                                         verts.data_ptr() if n_verts else None, faces.data_ptr() if n_faces else None,
+                                         n_verts, n_faces, stream_ptr()), "cips3d_marching_cubes_emit")
+    return verts, faces
+
+
+def marching_cubes(vol, level=0.0, affine=None):
+    """Marching cubes on one volume [h,w,d] fp32 -> (verts [V,3] fp32, faces [F,3] int64) on its device (contract:
+    include/cips3d_hip.h).  Reading the two totals is the one host synchronisation; the outputs are allocated from them."""
+    ws, totals = marching_cubes_count(vol, level)
+    n_v, n_f = (int(v) for v in totals.cpu())
+    verts, faces = marching_cubes_emit(vol, level, ws, n_v, n_f, affine)
+    return verts, faces.long()
+
+
+def mc_case_table():
+    """The library's case table (host only): (tri_count [256] int32, tri_edges [256, width, 3] int32, -1 padded)."""
+    import numpy as np
+    lib = _lib.load()
+    width = lib.cips3d_mc_table_width()
+    cnt = np.zeros(256, np.int32)
+    edges = np.zeros((256, width, 3), np.int32)
+    check(lib.cips3d_mc_case_table(cnt.ctypes.data, edges.ctypes.data), "cips3d_mc_case_table")
+    return cnt, edges

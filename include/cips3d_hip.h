@@ -20,6 +20,8 @@
  *   cips3d_camera_params      cips3d/nerf_utils.py:344-436,466-564
  *   cips3d_nerf_*             cips3d/nerf_utils.py:18-338 + cips3d/volume_renderer.py:39-303
  *   cips3d_modconv_* / torgb  models/model_v3.py:218-341,418-482
+ *   cips3d_align_volume,      cips3d/utils.py:183-224 (align_volume, extract_mesh_with_marching_cubes;
+ *   cips3d_marching_cubes_*   the reference runs skimage.measure.marching_cubes on the host)
  */
 #ifndef CIPS3D_HIP_H
 #define CIPS3D_HIP_H
@@ -30,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 30  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 31  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1081,6 +1083,46 @@ int cips3d_rng_fill(uint64_t seed, uint64_t base, float* normal, int64_t n_norma
                     void* stream);
 int64_t cips3d_rng_fill_threads(int64_t n_normal, int64_t n_uniform);
 int cips3d_rng_words(uint64_t seed, uint64_t base, uint32_t* out, int64_t n_threads, void* stream);
+
+/* ------------------------------------------------------------------ geometry export (csrc/mesh.hip) */
+
+/* Frustum alignment of a renderer SDF volume (cips3d/utils.py:183-203): volume, out [B,h,w,d].  With y_i, x_j, z_k =
+ * linspace(-1, 1) over h, w, d and c_k = linspace(far / near, 1, d)[k] (torch's fp32 values, bit for bit):
+ *   X = x_j c_k, Y = y_i c_k;  out[b,i,j,k] = 1 when X or Y lies outside [-1, 1], else volume[b] sampled trilinearly at
+ *   row (Y+1)(h-1)/2, column (X+1)(w-1)/2, depth (z_k+1)(d-1)/2, each clamped to [0, n-1]
+ *   (grid_sample(align_corners=True, padding_mode="border")).
+ * far / near is formed in double and rounded to fp32, as the reference's Python quotient is. */
+int cips3d_align_volume(const float* volume, float* out, int B, int h, int w, int d, double near_, double far_, void* stream);
+
+/* Marching cubes on one volume A [h,w,d] (h, w, d >= 2) at `level`, in two calls on one stream:
+ *   cips3d_marching_cubes_count writes totals[0] = V (vertices), totals[1] = F (triangles) to a device int32[2] and
+ *   fills `workspace` (cips3d_marching_cubes_workspace_bytes(h, w, d) bytes); the caller reads the totals, allocates the
+ *   outputs and calls cips3d_marching_cubes_emit with the same volume, level and workspace: verts [V,3] fp32, faces [F,3]
+ *   int32 (max_verts / max_faces bound every store).
+ * Contract:
+ *   axes as the reference's sdf.permute(1, 0, 2): x <-> column j, y <-> row i, z <-> depth k;
+ *   a point is inside when A < level (NaN: outside); one vertex per lattice edge whose ends disagree, shared by every cell
+ *   on that edge, at a + t e_axis, t = (level - A_a) / (A_b - A_a), a = the edge's lower end; then per axis
+ *   X = x * affine_host[0] + affine_host[1], Y = y * affine_host[2] + affine_host[3], Z = z * affine_host[4] + affine_host[5]
+ *   (affine_host NULL: index space);
+ *   vertices ordered by the lower end of their edge in memory order of A, then +x, +y, +z; triangles by their cell's lower
+ *   corner in the same order, then in case-table order (cips3d_mc_case_table); bit-reproducible (prefix sums, no atomics);
+ *   winding: in index space (and in any affine of positive determinant) (v1 - v0) x (v2 - v0) points towards larger values;
+ *   a face whose corners form a checkerboard separates its inside corners, so neighbouring cells agree and a surface that
+ *   stays off the border is a closed, oriented 2-manifold.
+ * No crossing: V = F = 0.  CIPS3D_E_BADARG for a dimension below 2 or null pointers, CIPS3D_E_UNSUPP when the counts could
+ * exceed int32 (the workspace query returns the same codes). */
+int64_t cips3d_marching_cubes_workspace_bytes(int h, int w, int d);
+int cips3d_marching_cubes_count(const float* volume, int h, int w, int d, float level, void* workspace, int32_t* totals,
+                                void* stream);
+int cips3d_marching_cubes_emit(const float* volume, int h, int w, int d, float level, const float* affine_host,
+                               const void* workspace, float* verts, int32_t* faces, int max_verts, int max_faces,
+                               void* stream);
+/* The case table (tools/gen_mc_table.py), host only: corner c = x + 2y + 4z of a cell, case bit c = corner c inside; cube
+ * edge e of axis e / 4 starts at corner (0, e&1, e>>1) for x-edges, (e&1, 0, e>>1) for y-edges, (e&1, e>>1, 0) for
+ * z-edges (e &= 3).  tri_count_host [256]; tri_edges_host [256][3 * cips3d_mc_table_width()], -1 past the count. */
+int cips3d_mc_table_width(void);
+int cips3d_mc_case_table(int32_t* tri_count_host, int32_t* tri_edges_host);
 
 #ifdef __cplusplus
 }
