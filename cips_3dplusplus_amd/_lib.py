@@ -123,6 +123,8 @@ _SIGS = {
     "cips3d_nerf_part_floats": (c_i64, [c_int, c_int, c_int, c_int]),
     "cips3d_nerf_render": (c_int, [C.POINTER(NerfParams), C.c_void_p]),
     "cips3d_nerf_fuses_finish": (c_int, [C.POINTER(NerfParams)]),
+    "cips3d_nerf_sdf_grad": (c_int, [C.POINTER(NerfParams), c_f32p, C.c_void_p]),
+    "cips3d_nerf_sdf_grad_supported": (c_int, [c_int, c_int]),
     "cips3d_nerf_finish": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_finish_rays": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_modulate_weights": (c_int, [c_f32p, c_f32p, c_i64, c_f32p, c_int, c_int, c_int, c_int, c_f32, c_int,
@@ -240,7 +242,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 31           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 32           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

@@ -128,11 +128,10 @@ class Generator(nn.Module):
         """model_v3.py:1201-1268: the NeRF half for caller-made geometry, pts (b, hw, n, 3) etc. -> thumb_rgb (b, hw, 3),
         sdf (b, hw, n, 1), mask (b, hw, 2), xyz (b, hw, 3), features (b, hw, C), eikonal_term.  The reference loops over
         `N_rays_forward`-sized ray chunks to bound memory; the fused kernel keeps no per-point activations, so one call
-        covers all rays (the chunk size is accepted and ignored)."""
-        if eikonal_reg:
-            raise NotImplementedError("eikonal_reg needs double backward (training-only)")
+        covers all rays (the chunk size is accepted and ignored).  eikonal_reg: eikonal_term = d sdf / d pts, the shape of
+        `pts` (a constant: VolumeFeatureRenderer.forward(return_eikonal=True)); None otherwise."""
         thumb, feats, sdf, mask, xyz, eik = self.renderer(pts=pts, rays_d=rays_d, viewdirs=viewdirs, z_vals=z_vals, near=near,
-                                                          far=far, styles=style_render)
+                                                          far=far, styles=style_render, return_eikonal=bool(eikonal_reg))
         return thumb, sdf, mask, xyz, feats, eik
 
     def init_forward(self, *args, **kwargs):
@@ -277,6 +276,17 @@ class Generator(nn.Module):
                 "sdf": sdf if return_sdf else None, "xyz": xyz if return_xyz else None,
                 "mask": m2[0].unsqueeze(1), "depth": m2[1].unsqueeze(1)}
 
+    def _eikonal_term(self, cam_poses, focals, near, far, style_render, img_size, N, perturb_u, static, film=None):
+        """ret_maps["eikonal_term"] of the inference path: d sdf / d pts at the forward's sample points, (B, img_size^2, N, 3) fp32
+        (model_v3.py:1009-1010 leaves the renderer's layout), a constant; None for with_sdf=False renderers (the reference
+        computes the term only in its SDF branch)."""
+        if not self.renderer.with_sdf:
+            return None
+        B = cam_poses.shape[0]
+        _, grad = self.renderer.sdf_gradient(cam_poses, focals, near, far, style_render, img_size, N, perturb_u=perturb_u,
+                                             static_viewdirs=static, film=film)
+        return grad.view(B, img_size * img_size, N, 3)
+
     def can_emit_uint8(self, B, img_size, N_samples, static_viewdirs=False):
         """True when a forward of this shape can write its image as uint8 (`rgb_out` of dtype uint8)."""
         plan = self._forward_plan(B, img_size, int(N_samples), bool(static_viewdirs))
@@ -334,8 +344,12 @@ class Generator(nn.Module):
                       sample_idx_h, sample_idx_w, perturb_u):
         from . import autograd as AG
         assert len(zs) == 2
-        if eikonal_reg or path_reg:
-            raise NotImplementedError("eikonal_reg / path_reg need double backward (training-only)")
+        if eikonal_reg:
+            raise NotImplementedError("eikonal_reg on the differentiable path: a graph through d sdf / d pts means double backward "
+                                      "(training-only).  The quantity itself, as a constant, comes from the inference path (call "
+                                      "under torch.no_grad()) or from VolumeFeatureRenderer.sdf_gradient / forward(return_eikonal=True)")
+        if path_reg:
+            raise NotImplementedError("path_reg needs double backward (training-only)")
         if N_rays_grad is not None or sample_idx_h is not None or sample_idx_w is not None or project_noise:
             raise NotImplementedError("ray sub-sampling / project_noise are training-only")
         noise_bufs = self.get_noise_bufs(noise_bufs, randomize_noise)
@@ -394,8 +408,14 @@ class Generator(nn.Module):
         leaves the last up-sampling stage as uint8: hip.rgb_to_uint8's bits without the fp32 image's round trip; planned
         forwards whose decoder ends in a fused stage, `can_emit_uint8`).  `ret["rgb"]` is that tensor."""
         assert len(zs) == 2
-        if eikonal_reg or path_reg:
-            raise NotImplementedError("eikonal_reg / path_reg are training-only (double backward); inference path here")
+        if path_reg:
+            raise NotImplementedError("path_reg is training-only (double backward); inference path here")
+        if eikonal_reg and self.renderer.with_sdf:
+            from . import hip
+            if not hip.nerf_sdf_grad_supported(self.renderer.hidden_dim, self.renderer.N_layers_renderer):
+                raise NotImplementedError(
+                    f"eikonal_reg: the SDF gradient kernel is built for hidden_dim = 256 and depth <= 64; this renderer has "
+                    f"hidden_dim = {self.renderer.hidden_dim}, depth = {self.renderer.N_layers_renderer}")
         if N_rays_grad is not None or sample_idx_h is not None or sample_idx_w is not None:
             raise NotImplementedError("ray sub-sampling is training-only (raises in the reference too, model_v3.py:954-956)")
         if project_noise:
@@ -424,9 +444,14 @@ class Generator(nn.Module):
             if style_render is None and truncation < 1 and (
                     recompute_mean or not hasattr(self, "style_render_mean") or not hasattr(self, "style_decoder_mean")):
                 self.style_render_mean, self.style_decoder_mean = self.get_mean_latent(10000, dev)
-            return self._planned_forward(plan, zs, cam_poses, per_view(focals), per_view(near), per_view(far), perturb_u,
-                                         noise_bufs, truncation, style_render, style_decoder, return_sdf, return_xyz,
-                                         fresh_perturb=fresh_perturb, styles_resident=styles_resident, rgb_out=rgb_out)
+            ret = self._planned_forward(plan, zs, cam_poses, per_view(focals), per_view(near), per_view(far), perturb_u,
+                                        noise_bufs, truncation, style_render, style_decoder, return_sdf, return_xyz,
+                                        fresh_perturb=fresh_perturb, styles_resident=styles_resident, rgb_out=rgb_out)
+            if eikonal_reg:
+                # at the points the forward sampled: the plan's own FiLM table and the jitter that run used (no second draw)
+                ret["eikonal_term"] = self._eikonal_term(cam_poses, per_view(focals), per_view(near), per_view(far), None, img_size,
+                                                         N, plan.last_perturb_u, static, film=plan.film)
+            return ret
         if rgb_out is not None:
             raise NotImplementedError("rgb_out needs the planned forward (k = 1 decoder with tiled widths, no style mixing)")
         if fresh_perturb:
@@ -441,11 +466,15 @@ class Generator(nn.Module):
             perturb_u=perturb_u, static_viewdirs=nerf_cfg.get("static_viewdirs", False), return_sdf=return_sdf)
         rgb = self.decoder(features=features, styles=style_decoder, rgbd_in=None, noise=noise_bufs)
         m2 = mask.transpose(0, 1).contiguous()
+        eik = None
+        if eikonal_reg:
+            eik = self._eikonal_term(cam_poses, per_view(focals), per_view(near), per_view(far), style_render, img_size, N, perturb_u,
+                                     static)
         return {
             "rgb": rgb,
             "thumb_rgb": thumb_rgb,
             "style_decoder": None,
-            "eikonal_term": None,
+            "eikonal_term": eik,
             "sdf": sdf if return_sdf else None,
             "xyz": xyz if return_xyz else None,
             "mask": m2[0].unsqueeze(1),

@@ -346,6 +346,46 @@ def nerf_render_maps(**kw):
     return features, thumb, xyz, mask
 
 
+def nerf_sdf_grad_supported(hidden, depth):
+    """Host-only: does cips3d_nerf_sdf_grad implement this trunk (hidden 256, depth 1..64)?"""
+    return bool(_lib.load().cips3d_nerf_sdf_grad_supported(int(hidden), int(depth)))
+
+
+def nerf_sdf_grad(*, near_, far_, w_first, packed32, film, layer_bias, w_sigma, b_sigma, B, n_samples, hidden, depth,
+                  img_size=1, cam_poses=None, focals=None, perturb_u=None, x_pts=None, n_rays=0, want_sdf=True, grad_out=None,
+                  sdf_out=None):
+    """d sdf / d pts at every sample point (csrc/nerf_sdf_grad.hip) -> (sdf [B,R,N] or None, grad [B,R,N,3]).  Camera form
+    (cam_poses, focals, img_size[, perturb_u]: the sample positions of nerf_render for the same arguments) or explicit form
+    (x_pts [B,R,N,3], n_rays = R).  grad_out / sdf_out: contiguous fp32 tensors of those shapes to write into."""
+    lib = _lib.load()
+    if not lib.cips3d_nerf_sdf_grad_supported(int(hidden), int(depth)):
+        raise NotImplementedError(f"the SDF gradient kernel is built for hidden_dim = 256 and depth <= 64 (got hidden {hidden}, "
+                                  f"depth {depth})")
+    p = _lib.NerfParams()
+    for f, t in (("near_", near_), ("far_", far_), ("w_first", w_first), ("film", film), ("layer_bias", layer_bias),
+                 ("w_sigma", w_sigma), ("b_sigma", b_sigma)):
+        setattr(p, f, dev_ptr(t, f))
+    p.packed32 = dev_ptr(packed32, "packed32", depth == 1)
+    explicit = x_pts is not None
+    p.cam_poses, p.focals = dev_ptr(cam_poses, "cam_poses", explicit), dev_ptr(focals, "focals", explicit)
+    p.perturb_u = dev_ptr(perturb_u, "perturb_u", True)
+    p.x_pts = dev_ptr(x_pts, "x_pts", True)
+    p.n_rays = int(n_rays) if explicit else 0
+    p.B, p.img_size, p.n_samples, p.hidden, p.depth, p.n_chunks = int(B), int(img_size), int(n_samples), int(hidden), int(depth), 1
+    R = p.n_rays if explicit else p.img_size * p.img_size
+    dev = near_.device
+    grad = torch.empty(p.B, R, p.n_samples, 3, device=dev) if grad_out is None else grad_out
+    sdf = sdf_out if sdf_out is not None else (torch.empty(p.B, R, p.n_samples, device=dev) if want_sdf else None)
+    if tuple(grad.shape) != (p.B, R, p.n_samples, 3) or (sdf is not None and tuple(sdf.shape) != (p.B, R, p.n_samples)):
+        raise RuntimeError(f"grad_out / sdf_out must have shapes {(p.B, R, p.n_samples, 3)} / {(p.B, R, p.n_samples)}")
+    p.sdf = dev_ptr(sdf, "sdf", True)
+    ev = _timed("nerf_sdf_grad")
+    check(lib.cips3d_nerf_sdf_grad(C.byref(p), dev_ptr(grad), stream_ptr()), "cips3d_nerf_sdf_grad")
+    if ev:
+        ev[1].record()
+    return sdf, grad
+
+
 def rays_in_world(cam_poses, focals, img_size, static_viewdirs=False):
     """-> rays_o, rays_d, viewdirs, each [B,S,S,3] (Render.get_rays_in_world)."""
     lib = _lib.load()

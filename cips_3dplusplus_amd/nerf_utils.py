@@ -77,15 +77,26 @@ class Render(object):
         return pts, rays_d, viewdirs, z_vals
 
     @staticmethod
+    def get_eikonal_term(pts, sdf):
+        """nerf_utils.py:221-228 is autograd.grad(sdf, pts, ones): it needs the graph from pts to sdf, which the fused kernels
+        never build."""
+        raise NotImplementedError("get_eikonal_term(pts, sdf) takes plain tensors: there is no graph to differentiate.  Use "
+                                  "VolumeFeatureRenderer.sdf_gradient(...) or VolumeFeatureRenderer.forward(..., "
+                                  "return_eikonal=True), which evaluate d sdf / d pts in the gradient kernel")
+
+    @staticmethod
     @torch.no_grad()
     def volume_integration(rgb, sdf, features, z_vals, rays_d, pts, with_sdf=True, sigmoid_beta=None, return_eikonal=False,
                            raw_noise_std=0., force_background=False):
         """nerf_utils.py:231-338 -> rgb_map, feature_map, xyz, mask (.., 2), eikonal_term (None).  with_sdf=False is the raw
         density branch (softplus of the network output, optionally + raw_noise_std * randn, :288-297), force_background the
-        last-sample override (:309-310).  The eikonal term (a training regulariser built on autograd.grad, :270-275) is not
-        computed."""
+        last-sample override (:309-310).  The eikonal term (autograd.grad of sdf with respect to pts, :270-275) cannot be
+        computed here: plain tensors carry no graph to differentiate."""
         if return_eikonal:
-            raise NotImplementedError("the eikonal term needs double backward (training-only)")
+            raise NotImplementedError("volume_integration receives plain tensors: there is no graph from pts to sdf to "
+                                      "differentiate.  The quantity itself comes from the gradient kernel: "
+                                      "VolumeFeatureRenderer.sdf_gradient(...) or VolumeFeatureRenderer.forward(..., "
+                                      "return_eikonal=True)")
         if with_sdf and sigmoid_beta is None:
             raise ValueError("with_sdf=True needs sigmoid_beta")
         z, lead = _flat_rays(z_vals, 1)

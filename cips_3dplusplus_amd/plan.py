@@ -486,6 +486,9 @@ class ForwardPlan:
         io.cam_poses, io.focals = dev_ptr(cam_poses, "cam_poses"), dev_ptr(focals, "focals")
         io.near_, io.far_ = dev_ptr(near, "near"), dev_ptr(far, "far")
         io.perturb_u = dev_ptr(perturb_u, "perturb_u", allow_none=True)
+        # the per-ray jitter [B, S*S] this run samples with (None: perturbation off), drawn here or given: what a pass that must
+        # revisit the run's sample points needs beside `self.film` (Generator.forward(eikonal_reg=True))
+        self.last_perturb_u = perturb_u
         R = S * S
         sdf = torch.empty(B, R, self.N, device=dev) if return_sdf else None
         io.sdf = dev_ptr(sdf, "sdf", allow_none=True)

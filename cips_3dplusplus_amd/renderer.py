@@ -139,9 +139,10 @@ class VolumeFeatureRenderer(nn.Module):
         self.exact_fp32 = precision == "fp32_exact"
         return self
 
-    def packed32(self):
-        """The exact-fp32 weight stream (None in the default precision), re-made when a weight changes."""
-        if not self.exact_fp32:
+    def packed32(self, force=False):
+        """The exact-fp32 weight stream (None in the default precision), re-made when a weight changes.  force: build it in
+        any precision (the SDF gradient kernel always multiplies on the fp32 matrix instruction)."""
+        if not self.exact_fp32 and not force:
             return None
         key = self._weights_key()
         if self._packed32 is None or self._packed32[0] != key:
@@ -240,6 +241,50 @@ class VolumeFeatureRenderer(nn.Module):
             sdf = sdf.view(B, img_size, img_size, N_samples, 1)
         return thumb, features, sdf, mask, xyz
 
+    def _sdf_grad(self, film, near, far, B, N, **geom):
+        """hip.nerf_sdf_grad with this renderer's weights and the FiLM table `film` [B, D+1, 2, H]."""
+        D, H = self.N_layers_renderer, self.hidden_dim
+        if not hip.nerf_sdf_grad_supported(H, D):
+            raise NotImplementedError(f"the SDF gradient (eikonal term) kernel is built for hidden_dim = 256 and depth <= 64; this "
+                                      f"renderer has hidden_dim = {H}, depth = {D}")
+        net = self.network
+        _, layer_bias = self._derived_buffers()
+        return hip.nerf_sdf_grad(near_=near.float().reshape(B).contiguous(), far_=far.float().reshape(B).contiguous(),
+                                 w_first=net.pts_linears[0].weight, packed32=self.packed32(force=True) if D > 1 else None,
+                                 film=film, layer_bias=layer_bias, w_sigma=net.sigma_linear.weight, b_sigma=net.sigma_linear.bias,
+                                 B=B, n_samples=N, hidden=H, depth=D, **geom)
+
+    @torch.no_grad()
+    def sdf_gradient(self, cam_poses, focals, near, far, styles, img_size, N_samples, perturb_u=None, static_viewdirs=False,
+                     film=None):
+        """d sdf / d pts at the sample points `render` evaluates for the same arguments (the reference's `eikonal_term`,
+        nerf_utils.py:221-228: autograd.grad(sdf, pts, ones) with pts the un-normalised world points) -> sdf (B,S,S,N,1),
+        grad (B,S,S,N,3).  One forward-mode pass through the FiLM-SIREN trunk on the exact-fp32 matrix instruction
+        (csrc/nerf_sdf_grad.hip), whatever `set_precision` says; the view layer is not part of it, so `static_viewdirs` does not
+        change the result.  styles (B, D+1, style_dim), or `film`: a FiLM table [B, D+1, 2, H] computed by the caller (styles
+        is then not read).  No autograd graph: the result is a constant.
+
+        Runs on the caller's stream through the renderer's lane-0 FiLM table: do not issue it from inside a `ViewPipeline` lane
+        (pipeline.py) while that pipeline has views in flight."""
+        if not self.with_sdf:
+            raise NotImplementedError("with_sdf=False: the network's output is a raw density, not a distance (the reference "
+                                      "computes the eikonal term only in its SDF branch)")
+        if not hip.nerf_sdf_grad_supported(self.hidden_dim, self.N_layers_renderer):
+            raise NotImplementedError(f"sdf_gradient: the kernel is built for hidden_dim = 256 and depth <= 64; this renderer has "
+                                      f"hidden_dim = {self.hidden_dim}, depth = {self.N_layers_renderer}")
+        B, dev = cam_poses.shape[0], cam_poses.device
+        if film is None:
+            styles_buf, film, tab = self._film_table(B, dev)
+            styles_buf.copy_(styles)
+            tab.run(B)
+        else:
+            film = film.detach().float().contiguous()
+        R = img_size * img_size
+        sdf, grad = self._sdf_grad(film, near, far, B, N_samples, img_size=img_size, cam_poses=cam_poses.float().contiguous(),
+                                   focals=focals.float().reshape(B).contiguous(),
+                                   perturb_u=None if perturb_u is None else perturb_u.float().reshape(B, R).contiguous())
+        return sdf.view(B, img_size, img_size, N_samples, 1), grad.view(B, img_size, img_size, N_samples, 3)
+
     @torch.no_grad()
     def run_network(self, inputs, viewdirs, styles=None):
         """volume_renderer.py:282-303: per-point (rgb, sdf, features) for normalised points + per-ray view directions."""
@@ -251,10 +296,13 @@ class VolumeFeatureRenderer(nn.Module):
         """The reference entry (volume_renderer.py:192-303): explicit sample points instead of a camera.
         pts (b h w N 3) or (b hw N 3); rays_d / viewdirs (b h w 3) | (b hw 3); z_vals (b h w N) | (b hw N); near / far
         (b 1 1); styles (b, D+1, style_dim) -> rgb_map (.., 3), feature_map (.., C), sdf (.., N, 1), mask (.., 2),
-        xyz (.., 3), eikonal_term (None).  Runs the same fused kernel in its explicit-geometry instantiation;
-        `N_samples_forward` (a memory bound of the reference) is accepted and ignored."""
-        if return_eikonal:
-            raise NotImplementedError("eikonal term needs double backward (training-only)")
+        xyz (.., 3), eikonal_term.  Runs the same fused kernel in its explicit-geometry instantiation;
+        `N_samples_forward` (a memory bound of the reference) is accepted and ignored.
+        return_eikonal: eikonal_term = d sdf / d pts, the shape of `pts` (volume_renderer.py:223-226), from the gradient kernel
+        (`sdf_gradient`; a constant, no graph); None otherwise and for with_sdf=False renderers, as in the reference."""
+        if return_eikonal and self.with_sdf and not hip.nerf_sdf_grad_supported(self.hidden_dim, self.N_layers_renderer):
+            raise NotImplementedError(f"return_eikonal: the SDF gradient kernel is built for hidden_dim = 256 and depth <= 64; this "
+                                      f"renderer has hidden_dim = {self.hidden_dim}, depth = {self.N_layers_renderer}")
         B = pts.shape[0]
         lead = pts.shape[:-2]
         N = pts.shape[-2]
@@ -279,5 +327,8 @@ class VolumeFeatureRenderer(nn.Module):
                         B=B, img_size=1, n_samples=N, hidden=H, depth=D, static_viewdirs=0, n_chunks=n_chunks,
                         sdf=sdf, x_pts=p, x_rays_d=d, x_viewdirs=v, x_z_vals=z, n_rays=R, raw_density=not self.with_sdf,
                         packed32=self.packed32())
+        eik = None
+        if return_eikonal and self.with_sdf:
+            eik = self._sdf_grad(film, near, far, B, N, x_pts=p, n_rays=R, want_sdf=False)[1].view(*lead, N, 3)
         to_rays = lambda t: t.view(B, t.shape[1], R).transpose(1, 2).reshape(*lead, t.shape[1]).contiguous()
-        return to_rays(thumb), to_rays(features), sdf.view(*lead, N, 1), to_rays(mask), to_rays(xyz), None
+        return to_rays(thumb), to_rays(features), sdf.view(*lead, N, 1), to_rays(mask), to_rays(xyz), eik

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 31  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 32  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -239,6 +239,19 @@ int64_t cips3d_nerf_part_floats(int B, int img_size, int hidden, int n_chunks);
 
 /* rays -> samples -> FiLM-SIREN MLP (fp32 MFMA) -> per-chunk alpha compositing. */
 int cips3d_nerf_render(const cips3d_nerf_params* p, void* stream);
+
+/* Gradient of the SDF head with respect to the sample points (the reference's eikonal term, autograd.grad(sdf, pts, ones):
+ * cips3d/nerf_utils.py:221-228), forward mode through the FiLM-SIREN trunk in one kernel (csrc/nerf_sdf_grad.hip).
+ *   grad [B, R, n_samples, 3] = d sdf / d pts at every sample point, pts the UN-normalised world points (the per-view factor
+ *   2 / (far - near) of normalize_points is included); p->sdf [B, R, n_samples] is written too when non-NULL.
+ * Reads of `p`: the geometry (camera form: cam_poses, focals, near_, far_, perturb_u, img_size -- the sample positions of
+ * cips3d_nerf_render for the same arguments; explicit form: x_pts with n_rays, near_, far_), w_first, film, layer_bias, w_sigma,
+ * b_sigma, depth, hidden and packed32 (the exact-fp32 weight stream: the matrix products run on v_mfma_f32_16x16x4_f32 whatever
+ * precision the render call uses; may be NULL at depth 1).  The view layer, the rgb head and every compositing field (part, o_*,
+ * n_chunks, stash, zero_words, ...) are ignored.  No atomics: bit-reproducible.  Never synchronises.
+ * hidden == 256 and depth <= 64, else CIPS3D_E_UNSUPP (cips3d_nerf_sdf_grad_supported: the same answer on the host, no GPU needed). */
+int cips3d_nerf_sdf_grad(const cips3d_nerf_params* p, float* grad, void* stream);
+int cips3d_nerf_sdf_grad_supported(int hidden, int depth);
 
 /* Ordered combination of the chunk partials into the final maps:
  *   features [B,H,R] (channel-major = NCHW), thumb_rgb [B,3,R], xyz [B,3,R], mask [B,2,R]. */
