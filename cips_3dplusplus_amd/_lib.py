@@ -87,6 +87,15 @@ class NerfParams(C.Structure):
                 ("zero_words", C.c_void_p), ("n_zero_words", C.c_int64), ("mask_planar", C.c_int32), ("pad3_", C.c_int32)]
 
 
+class NormalsParams(C.Structure):
+    """cips3d_normals_params (include/cips3d_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "sdf", "grad", "sigmoid_beta", "cam_poses", "focals", "near_", "far_", "perturb_u", "x_z_vals", "x_rays_d", "xyz", "eye",
+        "light", "normal_raw", "normal", "shade", "shade_u8")] + [
+        (n, C.c_int32) for n in ("B", "img_size", "n_samples", "n_rays")] + [
+        (n, C.c_float) for n in ("ka", "kd", "ks", "shininess")]
+
+
 class NerfBwdGeom(C.Structure):
     _fields_ = [("cam_poses", C.c_void_p), ("focals", C.c_void_p), ("near_", C.c_void_p), ("far_", C.c_void_p),
                 ("perturb_u", C.c_void_p), ("B", C.c_int32), ("img_size", C.c_int32), ("n_samples", C.c_int32),
@@ -125,6 +134,7 @@ _SIGS = {
     "cips3d_nerf_fuses_finish": (c_int, [C.POINTER(NerfParams)]),
     "cips3d_nerf_sdf_grad": (c_int, [C.POINTER(NerfParams), c_f32p, C.c_void_p]),
     "cips3d_nerf_sdf_grad_supported": (c_int, [c_int, c_int]),
+    "cips3d_nerf_normals": (c_int, [C.POINTER(NormalsParams), C.c_void_p]),
     "cips3d_nerf_finish": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_finish_rays": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_modulate_weights": (c_int, [c_f32p, c_f32p, c_i64, c_f32p, c_int, c_int, c_int, c_int, c_f32, c_int,
@@ -237,12 +247,14 @@ _SIGS = {
     "cips3d_marching_cubes_count": (c_int, [c_f32p, c_int, c_int, c_int, c_f32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_marching_cubes_emit": (c_int, [c_f32p, c_int, c_int, c_int, c_f32, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
                                            c_int, c_int, C.c_void_p]),
+    "cips3d_marching_cubes_normals": (c_int, [c_f32p, c_int, c_int, c_int, c_f32, C.c_void_p, C.c_void_p, c_f32p, c_int,
+                                              C.c_void_p]),
     "cips3d_mc_table_width": (c_int, []),
     "cips3d_mc_case_table": (c_int, [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 32           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 33           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -250,7 +262,7 @@ def _struct_table():
     """index of cips3d_sizeof_struct -> the ctypes mirror of that struct (plan.py holds the two big ones)."""
     from . import plan
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
-            6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob}
+            6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams}
 
 
 def load(build_if_missing=True):

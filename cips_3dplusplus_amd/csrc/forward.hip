@@ -27,6 +27,7 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 7: return (int64_t)sizeof(cips3d_nerf_bwd_fused_params);
     case 8: return (int64_t)sizeof(cips3d_range);
     case 9: return (int64_t)sizeof(cips3d_reduce_job);
+    case 10: return (int64_t)sizeof(cips3d_normals_params);
     default: return -1;
   }
 }

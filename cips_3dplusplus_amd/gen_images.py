@@ -108,10 +108,19 @@ def vertex_normals(verts, faces):
     return vn / np.maximum(n, 1e-20)
 
 
-def write_obj(path, verts, faces):
+def write_obj(path, verts, faces, normals=None):
+    """normals [V,3] (one per vertex): written as `vn` lines, and the faces as `f a//a b//b c//c`."""
+    if normals is not None and len(normals) != len(verts):
+        raise ValueError(f"write_obj: {len(normals)} normals for {len(verts)} vertices")
     with open(path, "w") as f:
         for v in verts:
             f.write(f"v {v[0]:.7g} {v[1]:.7g} {v[2]:.7g}\n")
-        for t in faces + 1:
-            f.write(f"f {t[0]} {t[1]} {t[2]}\n")
+        if normals is None:
+            for t in faces + 1:
+                f.write(f"f {t[0]} {t[1]} {t[2]}\n")
+        else:
+            for n in normals:
+                f.write(f"vn {n[0]:.7g} {n[1]:.7g} {n[2]:.7g}\n")
+            for t in faces + 1:
+                f.write(f"f {t[0]}//{t[0]} {t[1]}//{t[1]} {t[2]}//{t[2]}\n")
     return path

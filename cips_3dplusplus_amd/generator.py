@@ -276,16 +276,27 @@ class Generator(nn.Module):
                 "sdf": sdf if return_sdf else None, "xyz": xyz if return_xyz else None,
                 "mask": m2[0].unsqueeze(1), "depth": m2[1].unsqueeze(1)}
 
-    def _eikonal_term(self, cam_poses, focals, near, far, style_render, img_size, N, perturb_u, static, film=None):
-        """ret_maps["eikonal_term"] of the inference path: d sdf / d pts at the forward's sample points, (B, img_size^2, N, 3) fp32
-        (model_v3.py:1009-1010 leaves the renderer's layout), a constant; None for with_sdf=False renderers (the reference
-        computes the term only in its SDF branch)."""
+    def _geometry_terms(self, ret, eikonal_reg, return_normal, shade, xyz, cam_poses, focals, near, far, style_render, img_size, N,
+                        perturb_u, static, film=None):
+        """The entries of `ret` that need d sdf / d pts at the forward's sample points, from ONE gradient pass: "eikonal_term"
+        (B, img_size^2, N, 3) fp32 (model_v3.py:1009-1010 leaves the renderer's layout), "normal" (B,3,S,S) and, with `shade`
+        (VolumeFeatureRenderer.normal_map's dict without xyz), "shade" / "shade_u8".  Constants; None for with_sdf=False
+        renderers (the reference computes the term only in its SDF branch)."""
+        if return_normal:
+            ret["normal"] = None
         if not self.renderer.with_sdf:
-            return None
+            return
         B = cam_poses.shape[0]
-        _, grad = self.renderer.sdf_gradient(cam_poses, focals, near, far, style_render, img_size, N, perturb_u=perturb_u,
-                                             static_viewdirs=static, film=film)
-        return grad.view(B, img_size * img_size, N, 3)
+        sdf, grad = self.renderer.sdf_gradient(cam_poses, focals, near, far, style_render, img_size, N, perturb_u=perturb_u,
+                                               static_viewdirs=static, film=film)
+        if eikonal_reg:
+            ret["eikonal_term"] = grad.view(B, img_size * img_size, N, 3)
+        if return_normal:
+            out = self.renderer.normal_map(cam_poses, focals, near, far, None, img_size, N, perturb_u=perturb_u, grad=grad, sdf=sdf,
+                                           shade=None if shade is None else dict(shade, xyz=xyz))
+            ret["normal"] = out["normal"]
+            if shade is not None:
+                ret["shade"], ret["shade_u8"] = out["shade"], out["shade_u8"]
 
     def can_emit_uint8(self, B, img_size, N_samples, static_viewdirs=False):
         """True when a forward of this shape can write its image as uint8 (`rgb_out` of dtype uint8)."""
@@ -297,14 +308,19 @@ class Generator(nn.Module):
                 path_reg=False, style_render=None, style_decoder=None, noise_bufs=None, randomize_noise=True,
                 eikonal_reg=False, return_sdf=False, return_xyz=False, N_rays_forward=None, N_rays_grad=None,
                 N_samples_forward=None, nerf_cfg={}, recompute_mean=False, project_noise=False, mesh_path=None,
-                renderer_detach=None, sample_idx_h=None, sample_idx_w=None, perturb_u=None, differentiable=None, **kwargs):
+                renderer_detach=None, sample_idx_h=None, sample_idx_w=None, perturb_u=None, differentiable=None,
+                return_normal=False, **kwargs):
         """model_v3.py:875-1042.  Inference runs the fused path without an autograd graph.  The differentiable op chain of
         `autograd.py` (the inversion loop, projector_v10.py:211-277) is used when `differentiable=True`, or -- with the
         default `differentiable=None` -- when gradients are enabled and either an INPUT tensor (cam_poses, style_render,
         style_decoder, a noise buffer) or a DECODER parameter requires them.  Differentiable leaves: those inputs and the
         decoder's parameters.  The renderer's and the mapping networks' weights are constants of that path
         (`optim_render_params: false`, train_cips3d_compcars_v10.yaml:585): if one of them requires grad the call raises
-        instead of silently returning no gradient -- freeze them (`build_generator` does) or call under `torch.no_grad()`."""
+        instead of silently returning no gradient -- freeze them (`build_generator` does) or call under `torch.no_grad()`.
+        return_normal (extension; inference path only): adds ret["normal"] (B,3,S,S), the composited unit surface normal of the
+        thumbnail's pixels (VolumeFeatureRenderer.normal_map at the forward's own sample points; None for with_sdf=False
+        renderers).  The key is absent unless requested; every other entry and torch's generator state are unchanged by it, and
+        with eikonal_reg=True as well one gradient pass serves both."""
         kw = dict(zs=zs, cam_poses=cam_poses, focals=focals, img_size=img_size, near=near, far=far, truncation=truncation,
                   inject_index=inject_index, path_reg=path_reg, style_render=style_render, style_decoder=style_decoder,
                   noise_bufs=noise_bufs, randomize_noise=randomize_noise, eikonal_reg=eikonal_reg, return_sdf=return_sdf,
@@ -312,6 +328,8 @@ class Generator(nn.Module):
                   N_samples_forward=N_samples_forward, nerf_cfg=nerf_cfg, recompute_mean=recompute_mean,
                   project_noise=project_noise, mesh_path=mesh_path, renderer_detach=renderer_detach,
                   sample_idx_h=sample_idx_h, sample_idx_w=sample_idx_w, perturb_u=perturb_u)
+        if return_normal:
+            kw["return_normal"] = True
         if differentiable is None:
             differentiable = False
             if torch.is_grad_enabled():
@@ -341,9 +359,13 @@ class Generator(nn.Module):
     def _forward_grad(self, zs, cam_poses, focals, img_size, near, far, truncation, inject_index, path_reg, style_render,
                       style_decoder, noise_bufs, randomize_noise, eikonal_reg, return_sdf, return_xyz, N_rays_forward,
                       N_rays_grad, N_samples_forward, nerf_cfg, recompute_mean, project_noise, mesh_path, renderer_detach,
-                      sample_idx_h, sample_idx_w, perturb_u):
+                      sample_idx_h, sample_idx_w, perturb_u, return_normal=False):
         from . import autograd as AG
         assert len(zs) == 2
+        if return_normal:
+            raise NotImplementedError("return_normal on the differentiable path: the normal map is composited from d sdf / d pts, a "
+                                      "graph through it means double backward (training-only).  As a constant it comes from the "
+                                      "inference path (call under torch.no_grad()) or from VolumeFeatureRenderer.normal_map")
         if eikonal_reg:
             raise NotImplementedError("eikonal_reg on the differentiable path: a graph through d sdf / d pts means double backward "
                                       "(training-only).  The quantity itself, as a constant, comes from the inference path (call "
@@ -396,7 +418,7 @@ class Generator(nn.Module):
                        eikonal_reg=False, return_sdf=False, return_xyz=False, N_rays_forward=None, N_rays_grad=None,
                        N_samples_forward=None, nerf_cfg={}, recompute_mean=False, project_noise=False, mesh_path=None,
                        renderer_detach=None, sample_idx_h=None, sample_idx_w=None, perturb_u=None, styles_resident=None,
-                       rgb_out=None, **kwargs):
+                       rgb_out=None, return_normal=False, shade=None, **kwargs):
         """styles_resident (extension of the reference's call surface; multiview.sample_multi_view uses it): True = this call is a
         frame of a sequence that renders ONE latent from many cameras (render_video_web_v10.py:1792-1824) -- the previous call of
         the same shape (and stream) already ran the mapping networks, the style heads and the modulate table for exactly these zs /
@@ -406,16 +428,21 @@ class Generator(nn.Module):
         time per call), and a resident call cannot follow it.  Ignored on the per-op path.
         rgb_out (extension): a preallocated contiguous [B, 3, R, R] tensor that receives `rgb` -- float32, or uint8 (the image
         leaves the last up-sampling stage as uint8: hip.rgb_to_uint8's bits without the fp32 image's round trip; planned
-        forwards whose decoder ends in a fused stage, `can_emit_uint8`).  `ret["rgb"]` is that tensor."""
+        forwards whose decoder ends in a fused stage, `can_emit_uint8`).  `ret["rgb"]` is that tensor.
+        shade (extension, with return_normal=True; multiview.sample_multi_view's "shaded" frames): normal_map's `shade` dict
+        without xyz (the call's own map is used) -> ret["shade"] (B,1,S,S), ret["shade_u8"] (B,3,S,S)."""
         assert len(zs) == 2
         if path_reg:
             raise NotImplementedError("path_reg is training-only (double backward); inference path here")
-        if eikonal_reg and self.renderer.with_sdf:
+        if shade is not None and not return_normal:
+            raise ValueError("shade belongs to return_normal=True")
+        if (eikonal_reg or return_normal) and self.renderer.with_sdf:
             from . import hip
             if not hip.nerf_sdf_grad_supported(self.renderer.hidden_dim, self.renderer.N_layers_renderer):
                 raise NotImplementedError(
-                    f"eikonal_reg: the SDF gradient kernel is built for hidden_dim = 256 and depth <= 64; this renderer has "
-                    f"hidden_dim = {self.renderer.hidden_dim}, depth = {self.renderer.N_layers_renderer}")
+                    f"{'eikonal_reg' if eikonal_reg else 'return_normal'}: the SDF gradient kernel is built for hidden_dim = 256 "
+                    f"and depth <= 64; this renderer has hidden_dim = {self.renderer.hidden_dim}, depth = "
+                    f"{self.renderer.N_layers_renderer}")
         if N_rays_grad is not None or sample_idx_h is not None or sample_idx_w is not None:
             raise NotImplementedError("ray sub-sampling is training-only (raises in the reference too, model_v3.py:954-956)")
         if project_noise:
@@ -445,12 +472,15 @@ class Generator(nn.Module):
                     recompute_mean or not hasattr(self, "style_render_mean") or not hasattr(self, "style_decoder_mean")):
                 self.style_render_mean, self.style_decoder_mean = self.get_mean_latent(10000, dev)
             ret = self._planned_forward(plan, zs, cam_poses, per_view(focals), per_view(near), per_view(far), perturb_u,
-                                        noise_bufs, truncation, style_render, style_decoder, return_sdf, return_xyz,
-                                        fresh_perturb=fresh_perturb, styles_resident=styles_resident, rgb_out=rgb_out)
-            if eikonal_reg:
+                                        noise_bufs, truncation, style_render, style_decoder, return_sdf,
+                                        return_xyz or shade is not None, fresh_perturb=fresh_perturb,
+                                        styles_resident=styles_resident, rgb_out=rgb_out)
+            if eikonal_reg or return_normal:
                 # at the points the forward sampled: the plan's own FiLM table and the jitter that run used (no second draw)
-                ret["eikonal_term"] = self._eikonal_term(cam_poses, per_view(focals), per_view(near), per_view(far), None, img_size,
-                                                         N, plan.last_perturb_u, static, film=plan.film)
+                self._geometry_terms(ret, eikonal_reg, return_normal, shade, ret["xyz"], cam_poses, per_view(focals), per_view(near),
+                                     per_view(far), None, img_size, N, plan.last_perturb_u, static, film=plan.film)
+            if not return_xyz:
+                ret["xyz"] = None
             return ret
         if rgb_out is not None:
             raise NotImplementedError("rgb_out needs the planned forward (k = 1 decoder with tiled widths, no style mixing)")
@@ -466,17 +496,17 @@ class Generator(nn.Module):
             perturb_u=perturb_u, static_viewdirs=nerf_cfg.get("static_viewdirs", False), return_sdf=return_sdf)
         rgb = self.decoder(features=features, styles=style_decoder, rgbd_in=None, noise=noise_bufs)
         m2 = mask.transpose(0, 1).contiguous()
-        eik = None
-        if eikonal_reg:
-            eik = self._eikonal_term(cam_poses, per_view(focals), per_view(near), per_view(far), style_render, img_size, N, perturb_u,
-                                     static)
-        return {
+        ret = {
             "rgb": rgb,
             "thumb_rgb": thumb_rgb,
             "style_decoder": None,
-            "eikonal_term": eik,
+            "eikonal_term": None,
             "sdf": sdf if return_sdf else None,
             "xyz": xyz if return_xyz else None,
             "mask": m2[0].unsqueeze(1),
             "depth": m2[1].unsqueeze(1),
         }
+        if eikonal_reg or return_normal:
+            self._geometry_terms(ret, eikonal_reg, return_normal, shade, xyz, cam_poses, per_view(focals), per_view(near),
+                                 per_view(far), style_render, img_size, N, perturb_u, static)
+        return ret

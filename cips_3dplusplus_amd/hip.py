@@ -386,6 +386,70 @@ def nerf_sdf_grad(*, near_, far_, w_first, packed32, film, layer_bias, w_sigma, 
     return sdf, grad
 
 
+PHONG_DEFAULTS = dict(ka=0.1, kd=0.65, ks=0.2, shininess=64.0)     # the reference's create_mesh_renderer; pytorch3d's shininess
+
+
+def nerf_normals(*, sdf, grad, sigmoid_beta, B, n_samples, img_size=1, cam_poses=None, focals=None, near_=None, far_=None,
+                 perturb_u=None, x_z_vals=None, x_rays_d=None, n_rays=0, xyz=None, eye=None, light=None, ka=None, kd=None,
+                 ks=None, shininess=None, want=("normal_raw", "normal"), normal_raw_out=None, normal_out=None, shade_out=None,
+                 shade_u8_out=None):
+    """Composited normals / Phong-shaded frame (csrc/nerf_normals.hip) -> dict with the entries named in `want` (and every
+    entry a `*_out` tensor was given for): normal_raw, normal [B,3,R] fp32, shade [B,R] fp32, shade_u8 [B,3,R] uint8.
+    sdf [B,R,N], grad [B,R,N,3]: nerf_sdf_grad's outputs.  Camera form (cam_poses, focals, near_, far_, img_size[, perturb_u]) or
+    explicit form (x_z_vals [B,R,N], x_rays_d [B,R,3], n_rays = R).  The shade outputs need xyz [B,3,R], eye [B,3], light [B,3];
+    ka / kd / ks / shininess default to PHONG_DEFAULTS."""
+    lib = _lib.load()
+    outs = {"normal_raw": normal_raw_out, "normal": normal_out, "shade": shade_out, "shade_u8": shade_u8_out}
+    names = [n for n in outs if n in want or outs[n] is not None]
+    unknown = [n for n in want if n not in outs]
+    if unknown or not names:
+        raise RuntimeError(f"nerf_normals: want must name some of {tuple(outs)}, got {tuple(want)}")
+    if any(n in names for n in ("shade", "shade_u8")) and (xyz is None or eye is None or light is None):
+        raise RuntimeError("nerf_normals: the shade outputs need xyz, eye and light")
+    explicit = x_z_vals is not None
+    p = _lib.NormalsParams()
+    p.sdf, p.grad, p.sigmoid_beta = dev_ptr(sdf, "sdf"), dev_ptr(grad, "grad"), dev_ptr(sigmoid_beta, "sigmoid_beta")
+    for f, t in (("cam_poses", cam_poses), ("focals", focals), ("near_", near_), ("far_", far_)):
+        setattr(p, f, dev_ptr(t, f, explicit))
+    p.perturb_u = dev_ptr(perturb_u, "perturb_u", True)
+    p.x_z_vals, p.x_rays_d = dev_ptr(x_z_vals, "x_z_vals", True), dev_ptr(x_rays_d, "x_rays_d", not explicit)
+    p.xyz, p.eye, p.light = dev_ptr(xyz, "xyz", True), dev_ptr(eye, "eye", True), dev_ptr(light, "light", True)
+    p.B, p.img_size, p.n_samples, p.n_rays = int(B), int(img_size), int(n_samples), int(n_rays) if explicit else 0
+    R = p.n_rays if explicit else p.img_size * p.img_size
+    if tuple(sdf.shape) != (p.B, R, p.n_samples) or tuple(grad.shape) != (p.B, R, p.n_samples, 3):
+        raise RuntimeError(f"nerf_normals: sdf / grad must have shapes {(p.B, R, p.n_samples)} / {(p.B, R, p.n_samples, 3)}")
+    for name, t, shape in (("perturb_u", perturb_u, (p.B, R)), ("x_z_vals", x_z_vals, (p.B, R, p.n_samples)),
+                           ("x_rays_d", x_rays_d, (p.B, R, 3)), ("xyz", xyz, (p.B, 3, R)), ("eye", eye, (p.B, 3)),
+                           ("light", light, (p.B, 3))):
+        if t is not None and t.numel() != _numel(shape):
+            raise RuntimeError(f"nerf_normals: {name} must have {_numel(shape)} elements {shape}, got {tuple(t.shape)}")
+    dev = sdf.device
+    shapes = {"normal_raw": (p.B, 3, R), "normal": (p.B, 3, R), "shade": (p.B, R), "shade_u8": (p.B, 3, R)}
+    ret = {}
+    for n in names:
+        dt = torch.uint8 if n == "shade_u8" else torch.float32
+        t = outs[n] if outs[n] is not None else torch.empty(shapes[n], device=dev, dtype=dt)
+        if t.numel() != _numel(shapes[n]):
+            raise RuntimeError(f"nerf_normals: {n}_out must have {_numel(shapes[n])} elements {shapes[n]}, got {tuple(t.shape)}")
+        setattr(p, n, dev_ptr(t, n + "_out", dtype=dt))
+        ret[n] = t
+    ph = dict(PHONG_DEFAULTS)
+    ph.update({k: v for k, v in (("ka", ka), ("kd", kd), ("ks", ks), ("shininess", shininess)) if v is not None})
+    p.ka, p.kd, p.ks, p.shininess = (float(ph[k]) for k in ("ka", "kd", "ks", "shininess"))
+    ev = _timed("nerf_normals")
+    check(lib.cips3d_nerf_normals(C.byref(p), stream_ptr()), "cips3d_nerf_normals")
+    if ev:
+        ev[1].record()
+    return ret
+
+
+def _numel(shape):
+    n = 1
+    for v in shape:
+        n *= int(v)
+    return n
+
+
 def rays_in_world(cam_poses, focals, img_size, static_viewdirs=False):
     """-> rays_o, rays_d, viewdirs, each [B,S,S,3] (Render.get_rays_in_world)."""
     lib = _lib.load()
@@ -1416,12 +1480,28 @@ def marching_cubes_emit(vol, level, ws, n_verts, n_faces, affine=None):
     return verts, faces
 
 
-def marching_cubes(vol, level=0.0, affine=None):
+def marching_cubes_normals(vol, level, ws, n_verts, affine=None):
+    """cips3d_marching_cubes_normals after marching_cubes_count (same vol, level, workspace) -> unit normals [V,3] fp32 in the
+    emit call's vertex order: the volume's lattice gradient interpolated along each vertex's edge, in the affine's frame."""
+    lib = _lib.load()
+    h, w, d = vol.shape
+    normals = torch.empty(n_verts, 3, dtype=torch.float32, device=vol.device)
+    aff = None if affine is None else (C.c_float * 6)(*[float(v) for pair in affine for v in pair])
+    check(lib.cips3d_marching_cubes_normals(dev_ptr(vol, "vol"), h, w, d, float(level), aff, ws.data_ptr(),
+                                            normals.data_ptr() if n_verts else None, n_verts, stream_ptr()),
+          "cips3d_marching_cubes_normals")
+    return normals
+
+
+def marching_cubes(vol, level=0.0, affine=None, normals=False):
     """Marching cubes on one volume [h,w,d] fp32 -> (verts [V,3] fp32, faces [F,3] int64) on its device (contract:
-    include/cips3d_hip.h).  Reading the two totals is the one host synchronisation; the outputs are allocated from them."""
+    include/cips3d_hip.h).  Reading the two totals is the one host synchronisation; the outputs are allocated from them.
+    normals=True: a third value, the unit vertex normals [V,3] fp32 (marching_cubes_normals)."""
     ws, totals = marching_cubes_count(vol, level)
     n_v, n_f = (int(v) for v in totals.cpu())
     verts, faces = marching_cubes_emit(vol, level, ws, n_v, n_f, affine)
+    if normals:
+        return verts, faces.long(), marching_cubes_normals(vol, level, ws, n_v, affine)
     return verts, faces.long()
 
 

@@ -41,27 +41,31 @@ def align_volume(volume, near=0.88, far=1.12):
     return out.view(volume.shape)
 
 
-def extract_mesh_with_marching_cubes(sdf, level=0.0):
+def extract_mesh_with_marching_cubes(sdf, level=0.0, normals=False):
     """utils.py:206-224 on the aligned volume's first sample: (verts [V,3] fp32, faces [F,3] int64) in the reference's
-    output frame, or None when the volume has no crossing (the reference's caller gets None from its ValueError)."""
+    output frame, or None when the volume has no crossing (the reference's caller gets None from its ValueError).
+    normals=True: (verts, faces, normals [V,3] fp32) -- unit vertex normals in the same frame, the volume's lattice gradient
+    interpolated along each vertex's edge (skimage's grid normals, which the reference drops); they point towards larger
+    values, the side the triangles' winding faces (the reference frame mirrors two axes: positive determinant)."""
     v = _as_4d(sdf)[0].float().contiguous()
     h, w, d = v.shape
-    verts, faces = hip.marching_cubes(v, level, affine=reference_affine(h, w, d))
-    if faces.shape[0] == 0:
+    out = hip.marching_cubes(v, level, affine=reference_affine(h, w, d), normals=normals)
+    if out[1].shape[0] == 0:
         return None
-    return verts, faces
+    return out
 
 
 @torch.no_grad()
 def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_samples=None, locations=None, fov_ang=6,
-                 dist_radius=0.12, near=0.88, far=1.12, level=0.0):
+                 dist_radius=0.12, near=0.88, far=1.12, level=0.0, normals=False):
     """The reference's surface extraction on the renderer only (the decoder is not run): mapping network ->
     `G.renderer.render(..., return_sdf=True)` at resolution^2 rays x N_samples (default: resolution) with perturbation off
     -> align_volume -> marching cubes per view.
 
     zs: a list whose first entry is the renderer's z (B, z_dim), or that tensor; ignored when `style_render` (B, D+1, S) is
     given; both None: one random z.  locations: (B, 2) azimuth / elevation, default the frontal view.
-    Returns {"sdf": (B, S, S, N, 1), "aligned": the same shape, "meshes": [(verts, faces) or None per view]}.
+    Returns {"sdf": (B, S, S, N, 1), "aligned": the same shape, "meshes": [(verts, faces) or None per view]}; with
+    normals=True each mesh is (verts, faces, normals).
 
     Runs on the caller's stream through the renderer's lane-0 tables: do not issue it from inside a `ViewPipeline` lane
     (pipeline.py) while that pipeline has views in flight."""
@@ -86,5 +90,5 @@ def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_
     _, _, sdf, _, _ = G.renderer.render(cam, focal, near_c, far_c, style_render, resolution, N, perturb_u=None,
                                         return_sdf=True)
     aligned = align_volume(sdf, near, far)
-    meshes = [extract_mesh_with_marching_cubes(aligned[b:b + 1], level) for b in range(B)]
+    meshes = [extract_mesh_with_marching_cubes(aligned[b:b + 1], level, normals=normals) for b in range(B)]
     return {"sdf": sdf, "aligned": aligned, "meshes": meshes}

@@ -130,8 +130,8 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     one set of noise buffers, `perturb=False`, a camera trajectory (`yaw` / `circle` / `translate_rotate`), one
     `G(...)` call per `chunk` frames with `truncation=truncation_ratio, return_xyz=True`.  With torch.distributed
     initialised the frames are dealt to the ranks (contiguous blocks) and gathered to rank 0; `rgb` travels as uint8
-    (the `img_tensor_to_pil` step, :1825-1826) unless `to_uint8=False`.  Video encoding / mesh shading stay with the
-    caller (`gen_images.xyz_to_mesh` gives the surface of a frame's `xyz`).
+    (the `img_tensor_to_pil` step, :1825-1826) unless `to_uint8=False`.  Video encoding stays with the
+    caller (`gen_images.xyz_to_mesh` gives the surface of a frame's `xyz`; its shaded picture: `"shaded"` below).
 
     `hoist` (default): the loop renders every frame with the same sample_z, noise_bufs and truncation, so both mapping networks, the
     FiLM table and all modulated / demodulated decoder matrices are the same for the whole sequence: the first call of each call shape
@@ -142,7 +142,13 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     by that kernel, straight into the rank's frame block (`rgb_out`); False: fp32 image + `hip.rgb_to_uint8` (same bits).
     `lanes` (default 2): the rank's calls alternate between that many streams (pipeline.ViewPipeline: frames are independent of each
     other, one frame's launch-bound phases run under another's large kernels); the results are ordered behind all of them before
-    anything reads them.  With `hoist`, every lane computes the sequence's tables once (its first call).  1: one stream."""
+    anything reads them.  With `hoist`, every lane computes the sequence's tables once (its first call).  1: one stream.
+    `gather` may also name "normal" (the composited unit normals, (n,3,S,S) fp32: `G(..., return_normal=True)`) and "shaded": the
+    frame's geometry panel (render_video_web_v10.py:1839-1890) as uint8 (n,3,S,S), landing in one block per rank like `rgb` -- the
+    Phong-shaded depth surface seen from the frame's camera, lit from the reference's (5 sin azim, 0, 5 cos azim) of the frame's
+    trajectory row, computed per pixel from `xyz` and the normal (csrc/nerf_normals.hip) instead of rasterising a mesh.  Neither
+    is computed unless named.  Where a requested call shape has no forward plan the gradient pass goes through the renderer's
+    lane-0 tables (VolumeFeatureRenderer.sdf_gradient), so such a sequence runs on one lane."""
     from . import hip
     from .camera import yaw_trajectory, circle_trajectory, cameras_from_trajectory, translate_rotate_cameras
     dev = next(G.parameters()).device
@@ -174,11 +180,28 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
         noise_bufs = [torch.zeros_like(b) for b in noise_bufs]
 
     from .pipeline import pipeline_for
-    pipe = pipeline_for(G, lanes=lanes if dev.type == "cuda" else 1, device=dev)
-    full_done = [set() for _ in range(pipe.lanes)]     # per lane: call shapes (views per call) whose tables this sequence has computed
     ws = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     lo, hi = view_slice(n_views, dist.get_rank(group) if ws > 1 else 0, ws)
+    want_normal, want_shaded = "normal" in gather, "shaded" in gather
+    if want_normal or want_shaded:
+        if not G.renderer.with_sdf:
+            raise NotImplementedError('gather "normal" / "shaded": a with_sdf=False renderer has no surface normal')
+        static = bool(ncfg.get("static_viewdirs", False))
+        shapes = {min(chunk, hi - a) for a in range(lo, hi, chunk)}
+        if any(G._forward_plan(n, img_size, int(N_samples), static) is None for n in shapes):
+            lanes = 1
+        if hip.nerf_sdf_grad_supported(G.renderer.hidden_dim, G.renderer.N_layers_renderer):
+            # the gradient kernel's cached weight streams are made on first use: make them on the caller's stream, which every
+            # lane is ordered behind, not on whichever lane comes first
+            G.renderer._derived_buffers()
+            if G.renderer.N_layers_renderer > 1:
+                G.renderer.packed32(force=True)
+        # the reference's light follows the camera's azimuth (render_video_web_v10.py:1839-1890)
+        lights = torch.stack([5 * torch.sin(traj[:, 0]), torch.zeros_like(traj[:, 0]), 5 * torch.cos(traj[:, 0])], 1).float().to(dev)
+    pipe = pipeline_for(G, lanes=lanes if dev.type == "cuda" else 1, device=dev)
+    full_done = [set() for _ in range(pipe.lanes)]     # per lane: call shapes (views per call) whose tables this sequence has computed
     frames_u8 = None                   # this rank's uint8 frames land in ONE block (no concatenation copy at the end)
+    shaded_u8 = torch.empty(hi - lo, 3, img_size, img_size, dtype=torch.uint8, device=dev) if want_shaded else None
 
     def render(a, b):
         nonlocal frames_u8
@@ -194,13 +217,21 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
         lane = pipe.next_lane()
         done = full_done[lane]
         cams = (ext[a:b].contiguous(), foc[a:b].contiguous(), near[a:b].contiguous(), far[a:b].contiguous())
+        geom = {}
+        if want_normal or want_shaded:
+            geom["return_normal"] = True
+        if want_shaded:
+            geom["shade"] = dict(light=lights[a:b].contiguous(), u8_out=shaded_u8[a - lo:b - lo])
 
         def one_call():
             nonlocal frames_u8
             with torch.no_grad():
                 r = G(zs=zs, cam_poses=cams[0], focals=cams[1], img_size=img_size, near=cams[2], far=cams[3], noise_bufs=noise_bufs,
                       truncation=truncation_ratio, nerf_cfg=ncfg, return_xyz=True,
-                      styles_resident=hoist and done == {b - a}, rgb_out=direct)
+                      styles_resident=hoist and done == {b - a}, rgb_out=direct, **geom)
+            if want_shaded:
+                r = dict(r)
+                r["shaded"] = r["shade_u8"]
             if to_uint8 and direct is None:
                 r = dict(r)
                 if frames_u8 is None:

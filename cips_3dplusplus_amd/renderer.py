@@ -286,6 +286,51 @@ class VolumeFeatureRenderer(nn.Module):
         return sdf.view(B, img_size, img_size, N_samples, 1), grad.view(B, img_size, img_size, N_samples, 3)
 
     @torch.no_grad()
+    def normal_map(self, cam_poses, focals, near, far, styles, img_size, N_samples, perturb_u=None, film=None, shade=None,
+                   grad=None, sdf=None):
+        """Composited surface normals of the view `render` produces for the same arguments: the render's compositing weights
+        applied to d sdf / d pts (csrc/nerf_normals.hip) -> {"normal_raw": (B,3,S,S) = sum_i w_i grad_i, "normal": (B,3,S,S) =
+        F.normalize(normal_raw) (zero where no sample has weight)}.  Runs `sdf_gradient` first unless its results are handed in
+        (`sdf` (B,S,S,N[,1]) and `grad` (B,S,S,N,3), e.g. a forward's eikonal term); `styles` / `film` as there.
+        shade = dict(light=(B,3), xyz=(B,3,S,S) the render's map[, eye=(B,3): default the camera position cam_poses[:, :, 3]]
+        [, ka, kd, ks, shininess: default hip.PHONG_DEFAULTS][, u8_out: a contiguous uint8 (B,3,S,S) tensor to write into]) adds
+        "shade" (B,1,S,S) fp32 and "shade_u8" (B,3,S,S) uint8: pytorch3d's Phong for a white surface, per pixel -- the picture the
+        reference rasterises from the frame's depth mesh (render_video_web_v10.py:1839-1890), whose vertices are the pixels.
+        The same refusals and the same lane-0 note as `sdf_gradient`."""
+        if not self.with_sdf:
+            raise NotImplementedError("with_sdf=False: the network's output is a raw density, not a distance: it has no surface "
+                                      "normal (the reference computes the gradient only in its SDF branch)")
+        if not hip.nerf_sdf_grad_supported(self.hidden_dim, self.N_layers_renderer):
+            raise NotImplementedError(f"normal_map: the SDF gradient kernel is built for hidden_dim = 256 and depth <= 64; this "
+                                      f"renderer has hidden_dim = {self.hidden_dim}, depth = {self.N_layers_renderer}")
+        B, S, N = cam_poses.shape[0], int(img_size), int(N_samples)
+        R = S * S
+        if grad is None or sdf is None:
+            sdf, grad = self.sdf_gradient(cam_poses, focals, near, far, styles, S, N, perturb_u=perturb_u, film=film)
+        kw, want = {}, ("normal_raw", "normal")
+        if shade is not None:
+            unknown = set(shade) - {"light", "xyz", "eye", "ka", "kd", "ks", "shininess", "u8_out"}
+            if unknown or "light" not in shade or "xyz" not in shade:
+                raise ValueError(f"normal_map: shade needs light and xyz, and may hold eye, ka, kd, ks, shininess, u8_out; got "
+                                 f"{sorted(shade)}")
+            eye = shade.get("eye")
+            eye = cam_poses[:, :, 3] if eye is None else eye
+            kw = dict(xyz=shade["xyz"].float().reshape(B, 3, R).contiguous(), eye=eye.float().reshape(B, 3).contiguous(),
+                      light=shade["light"].float().reshape(B, 3).contiguous(), shade_u8_out=shade.get("u8_out"),
+                      **{k: shade[k] for k in ("ka", "kd", "ks", "shininess") if k in shade})
+            want += ("shade", "shade_u8")
+        out = hip.nerf_normals(sdf=sdf.float().reshape(B, R, N).contiguous(), grad=grad.float().reshape(B, R, N, 3).contiguous(),
+                               sigmoid_beta=self.sigmoid_beta, B=B, n_samples=N, img_size=S,
+                               cam_poses=cam_poses.float().contiguous(), focals=focals.float().reshape(B).contiguous(),
+                               near_=near.float().reshape(B).contiguous(), far_=far.float().reshape(B).contiguous(),
+                               perturb_u=None if perturb_u is None else perturb_u.float().reshape(B, R).contiguous(),
+                               want=want, **kw)
+        ret = {"normal": out["normal"].view(B, 3, S, S), "normal_raw": out["normal_raw"].view(B, 3, S, S)}
+        if shade is not None:
+            ret["shade"], ret["shade_u8"] = out["shade"].view(B, 1, S, S), out["shade_u8"].view(B, 3, S, S)
+        return ret
+
+    @torch.no_grad()
     def run_network(self, inputs, viewdirs, styles=None):
         """volume_renderer.py:282-303: per-point (rgb, sdf, features) for normalised points + per-ray view directions."""
         dirs = viewdirs.unsqueeze(-2).expand(inputs.shape)

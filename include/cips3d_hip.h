@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 32  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 33  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -252,6 +252,36 @@ int cips3d_nerf_render(const cips3d_nerf_params* p, void* stream);
  * hidden == 256 and depth <= 64, else CIPS3D_E_UNSUPP (cips3d_nerf_sdf_grad_supported: the same answer on the host, no GPU needed). */
 int cips3d_nerf_sdf_grad(const cips3d_nerf_params* p, float* grad, void* stream);
 int cips3d_nerf_sdf_grad_supported(int hidden, int depth);
+
+/* Composited surface normals of a rendered view and its Phong-shaded geometry frame (csrc/nerf_normals.hip): the render's
+ * compositing weights applied to the SDF gradient instead of the sample points.
+ *   sdf [B,R,N], grad [B,R,N,3]: what cips3d_nerf_sdf_grad wrote; sigmoid_beta [1] (device).
+ *   Sample spacing, one of two forms: camera form (x_z_vals NULL): cam_poses [B,3,4], focals, near_, far_ [B], perturb_u [B,R]
+ *   or NULL, img_size (R = img_size^2, n_rays = 0) -- z and |d| in cips3d_nerf_render's own expressions; explicit form:
+ *   x_z_vals [B,R,N], x_rays_d [B,R,3], n_rays = R.
+ *   delta_i = (z_{i+1} - z_i) |d|, delta_{N-1} = 1e10 |d|; sigma_i = sigmoid(-sdf_i / beta) / beta; alpha_i = 1 - exp(-sigma_i
+ *   delta_i); T_i = prod_{j<i} (1 - alpha_j + 1e-10); w_i = alpha_i T_i  (cips3d/nerf_utils.py:276-286).
+ * Outputs, each may be NULL, at least one set:
+ *   normal_raw [B,3,R] = sum_i w_i grad_i (the xyz map's formula and layout); normal [B,3,R] = normal_raw / max(|normal_raw|,
+ *   1e-12) (zero, not NaN, where all weights vanish);
+ *   shade [B,R] fp32 and shade_u8 [B,3,R] (three equal channels, floor(255 clamp(shade, 0, 1) + 0.5)); both need xyz [B,3,R]
+ *   (the render's map), eye [B,3] and light [B,3].  With n the unit normal, p = xyz, l = normalize(light - p), v = normalize(eye
+ *   - p), c = n . l:  shade = ka + kd max(c, 0) + ks [c > 0] max(v . (2 c n - l), 0)^shininess  -- pytorch3d's Phong for a white
+ *   vertex colour (the reference's create_mesh_renderer: ka, kd, ks = 0.1, 0.65, 0.2, shininess 64).
+ * Lanes span samples (coalesced reads); the transmittance is a shifted exclusive prefix product over a wave segment, carried
+ * across chunks of 64 samples for N > 64.  No atomics, bit-reproducible, independent of the grid; accurate exp / pow; never
+ * synchronises.  CIPS3D_E_BADARG, nothing launched: a null required pointer, n_samples < 1, no output, a shade output without
+ * xyz / eye / light.  CIPS3D_E_UNSUPP: B R > INT32_MAX. */
+typedef struct cips3d_normals_params {
+  const float* sdf; const float* grad; const float* sigmoid_beta;
+  const float* cam_poses; const float* focals; const float* near_; const float* far_; const float* perturb_u;   /* camera form */
+  const float* x_z_vals; const float* x_rays_d;                                                                   /* explicit form */
+  const float* xyz; const float* eye; const float* light;                                                         /* shading */
+  float* normal_raw; float* normal; float* shade; uint8_t* shade_u8;
+  int32_t B, img_size, n_samples, n_rays;
+  float ka, kd, ks, shininess;
+} cips3d_normals_params;
+int cips3d_nerf_normals(const cips3d_normals_params* p, void* stream);
 
 /* Ordered combination of the chunk partials into the final maps:
  *   features [B,H,R] (channel-major = NCHW), thumb_rgb [B,3,R], xyz [B,3,R], mask [B,2,R]. */
@@ -1131,6 +1161,15 @@ int cips3d_marching_cubes_count(const float* volume, int h, int w, int d, float 
 int cips3d_marching_cubes_emit(const float* volume, int h, int w, int d, float level, const float* affine_host,
                                const void* workspace, float* verts, int32_t* faces, int max_verts, int max_faces,
                                void* stream);
+/* Vertex normals of that mesh: normals [V,3] fp32 in cips3d_marching_cubes_emit's vertex order, after
+ * cips3d_marching_cubes_count with the same volume, level and workspace (the emit call is not needed first; max_verts bounds
+ * every store).  With G(p) the index-space gradient of A at lattice point p (central difference (A[p+1] - A[p-1]) / 2 in the
+ * interior, one-sided at a border: numpy.gradient, edge_order = 1; x <-> column, y <-> row, z <-> depth), the vertex on edge
+ * a -> b = a + e_axis with the emit kernel's t gets  g = (1 - t) G(a) + t G(b),  n_k = g_k / scale_k (the affine's scales
+ * affine_host[0], [2], [4]; NULL: 1),  n = n / max(|n|, 1e-12).  The normal points towards larger values: for an affine of
+ * positive determinant, the side the triangles' winding faces.  These are the grid normals of skimage's marching_cubes. */
+int cips3d_marching_cubes_normals(const float* volume, int h, int w, int d, float level, const float* affine_host,
+                                  const void* workspace, float* normals, int max_verts, void* stream);
 /* The case table (tools/gen_mc_table.py), host only: corner c = x + 2y + 4z of a cell, case bit c = corner c inside; cube
  * edge e of axis e / 4 starts at corner (0, e&1, e>>1) for x-edges, (e&1, 0, e>>1) for y-edges, (e&1, e>>1, 0) for
  * z-edges (e &= 3).  tri_count_host [256]; tri_edges_host [256][3 * cips3d_mc_table_width()], -1 past the count. */

@@ -1,8 +1,8 @@
 """Frontal marching-cubes mesh of a generator (cips_3dplusplus_amd.mesh.surface_mesh), written as an OBJ file.
 
-    python tools/extract_mesh.py [--ckpt DIR] [--depth 2] [--seed 0] [--resolution 128] [--out mesh.obj] [--time]
+    python tools/extract_mesh.py [--ckpt DIR] [--depth 2] [--seed 0] [--resolution 128] [--out mesh.obj] [--normals] [--time]
 
-Without --ckpt the generator is the FFHQ 256^2 configuration with synthetic weights (`--depth` renderer layers).  With
+--normals writes the vertex normals too (`vn` lines, `f a//a b//b c//c`).  Without --ckpt the generator is the FFHQ 256^2 configuration with synthetic weights (`--depth` renderer layers).  With
 --time it prints one JSON line of device-event timings (ms, median of --reps runs) of the renderer-only SDF pass, the
 alignment, the two marching-cubes calls and the whole surface_mesh call, with V and F; and the same three mesh steps on
 an analytic sphere (radius 0.3 n) in an n^3 volume, n = --resolution, whose triangle count does not depend on weights.
@@ -50,6 +50,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--resolution", type=int, default=128)
     ap.add_argument("--out", default="mesh.obj")
+    ap.add_argument("--normals", action="store_true")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--reps", type=int, default=11)
     args = ap.parse_args()
@@ -61,11 +62,11 @@ def main():
         G = pkg.build_generator(configs.ffhq_G_cfg(256, args.depth), dev, seed=args.seed)
     S = args.resolution
     z = torch.randn(1, G.z_dim, generator=torch.Generator().manual_seed(args.seed)).to(dev)
-    out = mesh.surface_mesh(G, zs=[z], resolution=S)
+    out = mesh.surface_mesh(G, zs=[z], resolution=S, normals=args.normals)
     m = out["meshes"][0]
     if m is not None:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        write_obj(args.out, m[0].cpu().numpy(), m[1].cpu().numpy())
+        write_obj(args.out, m[0].cpu().numpy(), m[1].cpu().numpy(), m[2].cpu().numpy() if args.normals else None)
         print(f"wrote {args.out}: {m[0].shape[0]} vertices, {m[1].shape[0]} faces")
     else:
         print("no surface: the SDF volume has no zero crossing")
