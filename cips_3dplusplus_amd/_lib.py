@@ -96,6 +96,14 @@ class NormalsParams(C.Structure):
         (n, C.c_float) for n in ("ka", "kd", "ks", "shininess")]
 
 
+class MeshResolveParams(C.Structure):
+    """cips3d_mesh_resolve_params (include/cips3d_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "verts", "faces", "workspace", "keys", "face", "zbuf", "bary", "attr", "base", "attr_out", "normals", "light", "shade",
+        "shade_u8")] + [(n, C.c_int32) for n in ("V", "F", "n_views", "S", "n_attr")] + [
+        (n, C.c_float) for n in ("fill", "ka", "kd", "ks", "shininess")]
+
+
 class NerfBwdGeom(C.Structure):
     _fields_ = [("cam_poses", C.c_void_p), ("focals", C.c_void_p), ("near_", C.c_void_p), ("far_", C.c_void_p),
                 ("perturb_u", C.c_void_p), ("B", C.c_int32), ("img_size", C.c_int32), ("n_samples", C.c_int32),
@@ -251,10 +259,13 @@ _SIGS = {
                                               C.c_void_p]),
     "cips3d_mc_table_width": (c_int, []),
     "cips3d_mc_case_table": (c_int, [C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_raster_workspace_bytes": (c_i64, [c_i64, c_i64, c_int, c_int]),
+    "cips3d_mesh_rasterize": (c_int, [c_f32p, c_i64, C.c_void_p, c_i64, c_f32p, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_resolve": (c_int, [C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 33           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 34           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -262,7 +273,8 @@ def _struct_table():
     """index of cips3d_sizeof_struct -> the ctypes mirror of that struct (plan.py holds the two big ones)."""
     from . import plan
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
-            6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams}
+            6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
+            11: MeshResolveParams}
 
 
 def load(build_if_missing=True):

@@ -28,6 +28,7 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 8: return (int64_t)sizeof(cips3d_range);
     case 9: return (int64_t)sizeof(cips3d_reduce_job);
     case 10: return (int64_t)sizeof(cips3d_normals_params);
+    case 11: return (int64_t)sizeof(cips3d_mesh_resolve_params);
     default: return -1;
   }
 }

@@ -170,13 +170,13 @@ class ModulatedConv2d(nn.Module):
 
 
 class NoiseInjection(nn.Module):
-    """model_v3.py:317-341 (project_noise is dead code for every released config)."""
+    """model_v3.py:317-341.  `project` is stored as the reference stores it; the projection itself (model_v3.py:344-415) is
+    driven by the call: Generator.forward(project_noise=True, mesh_path=...) projects the noise buffers of every layer
+    through one mesh.NoiseProjector before the decoder consumes them."""
 
     def __init__(self, project=False):
         super().__init__()
-        if project:
-            raise NotImplementedError("project_noise=True needs pytorch3d mesh rendering; unused by released configs")
-        self.project = project
+        self.project = bool(project)
         self.weight = nn.Parameter(torch.zeros(1))
 
 

@@ -213,7 +213,8 @@ class Generator(nn.Module):
         return lane
 
     def _planned_forward(self, plan, zs, cam_poses, focals, near, far, perturb_u, noise_bufs, truncation, style_render,
-                         style_decoder, return_sdf, return_xyz, fresh_perturb=False, styles_resident=None, rgb_out=None):
+                         style_decoder, return_sdf, return_xyz, fresh_perturb=False, styles_resident=None, rgb_out=None,
+                         noise_bound=None):
         from . import hip
         B = plan.B
         z_r = z_d = mean_r = mean_d = None
@@ -269,7 +270,7 @@ class Generator(nn.Module):
             float(truncation), mean_r, mean_d, return_sdf, events, fresh_perturb=fresh_perturb,
             marks=None if marks is None else marks.io_fields(), styles_resident=bool(styles_resident),
             style_stamp=stamp if styles_resident is not None else None, rgb_out=rgb_out,
-            style_refs=refs, views_in_flight=getattr(self, "_views_in_flight", 1))
+            style_refs=refs, views_in_flight=getattr(self, "_views_in_flight", 1), noise_bound=noise_bound)
         # mask arrives as [2,B,S,S] (plan.run): two contiguous [B,1,S,S] maps without a copy
         m2 = mask
         return {"rgb": rgb, "thumb_rgb": thumb, "style_decoder": None, "eikonal_term": None,
@@ -297,6 +298,49 @@ class Generator(nn.Module):
             ret["normal"] = out["normal"]
             if shade is not None:
                 ret["shade"], ret["shade_u8"] = out["shade"], out["shade_u8"]
+
+    def noise_projector(self, mesh, sizes):
+        """The NoiseProjector (mesh.py) of `mesh` -- an OBJ path or a (verts, faces) pair -- for noise layers of these map sizes,
+        kept on the generator and rebuilt when the mesh changes (another path or file time, other tensors or rewritten ones)."""
+        from . import mesh as _mesh
+        if mesh is None:
+            raise ValueError("project_noise=True needs mesh_path: an OBJ path or a (verts, faces) pair")
+        dev = next(self.parameters()).device
+        sizes = tuple(int(s) for s in sizes)
+        if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
+            import os
+            path = os.fspath(mesh)
+            key = ("obj", path, os.path.getmtime(path), sizes)
+        else:
+            verts, faces = mesh[0], mesh[1]
+            key = ("pair", sizes) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (verts, faces))
+        ent = self.__dict__.get("_noise_projector")
+        if ent is None or ent[0] != key:
+            if key[0] == "obj":
+                verts, faces = _mesh.read_obj(path, device=dev)
+            # (the pair stays alive with the entry: its addresses are the key)
+            ent = (key, _mesh.NoiseProjector(verts.to(dev), faces.to(dev), sizes), (verts, faces))
+            self.__dict__["_noise_projector"] = ent
+        return ent[1]
+
+    def _project_noise(self, noise_bufs, cam_poses, mesh, noise_bound):
+        """(projected noise buffers, bound of |noise| over them) for one call.  The bound is `noise_bound` when the caller gave
+        one (a sequence: no synchronisation); otherwise it is measured on the projected maps, which are written through raw
+        pointers and so must not go through the plan's per-(storage, version) cache."""
+        from . import hip, mesh as _mesh
+        if mesh is None:
+            raise ValueError("project_noise=True needs mesh_path: an OBJ path or a (verts, faces) pair")
+        if cam_poses.shape[0] != 1:
+            raise ValueError("project_noise runs at batch 1 (model_v3.py:389)")
+        if any(nb is None for nb in noise_bufs):
+            raise ValueError("project_noise=True needs explicit noise_bufs (Generator.create_noise_bufs)")
+        proj = self.noise_projector(mesh, [nb.shape[-1] for nb in noise_bufs])
+        azim, elev = _mesh.view_angles(cam_poses.float())
+        out = proj.project(noise_bufs, azim, elev)
+        if noise_bound is None:
+            ams = [hip.absmax(o.reshape(-1), B=1) for o in out]
+            noise_bound = max(float(hip.amax_value(a)[0]) for a in ams)
+        return out, float(noise_bound)
 
     def can_emit_uint8(self, B, img_size, N_samples, static_viewdirs=False):
         """True when a forward of this shape can write its image as uint8 (`rgb_out` of dtype uint8)."""
@@ -418,8 +462,14 @@ class Generator(nn.Module):
                        eikonal_reg=False, return_sdf=False, return_xyz=False, N_rays_forward=None, N_rays_grad=None,
                        N_samples_forward=None, nerf_cfg={}, recompute_mean=False, project_noise=False, mesh_path=None,
                        renderer_detach=None, sample_idx_h=None, sample_idx_w=None, perturb_u=None, styles_resident=None,
-                       rgb_out=None, return_normal=False, shade=None, **kwargs):
-        """styles_resident (extension of the reference's call surface; multiview.sample_multi_view uses it): True = this call is a
+                       rgb_out=None, return_normal=False, shade=None, noise_bound=None, **kwargs):
+        """project_noise=True (model_v3.py:387-415 for every noise layer): `noise_bufs` are projected through `mesh_path` -- an
+        OBJ path or a (verts, faces) pair, the frontal marching-cubes mesh -- from this call's camera (`_project_noise`)
+        before the forward, planned or per-op, consumes them unchanged; batch 1, explicit noise buffers.  False launches nothing.
+        noise_bound (extension; multiview.sample_multi_view passes it): an upper bound of |noise| over the call's buffers that
+        replaces the plan's measurement of them -- one value for a whole sequence keeps the range constants, and with them the
+        `styles_resident` promise, valid for buffers that are rewritten in place between frames.
+        styles_resident (extension of the reference's call surface; multiview.sample_multi_view uses it): True = this call is a
         frame of a sequence that renders ONE latent from many cameras (render_video_web_v10.py:1792-1824) -- the previous call of
         the same shape (and stream) already ran the mapping networks, the style heads and the modulate table for exactly these zs /
         styles / truncation / noise buffers, and this call reuses its tables (bit-identical to recomputing them; plan.run checks
@@ -445,11 +495,11 @@ class Generator(nn.Module):
                     f"{self.renderer.N_layers_renderer}")
         if N_rays_grad is not None or sample_idx_h is not None or sample_idx_w is not None:
             raise NotImplementedError("ray sub-sampling is training-only (raises in the reference too, model_v3.py:954-956)")
-        if project_noise:
-            raise NotImplementedError("project_noise needs pytorch3d mesh rendering; unused by released configs")
         # N_rays_forward / N_samples_forward only bound activation memory in the reference; the fused kernel
         # never materialises per-point activations, so they are accepted and ignored.
         noise_bufs = self.get_noise_bufs(noise_bufs, randomize_noise)
+        if project_noise:
+            noise_bufs, noise_bound = self._project_noise(noise_bufs, cam_poses, mesh_path, noise_bound)
 
         B = cam_poses.shape[0]
         dev = cam_poses.device
@@ -474,7 +524,7 @@ class Generator(nn.Module):
             ret = self._planned_forward(plan, zs, cam_poses, per_view(focals), per_view(near), per_view(far), perturb_u,
                                         noise_bufs, truncation, style_render, style_decoder, return_sdf,
                                         return_xyz or shade is not None, fresh_perturb=fresh_perturb,
-                                        styles_resident=styles_resident, rgb_out=rgb_out)
+                                        styles_resident=styles_resident, rgb_out=rgb_out, noise_bound=noise_bound)
             if eikonal_reg or return_normal:
                 # at the points the forward sampled: the plan's own FiLM table and the jitter that run used (no second draw)
                 self._geometry_terms(ret, eikonal_reg, return_normal, shade, ret["xyz"], cam_poses, per_view(focals), per_view(near),

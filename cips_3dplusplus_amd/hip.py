@@ -1514,3 +1514,91 @@ def mc_case_table():
     edges = np.zeros((256, width, 3), np.int32)
     check(lib.cips3d_mc_case_table(cnt.ctypes.data, edges.ctypes.data), "cips3d_mc_case_table")
     return cnt, edges
+
+
+# ---------------------------------------------------------------------------------------------- mesh rasteriser (csrc/mesh_raster.hip)
+def mesh_raster_workspace(n_verts, n_faces, n_views, image_size, device):
+    """(workspace, keys [n,S,S] int64 holding the uint64 keys) for mesh_rasterize / mesh_resolve at these sizes."""
+    lib = _lib.load()
+    nbytes = lib.cips3d_mesh_raster_workspace_bytes(int(n_verts), int(n_faces), int(n_views), int(image_size))
+    if nbytes < 0:
+        check(int(nbytes), "cips3d_mesh_raster_workspace_bytes")
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    keys = torch.empty(int(n_views), int(image_size), int(image_size), dtype=torch.int64, device=device)
+    return ws, keys
+
+
+def mesh_rasterize(verts, faces, cams, image_size, ws=None, keys=None):
+    """cips3d_mesh_rasterize: verts [V,3] fp32, faces [F,3] int32, cams [n,5] fp32 (azim, elev, fov_deg, dist, znear) ->
+    (workspace, keys), enqueued only; the key buffer is cleared by the call.  `ws` / `keys`: buffers of
+    mesh_raster_workspace for the same sizes, reused."""
+    lib = _lib.load()
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("mesh_rasterize: verts must be [V, 3], faces [F, 3]")
+    if cams.dim() != 2 or cams.shape[1] != 5:
+        raise RuntimeError("mesh_rasterize: cams must be [n, 5] = (azim, elev, fov_deg, dist, znear)")
+    V, F, n, S = verts.shape[0], faces.shape[0], cams.shape[0], int(image_size)
+    if ws is None or keys is None:
+        ws, keys = mesh_raster_workspace(V, F, n, S, verts.device)
+    elif keys.shape != (n, S, S) or keys.dtype != torch.int64 or \
+            ws.numel() < lib.cips3d_mesh_raster_workspace_bytes(V, F, n, S):
+        raise RuntimeError("mesh_rasterize: workspace / keys do not fit these sizes")
+    check(lib.cips3d_mesh_rasterize(dev_ptr(verts, "verts") if V else None,
+                                    V, dev_ptr(faces, "faces", dtype=torch.int32) if F else None, F, dev_ptr(cams, "cams"), n, S,
+                                    dev_ptr(ws, "ws", dtype=torch.uint8), dev_ptr(keys, "keys", dtype=torch.int64), stream_ptr()),
+          "cips3d_mesh_rasterize")
+    return ws, keys
+
+
+def mesh_resolve(verts, faces, ws, keys, want=("face", "zbuf", "bary"), attr=None, base=None, fill=0.0, normals=None, light=None,
+                 ka=None, kd=None, ks=None, shininess=None, out=None):
+    """cips3d_mesh_resolve after mesh_rasterize (same verts, faces, workspace, keys) -> dict with the entries named in `want`
+    (and every entry `out` holds a tensor for): face [n,S,S] int32, zbuf [n,S,S], bary [n,S,S,3], attr [n,C,S,S] (needs attr
+    [V,C]; empty pixels take `base` [n,C,S,S] when given, else `fill`), shade [n,S,S], shade_u8 [n,3,S,S] uint8 (need
+    normals [V,3] and light [n,3]).  ka / kd / ks / shininess default to PHONG_DEFAULTS."""
+    lib = _lib.load()
+    n, S = keys.shape[0], keys.shape[1]
+    V, F = verts.shape[0], faces.shape[0]
+    out = dict(out or {})
+    names = set(want) | set(out)
+    unknown = names - {"face", "zbuf", "bary", "attr", "shade", "shade_u8"}
+    if unknown:
+        raise RuntimeError(f"mesh_resolve: unknown outputs {sorted(unknown)}")
+    if "attr" in names and attr is None:
+        raise RuntimeError("mesh_resolve: the attr output needs attr")
+    if names & {"shade", "shade_u8"} and (normals is None or light is None):
+        raise RuntimeError("mesh_resolve: the shade outputs need normals and light")
+    n_attr = 0
+    if "attr" in names:
+        if attr.dim() != 2 or attr.shape[0] != V:
+            raise RuntimeError("mesh_resolve: attr must be [V, C]")
+        n_attr = attr.shape[1]
+    shapes = {"face": ((n, S, S), torch.int32), "zbuf": ((n, S, S), torch.float32), "bary": ((n, S, S, 3), torch.float32),
+              "attr": ((n, n_attr, S, S), torch.float32), "shade": ((n, S, S), torch.float32),
+              "shade_u8": ((n, 3, S, S), torch.uint8)}
+    for name in names:
+        shape, dt = shapes[name]
+        if out.get(name) is None:
+            out[name] = torch.empty(shape, dtype=dt, device=verts.device)
+        elif tuple(out[name].shape) != shape:
+            raise RuntimeError(f"mesh_resolve: {name} must be {shape}")
+    if base is not None and tuple(base.shape) != shapes["attr"][0]:
+        raise RuntimeError(f"mesh_resolve: base must be {shapes['attr'][0]}")
+    if normals is not None and tuple(normals.shape) != (V, 3):
+        raise RuntimeError("mesh_resolve: normals must be [V, 3]")
+    if light is not None and tuple(light.shape) != (n, 3):
+        raise RuntimeError("mesh_resolve: light must be [n, 3]")
+    ph = dict(PHONG_DEFAULTS)
+    ph.update({k: float(v) for k, v in dict(ka=ka, kd=kd, ks=ks, shininess=shininess).items() if v is not None})
+
+    def ptr(t, name, dtype=torch.float32):
+        return None if t is None or t.numel() == 0 else dev_ptr(t, name, dtype=dtype)
+    p = _lib.MeshResolveParams(
+        verts=ptr(verts, "verts"), faces=ptr(faces, "faces", torch.int32), workspace=dev_ptr(ws, "ws", dtype=torch.uint8),
+        keys=dev_ptr(keys, "keys", dtype=torch.int64), face=ptr(out.get("face"), "face", torch.int32),
+        zbuf=ptr(out.get("zbuf"), "zbuf"), bary=ptr(out.get("bary"), "bary"), attr=ptr(attr, "attr") if "attr" in names else None,
+        base=ptr(base, "base"), attr_out=ptr(out.get("attr"), "attr_out"), normals=ptr(normals, "normals"),
+        light=ptr(light, "light"), shade=ptr(out.get("shade"), "shade"), shade_u8=ptr(out.get("shade_u8"), "shade_u8", torch.uint8),
+        V=V, F=F, n_views=n, S=S, n_attr=n_attr, fill=float(fill), **ph)
+    check(lib.cips3d_mesh_resolve(C.byref(p), stream_ptr()), "cips3d_mesh_resolve")
+    return out

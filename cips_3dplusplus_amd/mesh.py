@@ -10,7 +10,13 @@ Marching cubes differs from skimage's Lewiner variant in how ambiguous cells are
 corners form a checkerboard separates its inside corners (tools/gen_mc_table.py), and no interior points are added.  The
 vertex set -- one point on every lattice edge whose ends change sign, linearly interpolated -- is the one both methods
 interpolate; the triangles of ambiguous cells can differ.
+
+The second half rasterises that mesh (csrc/mesh_raster.hip; the reference uses pytorch3d): `rasterize_mesh`, the Phong
+`render_mesh_frames` of exp/cips3d/utils.py:260-308, and `NoiseProjector`, the surface-bound decoder noise of
+models/model_v3.py:344-415 (`NoiseInjection.project_noise`), with the midpoint `subdivide` its mesh ladder needs.
 """
+import math
+
 import torch
 
 from . import hip
@@ -92,3 +98,168 @@ def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_
     aligned = align_volume(sdf, near, far)
     meshes = [extract_mesh_with_marching_cubes(aligned[b:b + 1], level, normals=normals) for b in range(B)]
     return {"sdf": sdf, "aligned": aligned, "meshes": meshes}
+
+
+# ------------------------------------------------------------------------------------------------ rasterisation
+def camera_rows(azim, elev, fov_deg=12.0, dist=1.0, znear=0.01, device=None):
+    """cams [n,5] fp32 = (azim, elev, fov_deg, dist, znear) per view, the rasteriser's camera input (the reference's
+    create_cameras arguments; angles in radians).  Every argument is a number, a sequence or a tensor of n values; device
+    tensors stay on the device (no synchronisation)."""
+    cols = [torch.as_tensor(c, dtype=torch.float32, device=device).reshape(-1) for c in (azim, elev, fov_deg, dist, znear)]
+    n = max(c.numel() for c in cols)
+    if any(c.numel() not in (1, n) for c in cols):
+        raise ValueError("camera_rows: every argument must hold one value or one per view")
+    return torch.stack([c.expand(n) for c in cols], 1).contiguous()
+
+
+def _faces_i32(faces):
+    if faces.numel() and int(faces.shape[0]) > 2 ** 31 - 1:
+        raise ValueError("more than 2^31 - 1 faces")
+    return faces.to(torch.int32).contiguous()
+
+
+def rasterize_mesh(verts, faces, azim, elev, image_size, fov_deg=12.0, dist=1.0, znear=0.01, attrs=None, base=None, fill=0.0,
+                   normals=None, light=None, want=None, ws=None, keys=None, out=None):
+    """Hard z-buffer rasterisation of (verts [V,3] fp32, faces [F,3] int32 / int64) from the cameras (azim, elev) [radians; one
+    value or n], the reference's create_cameras(azim, elev, dist, fov, znear) -> dict:
+      face [n,S,S] int32, zbuf [n,S,S] fp32 (view-space depth), bary [n,S,S,3] fp32 (perspective-correct): -1 where empty;
+      attrs [V,C] given: attr [n,C,S,S], the interpolated vertex attributes; empty pixels take `base` [n,C,S,S] or `fill`;
+      normals [V,3] and light [n,3] given: shade [n,S,S] fp32 and shade_u8 [n,3,S,S], the Phong frame on a white background.
+    `want` restricts the outputs; ws / keys: buffers of hip.mesh_raster_workspace to reuse; out: tensors to write into.
+    Contract: include/cips3d_hip.h (cips3d_mesh_rasterize)."""
+    verts = verts.float().contiguous()
+    f32 = _faces_i32(faces)
+    cams = camera_rows(azim, elev, fov_deg, dist, znear, device=verts.device)
+    if want is None:
+        want = ["face", "zbuf", "bary"] + (["attr"] if attrs is not None else []) + \
+               (["shade", "shade_u8"] if normals is not None and light is not None else [])
+    ws, keys = hip.mesh_rasterize(verts, f32, cams, image_size, ws=ws, keys=keys)
+    return hip.mesh_resolve(verts, f32, ws, keys, want=want, attr=None if attrs is None else attrs.float().contiguous(), base=base,
+                           fill=fill, normals=None if normals is None else normals.float().contiguous(),
+                           light=None if light is None else light.float().contiguous(), out=out)
+
+
+def render_mesh_frames(verts, faces, normals, trajectory, image_size=512, light=None):
+    """The reference's mesh panel (create_cameras / create_mesh_renderer, utils.py:260-308, as the frame loops call it): the
+    Phong picture of the mesh from every row (azim, elev, fov / 2) of `trajectory`, camera fov = 2 trajectory[:,2] degrees at
+    distance 1, point light (5 sin az, 0, 5 cos az) unless `light` [n,3] is given -> uint8 [n,3,S,S], white where empty.
+    The rasteriser is hard (one face per pixel); pytorch3d's soft blending is not reproduced."""
+    traj = torch.as_tensor(trajectory, dtype=torch.float32).to(verts.device)
+    az, el = traj[:, 0], traj[:, 1]
+    if light is None:
+        light = torch.stack([5 * torch.sin(az), torch.zeros_like(az), 5 * torch.cos(az)], 1)
+    out = rasterize_mesh(verts, faces, az, el, image_size, fov_deg=2.0 * traj[:, 2], dist=1.0, normals=normals,
+                         light=light.float().contiguous(), want=("shade_u8",))
+    return out["shade_u8"]
+
+
+def subdivide(verts, faces):
+    """Midpoint subdivision (trimesh.remesh.subdivide's result up to vertex order), torch ops only, any device: the
+    original vertices first, then one midpoint per undirected edge in ascending (min, max) order; face k = (a, b, c) becomes
+    faces 4k .. 4k+3 = (a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca).  -> (verts [V + E, 3], faces [4F, 3] int64)."""
+    faces = faces.long()
+    V, F = verts.shape[0], faces.shape[0]
+    ends = torch.cat([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]], 0)              # ab | bc | ca
+    lo, hi = ends.min(1).values, ends.max(1).values
+    uniq, inv = torch.unique(lo * V + hi, sorted=True, return_inverse=True)                   # one sorted 64-bit key per edge
+    mid = (verts[uniq // V] + verts[uniq % V]) * 0.5
+    ab, bc, ca = (V + inv).view(3, F)
+    a, b, c = faces.unbind(1)
+    new = torch.stack([torch.stack(t, 1) for t in ((a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca))], 1)
+    return torch.cat([verts, mid], 0), new.reshape(4 * F, 3)
+
+
+def subdivision_levels(im_res):
+    """Subdivision steps of the reference's mesh ladder for a noise map of im_res^2 (model_v3.py:360-385): <= 128: 0, 256: 1,
+    above: 3.  The reference tests `im_res == 256` a second time where 512 was meant, so 512 and 1024 both fall through to
+    three steps; kept as written."""
+    if im_res <= 128:
+        return 0
+    if im_res == 256:
+        return 1
+    return 3
+
+
+def read_obj(path, device=None):
+    """(verts [V,3] fp32, faces [F,3] int64, zero-based) from the `v` and `f` lines of an OBJ file; `f` entries may carry
+    /vt/vn suffixes (gen_images.write_obj writes v//vn), everything else is ignored."""
+    vs, fs = [], []
+    with open(path) as fh:
+        for line in fh:
+            if line.startswith("v "):
+                vs.append([float(x) for x in line.split()[1:4]])
+            elif line.startswith("f "):
+                fs.append([int(x.split("/")[0]) - 1 for x in line.split()[1:4]])
+    verts = torch.tensor(vs, dtype=torch.float32).reshape(-1, 3)
+    faces = torch.tensor(fs, dtype=torch.int64).reshape(-1, 3)
+    return verts.to(device), faces.to(device)
+
+
+class NoiseProjector:
+    """NoiseInjection.project_noise for every noise layer of a decoder (model_v3.py:344-415): the mesh, subdivided
+    `subdivision_levels(size)` times for a layer of size^2, carries one N(0,1) value per vertex (`vert_noise[i]` [V_L], drawn
+    once); per frame the mesh is rasterised from the frame's camera at every layer size and the covered pixels of the
+    layer's screen-space map are replaced by the interpolated vertex noise, so the noise sticks to the surface.
+    sizes: the layers' map sizes (noise_bufs[i].shape[-1]); generator: torch generator of the draw; vert_noise: the values
+    themselves (tests).  Workspaces are kept per stream: projections on different streams may be in flight together."""
+
+    def __init__(self, verts, faces, sizes, generator=None, vert_noise=None):
+        self.sizes = [int(s) for s in sizes]
+        verts, faces = verts.float().contiguous(), faces.long()
+        self.meshes = {0: (verts, _faces_i32(faces))}
+        v, f = verts, faces
+        for lvl in range(1, max(subdivision_levels(s) for s in self.sizes) + 1 if self.sizes else 1):
+            v, f = subdivide(v, f)
+            self.meshes[lvl] = (v.contiguous(), _faces_i32(f))
+        self.levels = [subdivision_levels(s) for s in self.sizes]
+        if vert_noise is None:
+            vert_noise = [torch.randn(self.meshes[l][0].shape[0], generator=generator,
+                                      device=verts.device if generator is None else generator.device).to(verts.device)
+                          for l in self.levels]
+        self.vert_noise = [t.float().reshape(-1, 1).contiguous() for t in vert_noise]
+        for t, l in zip(self.vert_noise, self.levels):
+            if t.shape[0] != self.meshes[l][0].shape[0]:
+                raise ValueError(f"vert_noise holds {t.shape[0]} values for a mesh of {self.meshes[l][0].shape[0]} vertices")
+        self._ws = {}
+        self._absmax = None
+
+    def absmax(self):
+        """max |vert_noise| over all layers (one synchronisation, once): interpolation is convex, so no projected value
+        exceeds it."""
+        if self._absmax is None:
+            self._absmax = max([float(t.abs().max()) for t in self.vert_noise if t.numel()] or [0.0])
+        return self._absmax
+
+    def project(self, noise_bufs, azim, elev, fov_deg=12.0, out=None):
+        """One projected map per layer: noise_bufs[i] [1,1,s,s] with its covered pixels replaced; every other pixel is the
+        caller's value bit for bit.  azim / elev: numbers or one-element tensors (device tensors: no synchronisation).  The
+        reference fixes fov = 12 degrees here whatever the trajectory's fov is; batch 1, as there."""
+        if len(noise_bufs) != len(self.sizes):
+            raise ValueError(f"expected {len(self.sizes)} noise buffers, got {len(noise_bufs)}")
+        dev = self.meshes[0][0].device
+        cams = camera_rows(azim, elev, fov_deg, 1.0, 0.01, device=dev)
+        if cams.shape[0] != 1:
+            raise ValueError("project_noise runs at batch 1 (model_v3.py:389)")
+        stream = hip.stream_ptr()
+        done = {}
+        res = []
+        for i, (nb, s, lvl) in enumerate(zip(noise_bufs, self.sizes, self.levels)):
+            if nb is None or tuple(nb.shape) != (1, 1, s, s):
+                raise ValueError(f"noise_bufs[{i}] must be a (1, 1, {s}, {s}) tensor")
+            v, f = self.meshes[lvl]
+            if s not in done:                     # one rasterisation per map size, shared by the layers of that size
+                ws, keys = self._ws.get((stream, s), (None, None))
+                self._ws[(stream, s)] = done[s] = hip.mesh_rasterize(v, f, cams, s, ws=ws, keys=keys)
+            ws, keys = done[s]
+            o = None if out is None else out[i]
+            r = hip.mesh_resolve(v, f, ws, keys, want=("attr",), attr=self.vert_noise[i], base=nb.float().contiguous(),
+                                 out=None if o is None else {"attr": o})
+            res.append(r["attr"])
+        return res
+
+
+def view_angles(cam_poses):
+    """(azim, elev) [B] of camera-to-world poses [B,3,4] from the camera position C = cam_poses[:, :, 3]:
+    azim = atan2(C_x, C_z), elev = asin(C_y / |C|) -- the trajectory row the pose was made from."""
+    c = cam_poses[:, :, 3].double()
+    return torch.atan2(c[:, 0], c[:, 2]).float(), torch.asin(c[:, 1] / c.norm(dim=1)).float()

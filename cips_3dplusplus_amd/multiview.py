@@ -125,7 +125,7 @@ def render_views_sharded(render_fn, n_views, keys=("rgb",), dst=0, group=None, c
 def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, truncation_ratio=0.5, N_samples=128,
                       zero_noise_bufs=False, noise_bufs=None, azim_range=(-0.77, 0.77), elev=0.0, circle=None,
                       trans_max=0.04, only_rotate=False, chunk=1, gather=("rgb", "thumb_rgb", "xyz"), to_uint8=True,
-                      group=None, hoist=True, uint8_in_kernel=True, lanes=2):
+                      group=None, hoist=True, uint8_in_kernel=True, lanes=2, project_noise=None):
     """The frame loop of `_sample_multi_view_web` (render_video_web_v10.py:1651-1899) without the web page: one z pair,
     one set of noise buffers, `perturb=False`, a camera trajectory (`yaw` / `circle` / `translate_rotate`), one
     `G(...)` call per `chunk` frames with `truncation=truncation_ratio, return_xyz=True`.  With torch.distributed
@@ -148,7 +148,13 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     Phong-shaded depth surface seen from the frame's camera, lit from the reference's (5 sin azim, 0, 5 cos azim) of the frame's
     trajectory row, computed per pixel from `xyz` and the normal (csrc/nerf_normals.hip) instead of rasterising a mesh.  Neither
     is computed unless named.  Where a requested call shape has no forward plan the gradient pass goes through the renderer's
-    lane-0 tables (VolumeFeatureRenderer.sdf_gradient), so such a sequence runs on one lane."""
+    lane-0 tables (VolumeFeatureRenderer.sdf_gradient), so such a sequence runs on one lane.
+    `project_noise`: a (verts, faces) pair or an OBJ path -- the frontal marching-cubes mesh (render_video_web_v10.py:237-269,
+    `mesh_path=` at :307): every frame's noise buffers are projected through it from the frame's camera first
+    (`G(project_noise=True, mesh_path=...)`, mesh.NoiseProjector), so the decoder's noise sticks to the surface.  chunk must be 1
+    (the projection runs at batch 1).  Barycentric interpolation is convex, so max(|noise_bufs|, |vertex noise|) bounds every
+    frame's maps: it is measured once here and handed to every call (`noise_bound=`), which keeps the range constants, and with
+    them `hoist`, valid without a measurement per frame; every call writes fresh maps on its own lane's stream."""
     from . import hip
     from .camera import yaw_trajectory, circle_trajectory, cameras_from_trajectory, translate_rotate_cameras
     dev = next(G.parameters()).device
@@ -178,6 +184,15 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
                 dist.broadcast(b, src=0, group=group)
     if zero_noise_bufs:
         noise_bufs = [torch.zeros_like(b) for b in noise_bufs]
+
+    proj_kw = {}
+    if project_noise is not None:
+        if chunk != 1:
+            raise ValueError("project_noise renders one view per call: chunk must be 1")
+        # built on the caller's stream, which every lane is ordered behind (its subdivided meshes and vertex noise are shared)
+        projector = G.noise_projector(project_noise, [b.shape[-1] for b in noise_bufs])
+        bound = max([projector.absmax()] + [float(b.abs().max()) for b in noise_bufs])
+        proj_kw = dict(project_noise=True, mesh_path=project_noise, noise_bound=bound)
 
     from .pipeline import pipeline_for
     ws = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -228,7 +243,7 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
             with torch.no_grad():
                 r = G(zs=zs, cam_poses=cams[0], focals=cams[1], img_size=img_size, near=cams[2], far=cams[3], noise_bufs=noise_bufs,
                       truncation=truncation_ratio, nerf_cfg=ncfg, return_xyz=True,
-                      styles_resident=hoist and done == {b - a}, rgb_out=direct, **geom)
+                      styles_resident=hoist and done == {b - a}, rgb_out=direct, **geom, **proj_kw)
             if want_shaded:
                 r = dict(r)
                 r["shaded"] = r["shade_u8"]

@@ -435,8 +435,10 @@ class ForwardPlan:
 
     def run(self, z_r, z_d, cam_poses, focals, near, far, perturb_u, noise_bufs, trunc_psi, mean_r, mean_d, return_sdf,
             events=None, fresh_perturb=False, marks=None, styles_resident=False, style_stamp=None, rgb_out=None,
-            style_refs=None, views_in_flight=1):
-        """fresh_perturb: draw the per-ray jitter here (perturb_u must be None) -- together with the decoder's fresh noise in
+            style_refs=None, views_in_flight=1, noise_bound=None):
+        """noise_bound: a caller's upper bound of |noise| over the given buffers; replaces the measurement (`_noise_bound`:
+        cached per storage and version, which a buffer rewritten through raw pointers does not move).
+        fresh_perturb: draw the per-ray jitter here (perturb_u must be None) -- together with the decoder's fresh noise in
         one cips3d_rng_fill launch when both are fresh.
         styles_resident: a frame of a sequence (cips3d_forward_io.styles_resident): the style phase and the modulate table are
         skipped and the plan's tables are used as the last FULL run left them.  `style_stamp` identifies what those tables were
@@ -455,7 +457,10 @@ class ForwardPlan:
             if not hip.FAST_RNG:
                 perturb_u = torch.rand(B, S * S, device=dev)
         io = ForwardIO()
-        io.noise_bound = self._noise_bound(noise_bufs, fresh_noise)
+        if noise_bound is not None and not fresh_noise and getattr(self, "ranged", False):
+            io.noise_bound = float(noise_bound)
+        else:
+            io.noise_bound = self._noise_bound(noise_bufs, fresh_noise)
         stamp = None if style_stamp is None else (style_stamp, float(io.noise_bound))
         if styles_resident:
             # (the FiLM / modulation tables belong to the modules and are shared by every plan of this batch size: nothing may

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 33  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 34  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1175,6 +1175,51 @@ int cips3d_marching_cubes_normals(const float* volume, int h, int w, int d, floa
  * z-edges (e &= 3).  tri_count_host [256]; tri_edges_host [256][3 * cips3d_mc_table_width()], -1 past the count. */
 int cips3d_mc_table_width(void);
 int cips3d_mc_case_table(int32_t* tri_count_host, int32_t* tri_edges_host);
+
+/* ------------------------------------------------------------------ mesh rasteriser (csrc/mesh_raster.hip) */
+
+/* Hard z-buffer rasterisation of a triangle mesh, verts [V,3] fp32, faces [F,3] int32, from n_views cameras into square
+ * S x S frames: the nearest face per pixel, perspective-correct barycentrics, no blending, no culling by winding
+ * (what the reference takes from pytorch3d: exp/cips3d/utils.py:260-308, models/model_v3.py:344-415, with
+ * faces_per_pixel = 1 and no blur).
+ * Camera: cams [n_views,5] fp32 on the device = (azim, elev [radians], fov_deg, dist, znear) per view -- the reference's
+ * create_cameras (pytorch3d's look_at_view_transform + FoVPerspectiveCameras):
+ *   C = dist (cos el sin az, sin el, cos el cos az);  z_ax = -C / |C|;  x_ax = normalize((0,1,0) x z_ax);  y_ax = z_ax x x_ax;
+ *   p_v = ((p - C) . x_ax, (p - C) . y_ax, (p - C) . z_ax);  s = 1 / tan(fov / 2);  x_n = s p_v.x / p_v.z, y_n = s p_v.y / p_v.z
+ *   (+x left, +y up); the centre of pixel (row i, column j) lies at x_n = 1 - (2j + 1) / S, y_n = 1 - (2i + 1) / S.
+ * Coverage: a face covers a pixel when the three edge functions at the pixel centre are >= 0 after orienting by the sign
+ * of the face's screen area (both windings are drawn).  A face of zero screen area is skipped.  A face with ANY vertex at
+ * p_v.z < znear (or p_v.z <= 0) is dropped whole -- there is no clipping against the near plane; the product's mesh sits at
+ * distance ~1 with znear = 0.01.  A face with a vertex id outside [0, V) is skipped.
+ * Depth: view-space z with 1 / z = sum_k b_k / z_k (b: screen-space barycentrics); bary: w_k = (b_k / z_k) z.
+ * Ordering: keys [n_views,S,S] uint64 = (fp32 bits of z) << 32 | face id, lowered with a 64-bit unsigned atomicMin; all ones
+ * = empty.  z > 0, so the bits order like the depths; the minimum does not depend on arrival order: bit-reproducible,
+ * independent of the grid, and equal depths go to the lower face id.
+ *
+ * cips3d_mesh_rasterize clears `keys` itself (part of the call), fills `workspace` (cips3d_mesh_raster_workspace_bytes: the
+ * derived cameras and the projected vertices) and `keys`.  cips3d_mesh_resolve, on the same stream with the same verts,
+ * faces, workspace, keys and sizes, decodes the winners; every output may be NULL:
+ *   face [n,S,S] int32, zbuf [n,S,S] fp32, bary [n,S,S,3] fp32: -1 where empty;
+ *   attr_out [n,n_attr,S,S] = sum_k w_k attr[v_k,:] (attr [V,n_attr]); an empty pixel takes the same pixel of `base`
+ *   [n,n_attr,S,S] when given (base may be attr_out itself), else `fill`;
+ *   shade [n,S,S] fp32, shade_u8 [n,3,S,S] (three equal channels, floor(255 clamp(shade, 0, 1) + 0.5)): cips3d_nerf_normals'
+ *   Phong with n = normalize(sum_k w_k normals[v_k]), p = sum_k w_k verts[v_k], eye = C, light [n,3]; empty pixels are
+ *   white (1.0 / 255).
+ * Neither call synchronises.  CIPS3D_E_BADARG, nothing launched: a null required pointer, a negative size, S < 1, attr_out
+ * without attr or n_attr < 1, a shade output without normals / light.  CIPS3D_E_UNSUPP: V or F > INT32_MAX, S > 16384,
+ * n_views > 65536 (the workspace query returns the same codes). */
+typedef struct cips3d_mesh_resolve_params {
+  const float* verts; const int32_t* faces; const void* workspace; const uint64_t* keys;
+  int32_t* face; float* zbuf; float* bary;
+  const float* attr; const float* base; float* attr_out;
+  const float* normals; const float* light; float* shade; uint8_t* shade_u8;
+  int32_t V, F, n_views, S, n_attr;
+  float fill, ka, kd, ks, shininess;
+} cips3d_mesh_resolve_params;
+int64_t cips3d_mesh_raster_workspace_bytes(int64_t V, int64_t F, int n_views, int S);
+int cips3d_mesh_rasterize(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* cams, int n_views,
+                          int S, void* workspace, uint64_t* keys, void* stream);
+int cips3d_mesh_resolve(const cips3d_mesh_resolve_params* p, void* stream);
 
 #ifdef __cplusplus
 }

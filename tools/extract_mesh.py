@@ -1,11 +1,17 @@
 """Frontal marching-cubes mesh of a generator (cips_3dplusplus_amd.mesh.surface_mesh), written as an OBJ file.
 
     python tools/extract_mesh.py [--ckpt DIR] [--depth 2] [--seed 0] [--resolution 128] [--out mesh.obj] [--normals] [--time]
+                                 [--frames N [--frames-out DIR] [--image-size 512]]
 
 --normals writes the vertex normals too (`vn` lines, `f a//a b//b c//c`).  Without --ckpt the generator is the FFHQ 256^2 configuration with synthetic weights (`--depth` renderer layers).  With
 --time it prints one JSON line of device-event timings (ms, median of --reps runs) of the renderer-only SDF pass, the
 alignment, the two marching-cubes calls and the whole surface_mesh call, with V and F; and the same three mesh steps on
 an analytic sphere (radius 0.3 n) in an n^3 volume, n = --resolution, whose triangle count does not depend on weights.
+--frames N rasterises the mesh from the N-frame yaw trajectory (mesh.render_mesh_frames: the reference's Phong mesh panel) and
+writes frame_000.png ... into --frames-out (default: next to --out); with --time the JSON line gains `raster_ms` / `resolve_ms`
+of those N frames in one call on the sphere mesh at --image-size, and `levels`: V / F of the production mesh after 0, 1 and 3
+midpoint subdivisions (mesh.subdivision_levels) with the one-view rasterise / resolve times of a noise projection at every
+layer size that uses the level.
 """
 import argparse
 import json
@@ -43,6 +49,16 @@ def mesh_steps(vol, level, affine, reps):
     return v, f, t_count, t_emit
 
 
+def raster_steps(verts, faces, cams, size, reps, **resolve_kw):
+    """median device ms of (cips3d_mesh_rasterize, cips3d_mesh_resolve) on preallocated buffers."""
+    f32 = faces.to(torch.int32).contiguous()
+    (ws, keys), t_raster = timed(lambda: hip.mesh_rasterize(verts, f32, cams, size), 1)
+    _, t_raster = timed(lambda: hip.mesh_rasterize(verts, f32, cams, size, ws=ws, keys=keys), reps)
+    out, _ = timed(lambda: hip.mesh_resolve(verts, f32, ws, keys, **resolve_kw), 1)
+    _, t_resolve = timed(lambda: hip.mesh_resolve(verts, f32, ws, keys, out=out, **resolve_kw), reps)
+    return round(t_raster, 4), round(t_resolve, 4)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default=None)
@@ -53,6 +69,9 @@ def main():
     ap.add_argument("--normals", action="store_true")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--reps", type=int, default=11)
+    ap.add_argument("--frames", type=int, default=0)
+    ap.add_argument("--frames-out", default=None)
+    ap.add_argument("--image-size", type=int, default=512)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     if args.ckpt:
@@ -62,7 +81,7 @@ def main():
         G = pkg.build_generator(configs.ffhq_G_cfg(256, args.depth), dev, seed=args.seed)
     S = args.resolution
     z = torch.randn(1, G.z_dim, generator=torch.Generator().manual_seed(args.seed)).to(dev)
-    out = mesh.surface_mesh(G, zs=[z], resolution=S, normals=args.normals)
+    out = mesh.surface_mesh(G, zs=[z], resolution=S, normals=args.normals or args.frames > 0)
     m = out["meshes"][0]
     if m is not None:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -70,6 +89,18 @@ def main():
         print(f"wrote {args.out}: {m[0].shape[0]} vertices, {m[1].shape[0]} faces")
     else:
         print("no surface: the SDF volume has no zero crossing")
+    traj = None
+    if args.frames > 0:
+        from cips_3dplusplus_amd.camera import yaw_trajectory
+        traj = yaw_trajectory(args.frames)
+        if m is not None:
+            from PIL import Image
+            frames = mesh.render_mesh_frames(m[0], m[1], m[2], traj, image_size=args.image_size)
+            fdir = args.frames_out or os.path.dirname(os.path.abspath(args.out))
+            os.makedirs(fdir, exist_ok=True)
+            for i, fr in enumerate(frames.permute(0, 2, 3, 1).cpu().numpy()):
+                Image.fromarray(fr).save(os.path.join(fdir, f"frame_{i:03d}.png"))
+            print(f"wrote {args.frames} mesh frames of {args.image_size}^2 to {fdir}")
     if not args.time:
         return
     reps = args.reps
@@ -89,13 +120,40 @@ def main():
     sph = (torch.sqrt(ax[:, None, None] ** 2 + ax[None, :, None] ** 2 + ax[None, None, :] ** 2) - 0.3 * S).contiguous()
     _, t_salign = timed(lambda: mesh.align_volume(sph[None]), reps)
     sv, sf, t_scount, t_semit = mesh_steps(sph, 0.0, None, reps)
+    extra = {}
+    if traj is not None:
+        # the N mesh frames in one call, on the sphere mesh in the reference's output frame
+        sv_f, sf_f, sn_f = hip.marching_cubes(sph, 0.0, affine=mesh.reference_affine(S, S, S), normals=True)
+        cams = mesh.camera_rows(traj[:, 0], traj[:, 1], 2.0 * traj[:, 2], device=dev)
+        light = torch.stack([5 * torch.sin(traj[:, 0]), torch.zeros(len(traj)), 5 * torch.cos(traj[:, 0])], 1).to(dev).contiguous()
+        t_r, t_s = raster_steps(sv_f, sf_f, cams, args.image_size, reps, want=("shade_u8",), normals=sn_f, light=light)
+        extra.update({"raster_ms": t_r, "resolve_ms": t_s, "frames": args.frames, "image_size": args.image_size})
+        # the production mesh along the reference's subdivision ladder: one view, one noise layer per size
+        levels = []
+        if m is not None:
+            lv, lf = m[0], m[1]
+            cam1 = mesh.camera_rows(0.3, 0.1, 12.0, device=dev)
+            for lvl in range(4):
+                if lvl:
+                    lv, lf = mesh.subdivide(lv, lf)
+                sizes = [s for s in (64, 128, 256, 512, 1024) if mesh.subdivision_levels(s) == lvl]
+                if not sizes:
+                    continue
+                noise = torch.randn(lv.shape[0], 1, device=dev)
+                row = {"level": lvl, "V": int(lv.shape[0]), "F": int(lf.shape[0]), "sizes": {}}
+                for s in sizes:
+                    t_r, t_s = raster_steps(lv.contiguous(), lf, cam1, s, reps, want=("attr",), attr=noise,
+                                            base=torch.randn(1, 1, s, s, device=dev))
+                    row["sizes"][str(s)] = {"raster_ms": t_r, "resolve_ms": t_s}
+                levels.append(row)
+        extra["levels"] = levels
     print(json.dumps({
         "workload": f"surface_mesh depth={args.depth} {S}^2 rays x {S} samples, frontal", "device": torch.cuda.get_device_name(0),
         "render_ms": round(t_render, 4), "align_ms": round(t_align, 4), "count_ms": round(t_count, 4),
         "emit_ms": round(t_emit, 4), "end_to_end_ms": round(t_total, 4), "V": int(v.shape[0]), "F": int(f.shape[0]),
         "sphere": {"n": S, "radius": 0.3 * S, "align_ms": round(t_salign, 4), "count_ms": round(t_scount, 4),
                    "emit_ms": round(t_semit, 4), "V": int(sv.shape[0]), "F": int(sf.shape[0])},
-        "reps": reps}))
+        "reps": reps, **extra}))
 
 
 if __name__ == "__main__":
