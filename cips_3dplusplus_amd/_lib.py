@@ -104,6 +104,22 @@ class MeshResolveParams(C.Structure):
         (n, C.c_float) for n in ("fill", "ka", "kd", "ks", "shininess")]
 
 
+VGG_CONVS = 13                  # CIPS3D_VGG_CONVS
+
+
+class VggCtx(C.Structure):
+    """cips3d_vgg_ctx (include/cips3d_hip.h)."""
+    _fields_ = [("w_fwd", C.c_void_p * VGG_CONVS), ("w_bwd", C.c_void_p * VGG_CONVS), ("bias", C.c_void_p * VGG_CONVS)]
+
+
+class VggIO(C.Structure):
+    """cips3d_vgg_io (include/cips3d_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_convs", C.c_int32),
+                ("normalize", C.c_int32), ("pad_", C.c_int32), ("z", C.c_void_p * VGG_CONVS), ("pooled", C.c_void_p * 4),
+                ("target", C.c_void_p * VGG_CONVS), ("tap_w", C.c_float * VGG_CONVS), ("pad2_", C.c_int32),
+                ("partial", C.c_void_p), ("loss", C.c_void_p), ("gloss", C.c_void_p), ("g", C.c_void_p * 2), ("dx", C.c_void_p)]
+
+
 class NerfBwdGeom(C.Structure):
     _fields_ = [("cam_poses", C.c_void_p), ("focals", C.c_void_p), ("near_", C.c_void_p), ("far_", C.c_void_p),
                 ("perturb_u", C.c_void_p), ("B", C.c_int32), ("img_size", C.c_int32), ("n_samples", C.c_int32),
@@ -262,10 +278,20 @@ _SIGS = {
     "cips3d_mesh_raster_workspace_bytes": (c_i64, [c_i64, c_i64, c_int, c_int]),
     "cips3d_mesh_rasterize": (c_int, [c_f32p, c_i64, C.c_void_p, c_i64, c_f32p, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_mesh_resolve": (c_int, [C.c_void_p, C.c_void_p]),
+    "cips3d_vgg_supported": (c_int, [c_int, c_int, c_int]),
+    "cips3d_vgg_channels": (c_int, [c_int]),
+    "cips3d_vgg_stride": (c_int, [c_int]),
+    "cips3d_vgg_partial_bytes": (c_i64, []),
+    "cips3d_vgg_pack": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
+    "cips3d_vgg_features": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_vgg_loss_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_vgg_loss_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_sizeof_vgg_ctx": (c_int, []),
+    "cips3d_sizeof_vgg_io": (c_int, []),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 34           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 35           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -274,7 +300,7 @@ def _struct_table():
     from . import plan
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
-            11: MeshResolveParams}
+            11: MeshResolveParams, 12: VggCtx, 13: VggIO}
 
 
 def load(build_if_missing=True):

@@ -29,6 +29,8 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 9: return (int64_t)sizeof(cips3d_reduce_job);
     case 10: return (int64_t)sizeof(cips3d_normals_params);
     case 11: return (int64_t)sizeof(cips3d_mesh_resolve_params);
+    case 12: return (int64_t)sizeof(cips3d_vgg_ctx);
+    case 13: return (int64_t)sizeof(cips3d_vgg_io);
     default: return -1;
   }
 }

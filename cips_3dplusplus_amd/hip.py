@@ -1602,3 +1602,16 @@ def mesh_resolve(verts, faces, ws, keys, want=("face", "zbuf", "bary"), attr=Non
         V=V, F=F, n_views=n, S=S, n_attr=n_attr, fill=float(fill), **ph)
     check(lib.cips3d_mesh_resolve(C.byref(p), stream_ptr()), "cips3d_mesh_resolve")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- VGG16 conv loss (csrc/vgg.hip)
+def vgg_supported(B, H, W):
+    """cips3d_vgg_supported as a bool: B >= 1, H and W multiples of 16 (decided on the host; perceptual.VGG16ConvLoss)."""
+    return _lib.load().cips3d_vgg_supported(int(B), int(H), int(W)) == 0
+
+
+def vgg_check_supported(B, H, W):
+    code = _lib.load().cips3d_vgg_supported(int(B), int(H), int(W))
+    if code != 0:
+        raise RuntimeError(f"VGG16 conv loss: B = {B}, H = {H}, W = {W} is outside the size contract (B >= 1, H and W multiples "
+                           f"of 16): {_lib.load().cips3d_strerror(code).decode()}")

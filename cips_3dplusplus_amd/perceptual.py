@@ -1,0 +1,307 @@
+"""VGG16 conv perceptual loss of flip inversion on the HIP kernels of csrc/vgg.hip.
+
+Follows `VGG16ConvLoss` of exp/cips3d/models/vgg_per_loss.py:203-334 (arguments, defaults, the `layers` property, the four
+`loss_weight` tables, `forward` = the weighted, flattened, concatenated taps) and `get_perceptual_fea` of
+models/projector_v10.py:131-151.  The network is torchvision's vgg16.features: 13 3x3 convolutions with ReLU, four max-pools,
+taps at PRE-ReLU conv outputs (`features_N` = the output of `features.N`).
+
+    net = VGG16ConvLoss('vgg16_conv_random')                 # Kaiming-normal fan_out weights, zero bias (vgg_per_loss.py:138-143)
+    net = VGG16ConvLoss('vgg16_conv', weights='vgg16-397923af.pth')      # a torchvision state dict the user has
+    t = net.taps(target)                                     # constants of the loss, computed once
+    loss = net.loss(x, t)                                    # ONE autograd node: sum_k w_k^2 sum (f_k(x) - t_k)^2
+
+`loss` never builds the concatenated vector (8.0 M floats per image at 256^2); `forward` does, for callers who want it.
+There is no CPU path: tensors must live on the GPU.  `vgg16_relu` and `use_stat_loss` are not implemented.
+"""
+import ctypes as C
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+from torch.autograd import Function
+
+from . import _lib, hip
+
+CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)       # vgg16.features.N of conv l
+CHANNELS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+POOL_BEFORE = (0, 0, 1, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0)              # a 2x2/2 max-pool sits in front of conv l
+TAP_CONV = {f"features_{n}": l for l, n in enumerate(CONV_INDEX)}   # tap name -> conv l
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+MODEL_NAMES = ("vgg16_relu", "vgg16_conv", "vgg16_conv_random")
+
+
+def conv_shapes(H, W, n_convs=13):
+    """[(C_l, H_l, W_l)] of the outputs of convs 0 .. n_convs - 1 for an H x W input."""
+    out = []
+    for l in range(n_convs):
+        if POOL_BEFORE[l]:
+            H, W = H // 2, W // 2
+        out.append((CHANNELS[l], H, W))
+    return out
+
+
+def feature_length(H, W, layers):
+    """Length of one sample's row of `forward` (sum_k C_k H_k W_k)."""
+    shapes = conv_shapes(H, W)
+    return sum(shapes[TAP_CONV[k]][0] * shapes[TAP_CONV[k]][1] * shapes[TAP_CONV[k]][2] for k in layers)
+
+
+def random_weights(generator=None):
+    """The reference's `vgg16_conv_random` initialisation (vgg_per_loss.py:138-143): kaiming_normal_(mode='fan_out',
+    nonlinearity='relu') = N(0, 2 / (9 Cout)), zero bias; drawn from `generator` (None: torch's global one)."""
+    ws, cin = [], 3
+    for cout in CHANNELS:
+        std = (2.0 / (cout * 9)) ** 0.5
+        ws.append((torch.empty(cout, cin, 3, 3).normal_(0.0, std, generator=generator), torch.zeros(cout)))
+        cin = cout
+    return ws
+
+
+def weights_from_state_dict(sd):
+    """[(weight, bias)] of the 13 convs from a state dict in the torchvision layout `features.N.weight` / `features.N.bias`
+    (N in CONV_INDEX); `classifier.*` and any other key is ignored.  A missing or mis-shaped entry raises."""
+    ws, cin = [], 3
+    for n, cout in zip(CONV_INDEX, CHANNELS):
+        for suffix, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+            key = f"features.{n}.{suffix}"
+            if key not in sd:
+                raise KeyError(f"VGG16 state dict has no '{key}' (expected the torchvision layout features.N.weight / .bias)")
+            if tuple(sd[key].shape) != shape:
+                raise ValueError(f"'{key}' has shape {tuple(sd[key].shape)}, expected {shape}")
+        ws.append((sd[f"features.{n}.weight"].detach().float().clone(), sd[f"features.{n}.bias"].detach().float().clone()))
+        cin = cout
+    return ws
+
+
+class _Run:
+    """The buffers of one forward call: the io struct, the pre-ReLU tensors z_l it points at, everything it must keep alive."""
+    __slots__ = ("io", "z", "keep", "shape")
+
+
+class _VGGLossFn(Function):
+    @staticmethod
+    def forward(ctx, x, net, targets, tap_w, normalize):
+        run, loss = net._loss_forward(x, targets, tap_w, normalize)
+        ctx.net, ctx.run = net, run
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dx = ctx.net._loss_backward(ctx.run, g)
+        return dx, None, None, None, None
+
+
+class VGG16ConvLoss(nn.Module):
+    def __init__(self, model_name="vgg16_conv", downsample_size=-1, use_stat_loss=False, layers=None, loss_w_dict=None,
+                 weights=None, generator=None, **kwargs):
+        super().__init__()
+        if model_name not in MODEL_NAMES:
+            raise ValueError(f"model_name must be one of {MODEL_NAMES}, got {model_name!r}")
+        if model_name == "vgg16_relu":
+            raise NotImplementedError("vgg16_relu (taps behind the ReLUs) is not implemented; use vgg16_conv or vgg16_conv_random")
+        if use_stat_loss:
+            raise NotImplementedError("use_stat_loss=True is not implemented")
+        self.model_name, self.downsample_size, self.use_stat_loss = model_name, downsample_size, False
+        self._layers = list(self.layers if layers is None else layers)
+        for k in self._layers:
+            if k not in TAP_CONV:
+                raise ValueError(f"unknown tap {k!r}: taps are the conv outputs {sorted(TAP_CONV, key=TAP_CONV.get)}")
+        if sorted(set(self._layers), key=TAP_CONV.get) != self._layers:
+            raise ValueError("layers must be distinct and in network order")
+        self.n_convs = max(TAP_CONV[k] for k in self._layers) + 1       # only the layers up to the deepest tap run
+        if model_name == "vgg16_conv_random":
+            ws = random_weights(generator)
+        else:
+            if weights is None:
+                raise RuntimeError(
+                    "VGG16ConvLoss('vgg16_conv') needs the pretrained VGG16: pass weights= (a path to, or the state dict of, "
+                    "torchvision's vgg16 checkpoint with features.N.weight / features.N.bias), or use "
+                    "model_name='vgg16_conv_random' for the reference's randomly initialised network")
+            sd = torch.load(weights, map_location="cpu") if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__") \
+                else weights
+            ws = weights_from_state_dict(sd)
+        for n, (w, b) in zip(CONV_INDEX, ws):
+            self.register_buffer(f"weight_{n}", w.contiguous())
+            self.register_buffer(f"bias_{n}", b.contiguous())
+        self.loss_w_dict = dict(self.loss_weight("vgg16_conv_1024") if loss_w_dict is None else loss_w_dict)
+        self._packed = {}                # device -> (cips3d_vgg_ctx, the tensors it points at)
+
+    # ---- the reference's tables (vgg_per_loss.py:248-295)
+    @property
+    def layers(self):
+        if getattr(self, "_layers", None) is not None:
+            return list(self._layers)
+        return ["features_2", "features_7", "features_14", "features_21", "features_28"]
+
+    def loss_weight(self, name):
+        tables = {
+            "vgg16_conv_1024": (0.0002, 0.0001, 0.0001, 0.0002, 0.0005),
+            "vgg16_conv_256": (0.001, 0.0006, 0.0005, 0.0005, 0.001),
+            "vgg16_relu_1024": (0.0006, 0.0004, 0.0004, 0.0007, 0.007),
+            "vgg16_relu_256": (0.001, 0.001, 0.001, 0.002, 0.01),
+        }
+        if name not in tables:
+            raise ValueError(f"no loss weight table {name!r}")
+        return dict(zip(("features_2", "features_7", "features_14", "features_21", "features_28"), tables[name]))
+
+    def conv_weights(self):
+        """[(weight, bias)] of the convs, as loaded (torchvision layout order)."""
+        return [(getattr(self, f"weight_{n}"), getattr(self, f"bias_{n}")) for n in CONV_INDEX]
+
+    def state_dict_torchvision(self):
+        """The weights back in the torchvision layout (features.N.weight / features.N.bias)."""
+        sd = {}
+        for n, (w, b) in zip(CONV_INDEX, self.conv_weights()):
+            sd[f"features.{n}.weight"], sd[f"features.{n}.bias"] = w, b
+        return sd
+
+    # ---- device state
+    def _ctx(self, device):
+        key = (device.type, device.index)
+        if key not in self._packed:
+            lib = _lib.load()
+            ctx, keep, srcs = _lib.VggCtx(), [], (C.c_void_p * _lib.VGG_CONVS)()
+            for l in range(self.n_convs):
+                w, b = (t.to(device=device, dtype=torch.float32).contiguous() for t in self.conv_weights()[l])
+                n = w.numel()
+                fwd = torch.empty(n, device=device)
+                bwd = torch.empty(n, device=device) if l > 0 else None
+                keep += [w, b, fwd, bwd]
+                srcs[l] = w.data_ptr()
+                ctx.w_fwd[l], ctx.w_bwd[l], ctx.bias[l] = fwd.data_ptr(), (bwd.data_ptr() if l > 0 else None), b.data_ptr()
+            with torch.cuda.device(device):
+                _lib.check(lib.cips3d_vgg_pack(C.byref(ctx), srcs, self.n_convs, _lib.stream_ptr()), "cips3d_vgg_pack")
+                torch.cuda.current_stream().synchronize()       # the fp32 sources are dropped below
+            self._packed[key] = (ctx, [t for i, t in enumerate(keep) if i % 4 != 0])
+        return self._packed[key][0]
+
+    def _check_input(self, x):
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"VGG16ConvLoss expects [B,3,H,W], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError("VGG16ConvLoss runs on the GPU only (the cips3d HIP path has no CPU fallback)")
+        hip.vgg_check_supported(x.shape[0], x.shape[2], x.shape[3])
+
+    def _prepare(self, x):
+        """-> (network input, normalize flag).  downsample_size > 0: the normalisation and the area down-sampling are torch
+        plumbing in front of the first layer (vgg_per_loss.py:312-316), which then takes its input as it is."""
+        x = x.float()
+        if self.downsample_size > 0:
+            mean = x.new_tensor(IMAGENET_MEAN).view(1, 3, 1, 1)
+            std = x.new_tensor(IMAGENET_STD).view(1, 3, 1, 1)
+            x = ((x + 1) / 2.0 - mean) / std
+            return F.interpolate(x, size=(self.downsample_size, self.downsample_size), mode="area").contiguous(), 0
+        return x.contiguous(), 1
+
+    def _new_run(self, x, normalize):
+        B, _, H, W = x.shape
+        shapes = conv_shapes(H, W, self.n_convs)
+        al = lambda n: (n + 63) // 64 * 64
+        zn = [al(B * c * h * w) for c, h, w in shapes]
+        pn = [al(B * shapes[l - 1][0] * shapes[l][1] * shapes[l][2]) for l in range(self.n_convs) if POOL_BEFORE[l]]
+        buf = torch.empty(sum(zn) + sum(pn), device=x.device)
+        run = _Run()
+        io = _lib.VggIO()
+        io.x, io.B, io.H, io.W, io.n_convs, io.normalize = x.data_ptr(), B, H, W, self.n_convs, normalize
+        off, run.z = 0, []
+        for l, (c, h, w) in enumerate(shapes):
+            zl = buf[off:off + B * c * h * w].view(B, c, h, w)
+            io.z[l] = zl.data_ptr()
+            run.z.append(zl)
+            off += zn[l]
+        for k, n in enumerate(pn):
+            io.pooled[k] = buf.data_ptr() + 4 * off
+            off += n
+        run.io, run.keep, run.shape = io, [x, buf], (B, H, W)
+        return run
+
+    def _features(self, x, normalize):
+        self._check_input(x)
+        run = self._new_run(x, normalize)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().cips3d_vgg_features(C.byref(self._ctx(x.device)), C.byref(run.io), _lib.stream_ptr()),
+                       "cips3d_vgg_features")
+        return run
+
+    def _tap_weights(self, loss_w_dict):
+        d = self.loss_w_dict if loss_w_dict is None else loss_w_dict
+        return [float(d[k]) for k in self._layers]
+
+    def _loss_forward(self, x, targets, tap_w, normalize):
+        self._check_input(x)
+        run = self._new_run(x, normalize)
+        io = run.io
+        for k, t, w in zip(self._layers, targets, tap_w):
+            l = TAP_CONV[k]
+            if tuple(t.shape) != tuple(run.z[l].shape):
+                raise RuntimeError(f"target of {k} has shape {tuple(t.shape)}, the tap is {tuple(run.z[l].shape)}")
+            io.target[l] = _lib.dev_ptr(t, f"target of {k}")
+            io.tap_w[l] = w
+        lib = _lib.load()
+        partial = torch.empty(int(lib.cips3d_vgg_partial_bytes()) // 8, device=x.device, dtype=torch.float64)
+        loss = torch.empty((), device=x.device)
+        io.partial, io.loss = partial.data_ptr(), loss.data_ptr()
+        run.keep += [partial, list(targets)]
+        with torch.cuda.device(x.device):
+            _lib.check(lib.cips3d_vgg_loss_forward(C.byref(self._ctx(x.device)), C.byref(io), _lib.stream_ptr()),
+                       "cips3d_vgg_loss_forward")
+        return run, loss
+
+    def _loss_backward(self, run, gloss):
+        B, H, W = run.shape
+        x = run.keep[0]
+        gloss = gloss.detach().to(device=x.device, dtype=torch.float32).reshape(1).contiguous()
+        g = torch.empty(2, B * 64 * H * W, device=x.device)
+        dx = torch.empty_like(x)
+        io = run.io
+        io.gloss, io.dx = gloss.data_ptr(), dx.data_ptr()
+        io.g[0], io.g[1] = g[0].data_ptr(), g[1].data_ptr()
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().cips3d_vgg_loss_backward(C.byref(self._ctx(x.device)), C.byref(io), _lib.stream_ptr()),
+                       "cips3d_vgg_loss_backward")
+        return dx
+
+    # ---- public
+    def taps(self, x):
+        """The raw (unweighted) taps of x in [-1, 1], [B,C_k,H_k,W_k] each, in `layers` order; no gradient (targets)."""
+        with torch.no_grad():
+            xin, normalize = self._prepare(x)
+            run = self._features(xin, normalize)
+            return [run.z[TAP_CONV[k]].clone() for k in self._layers]
+
+    def forward(self, x, *args, loss_w_dict=None, use_stat_loss=None, **kwargs):
+        """x in [-1, 1], [B,3,H,W] -> [B, sum_k C_k H_k W_k]: every tap flattened (C,H,W), times its weight, concatenated in
+        `layers` order (vgg_per_loss.py:318-334).  Not differentiable: the differentiable form is `loss`."""
+        if use_stat_loss:
+            raise NotImplementedError("use_stat_loss=True is not implemented")
+        ws = self._tap_weights(loss_w_dict)
+        return torch.cat([t.flatten(1) * w for t, w in zip(self.taps(x), ws)], dim=1)
+
+    def loss(self, x, target_taps, loss_w_dict=None):
+        """sum_k w_k^2 sum (tap_k(x) - target_taps[k])^2 = ((forward(x) - forward(target)) ** 2).sum() as one autograd node;
+        differentiable with respect to x only (the targets are constants, the weights are frozen)."""
+        if len(target_taps) != len(self._layers):
+            raise RuntimeError(f"{len(self._layers)} target taps expected ({self._layers}), got {len(target_taps)}")
+        xin, normalize = self._prepare(x)
+        return _VGGLossFn.apply(xin, self, [t.detach() for t in target_taps], self._tap_weights(loss_w_dict), normalize)
+
+    def _thumb(self, image, img_size):
+        return F.interpolate(image, scale_factor=64 / img_size, recompute_scale_factor=False, mode="bicubic", align_corners=False)
+
+    def get_perceptual_fea(self, image, image_thumb=None, img_size=1024, **kwargs):
+        """(features, features_thumb) of an image in [-1, 1] and its 64^2 thumbnail (bicubic from `image` when not given):
+        projector_v10.py:131-151."""
+        if image.dim() == 3:
+            image = image.unsqueeze(0)
+        if image_thumb is None:
+            image_thumb = self._thumb(image, img_size)
+        return self(image, **kwargs), self(image_thumb, **kwargs)
+
+    def get_perceptual_taps(self, image, image_thumb=None, img_size=1024):
+        """The same pair as raw tap lists: the targets `loss` takes."""
+        if image.dim() == 3:
+            image = image.unsqueeze(0)
+        if image_thumb is None:
+            image_thumb = self._thumb(image, img_size)
+        return self.taps(image), self.taps(image_thumb)

@@ -7,9 +7,11 @@ an appearance phase that starts from the truncated NeRF style and flips the deco
 image) pair every `flip_w_decoder_every` steps, and the noise regulariser (:1179-1192).  The batch is the image and its
 horizontal flip rendered from mirrored azimuths.
 
-What is NOT here: the VGG perceptual features (`get_perceptual_fea`, pretrained weights are not obtainable) -- the loss
-is a callable; the default is the surrogate of SURVEY 8d config 5 (MSE on `rgb` + `thumb_weight` x MSE on `thumb_rgb`
-against fixed targets).  Streamlit charts, videos and PSNR logging are out of scope.
+The loss is a callable `loss_fn(rgb, thumb)`.  `perceptual_loss` is the reference's (:980-982, 1170-1174): the VGG16 conv
+features of the image batch and of the 64^2 thumbnail against fixed target features, on the HIP kernels of csrc/vgg.hip
+(perceptual.VGG16ConvLoss; `vgg16_conv_random`, or the pretrained network when the user has its weights).  `surrogate_loss`
+(MSE on `rgb` + `thumb_weight` x MSE on `thumb_rgb` against fixed targets) stays the default of the
+benchmarks.  What is NOT here: the mask blending of :1160-1167; Streamlit charts, videos and PSNR logging.
 
 The three Adam optimisers of the reference run as `optim.HipAdam` (csrc/optim.hip: torch.optim.Adam's update rule, one
 bandwidth-bound launch per 48 tensors; CIPS3D_HIP_ADAM=0: torch.optim.Adam, fused where torch offers it).
@@ -92,6 +94,18 @@ def surrogate_loss(target_rgb, target_thumb, rgb_weight=1.0, thumb_weight=50.0):
             return AG.weighted_mse_pair(rgb, target_rgb.to(rgb.device, torch.float32), rgb_weight,
                                         thumb, target_thumb.to(thumb.device, torch.float32), thumb_weight)
         return rgb_weight * ((rgb - target_rgb) ** 2).mean() + thumb_weight * ((thumb - target_thumb) ** 2).mean()
+    return loss
+
+
+def perceptual_loss(net, target_images, rgb_weight=1.0, thumb_weight=1.0, img_size=1024):
+    """rgb_weight sum (fea(rgb) - fea(target))^2 + thumb_weight sum (fea(thumb) - fea(target_thumb))^2 with `net` a
+    perceptual.VGG16ConvLoss (projector_v10.py:1170-1174).  The target features -- of `target_images` [B,3,S,S] in [-1, 1] and of
+    their bicubic 64^2 thumbnails (`get_perceptual_fea`, :131-151, scale 64 / img_size) -- are computed once (:980-982).  Each of
+    the two terms is one autograd node that never builds the concatenated feature vector."""
+    taps_rgb, taps_thumb = net.get_perceptual_taps(target_images, img_size=img_size)
+
+    def loss(rgb, thumb):
+        return rgb_weight * net.loss(rgb, taps_rgb) + thumb_weight * net.loss(thumb, taps_thumb)
     return loss
 
 

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 34  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 35  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1220,6 +1220,61 @@ int64_t cips3d_mesh_raster_workspace_bytes(int64_t V, int64_t F, int n_views, in
 int cips3d_mesh_rasterize(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* cams, int n_views,
                           int S, void* workspace, uint64_t* keys, void* stream);
 int cips3d_mesh_resolve(const cips3d_mesh_resolve_params* p, void* stream);
+
+/* VGG16 conv perceptual loss of flip inversion (csrc/vgg.hip; reference exp/cips3d/models/vgg_per_loss.py:203-334,
+ * models/projector_v10.py:131-151, 1170-1174).  The network is the 13 convolutions of torchvision's vgg16.features
+ * (conv l = features.{0,2,5,7,10,12,14,17,19,21,24,26,28}[l]; widths cips3d_vgg_channels(l); a 2x2/2 max-pool in front of
+ * convs 2, 4, 7, 10: cips3d_vgg_stride(l) = 1, 1, 2, 2, 4, 4, 4, 8, ...), ReLU between them, frozen weights shared by the
+ * batch.  Every tensor is NCHW fp32.  A "tap" is the PRE-ReLU output of a conv.
+ *
+ *   loss = sum over tap layers l of tap_w[l]^2 * sum (z_l - target[l])^2            (batch and map summed)
+ *
+ * Size contract (cips3d_vgg_supported: 0, CIPS3D_E_UNSUPP or CIPS3D_E_BADARG, decided on the host, nothing launched):
+ * B >= 1; H and W multiples of 16 (>= 16, not necessarily equal); H W <= 2^24.
+ *
+ * cips3d_vgg_pack       weights[l] = conv l's [Cout,Cin,3,3] device tensor -> ctx->w_fwd[l] (the MFMA fragment order) and
+ *                       ctx->w_bwd[l] (transposed and rotated 180 degrees, same order: the data gradient's operand), 9 Cout Cin
+ *                       floats each; conv 0 is copied as it is into w_fwd[0] (1728 floats, w_bwd[0] unused).  Once per network.
+ * cips3d_vgg_features   convs 0 .. n_convs - 1: io->z[l] [B,C_l,H_l,W_l] (pre-ReLU) and io->pooled[k] (max-pool of relu(z)
+ *                       in front of conv {2,4,7,10}[k]).  normalize != 0: x is in [-1, 1] and conv 0 applies
+ *                       ((x + 1) / 2 - mean) / std (ImageNet) first; 0: x is already normalised.
+ * cips3d_vgg_loss_forward   the same, then loss[0] as above over the layers with target[l] != NULL (conv n_convs - 1 must be
+ *                       one).  Deterministic: fp64 partial sums per workgroup, added in a fixed order (partial:
+ *                       cips3d_vgg_partial_bytes() of scratch).
+ * cips3d_vgg_loss_backward  dx [B,3,H,W] = gloss[0] * d loss / d x from the z of the forward call (the only tensors kept), the
+ *                       targets and two gradient buffers g[0], g[1] of B * 64 * H * W floats each.
+ * None of the calls synchronises.  CIPS3D_E_BADARG: a null ctx / io / required pointer, n_convs outside [1, 13]. */
+#define CIPS3D_VGG_CONVS 13
+typedef struct cips3d_vgg_ctx {
+  float* w_fwd[CIPS3D_VGG_CONVS];
+  float* w_bwd[CIPS3D_VGG_CONVS];
+  const float* bias[CIPS3D_VGG_CONVS];
+} cips3d_vgg_ctx;
+typedef struct cips3d_vgg_io {
+  const float* x;                            /* [B,3,H,W] */
+  int32_t B, H, W, n_convs;
+  int32_t normalize, pad_;
+  float* z[CIPS3D_VGG_CONVS];
+  float* pooled[4];
+  const float* target[CIPS3D_VGG_CONVS];     /* NULL: conv l is not a tap */
+  float tap_w[CIPS3D_VGG_CONVS];
+  int32_t pad2_;
+  void* partial;
+  float* loss;                               /* [1] */
+  const float* gloss;                        /* [1]: the loss' incoming gradient */
+  float* g[2];
+  float* dx;
+} cips3d_vgg_io;
+int cips3d_vgg_supported(int B, int H, int W);
+int cips3d_vgg_channels(int conv);
+int cips3d_vgg_stride(int conv);
+int64_t cips3d_vgg_partial_bytes(void);
+int cips3d_vgg_pack(const cips3d_vgg_ctx* ctx, const float* const* weights, int n_convs, void* stream);
+int cips3d_vgg_features(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
+int cips3d_vgg_loss_forward(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
+int cips3d_vgg_loss_backward(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
+int cips3d_sizeof_vgg_ctx(void);
+int cips3d_sizeof_vgg_io(void);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,82 @@
+"""The VGG16 conv perceptual loss of a flip-inversion step, alone: forward + backward at B = 2, 256^2 image + 64^2 thumbnail.
+
+    python tools/bench_perceptual.py [--res 256] [--iters 30]
+
+Prints one JSON line: the HIP node (perceptual.VGG16ConvLoss.loss, csrc/vgg.hip) and, next to it, the same loss evaluated by
+torch's F.conv2d / max_pool2d / relu with autograd on the device -- the only alternative there is.  HIP events around each
+iteration, median after warm-up; both in one process on one device, interleaved by rounds."""
+import argparse, json, os, statistics, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn.functional as F
+from cips_3dplusplus_amd.perceptual import CONV_INDEX, IMAGENET_MEAN, IMAGENET_STD, POOL_BEFORE, VGG16ConvLoss
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--res", type=int, default=256)
+ap.add_argument("--iters", type=int, default=30)
+ap.add_argument("--rounds", type=int, default=3)
+a = ap.parse_args()
+dev = "cuda"
+net = VGG16ConvLoss("vgg16_conv_random", generator=torch.Generator().manual_seed(2))
+g = torch.Generator(device=dev).manual_seed(1)
+target = torch.randn(2, 3, a.res, a.res, device=dev, generator=g).clamp(-1, 1)
+rgb = torch.randn(2, 3, a.res, a.res, device=dev, generator=g).clamp(-1, 1).requires_grad_(True)
+thumb = torch.randn(2, 3, 64, 64, device=dev, generator=g).clamp(-1, 1).requires_grad_(True)
+taps_rgb, taps_thumb = net.get_perceptual_taps(target, img_size=a.res)
+ws = [(w.to(dev), b.to(dev)) for w, b in net.conv_weights()]
+wk = [float(net.loss_w_dict[k]) for k in net.layers]
+mean = torch.tensor(IMAGENET_MEAN, device=dev).view(1, 3, 1, 1)
+std = torch.tensor(IMAGENET_STD, device=dev).view(1, 3, 1, 1)
+
+
+def torch_loss(x, targets):
+    h = ((x + 1) / 2 - mean) / std
+    total, k = 0, 0
+    for l in range(13):
+        if POOL_BEFORE[l]:
+            h = F.max_pool2d(h, 2)
+        z = F.conv2d(h, ws[l][0], ws[l][1], padding=1)
+        if f"features_{CONV_INDEX[l]}" in net.layers:
+            total = total + wk[k] ** 2 * ((z - targets[k]) ** 2).sum()
+            k += 1
+        h = F.relu(z)
+    return total
+
+
+def step_hip():
+    rgb.grad = thumb.grad = None
+    (net.loss(rgb, taps_rgb) + net.loss(thumb, taps_thumb)).backward()
+
+
+def step_torch():
+    rgb.grad = thumb.grad = None
+    (torch_loss(rgb, taps_rgb) + torch_loss(thumb, taps_thumb)).backward()
+
+
+def timed(fn, iters):
+    ms = []
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+step_hip(); g_hip = rgb.grad.clone(); l_hip = float(net.loss(rgb, taps_rgb))
+step_torch(); g_torch = rgb.grad.clone(); l_torch = float(torch_loss(rgb, taps_rgb))
+for fn in (step_hip, step_torch):
+    timed(fn, 5)
+res = {"hip": [], "torch": []}
+for _ in range(a.rounds):
+    res["hip"] += timed(step_hip, a.iters)
+    res["torch"] += timed(step_torch, a.iters)
+shapes = [(2, a.res), (2, 64)]
+flop = sum(2 * B * 2.0 * 9 * sum((3 if l == 0 else net.conv_weights()[l][0].shape[1]) * net.conv_weights()[l][0].shape[0]
+                                 * (S >> sum(POOL_BEFORE[:l + 1])) ** 2 for l in range(13)) for B, S in shapes)
+hip_ms, torch_ms = statistics.median(res["hip"]), statistics.median(res["torch"])
+print(json.dumps({"metric": "VGG16 conv perceptual loss, forward + backward, B=2 image + 64^2 thumbnail", "res": a.res,
+                  "hip_ms": hip_ms, "torch_conv2d_ms": torch_ms, "hip_min_ms": min(res["hip"]), "torch_min_ms": min(res["torch"]),
+                  "flop_fwd_plus_data_grad": flop, "hip_tflops": flop / hip_ms / 1e9,
+                  "loss_hip": l_hip, "loss_torch": l_torch,
+                  "grad_rel_l2_hip_vs_torch": float((g_hip - g_torch).norm() / g_torch.norm()), "device": torch.cuda.get_device_name(0)}))
