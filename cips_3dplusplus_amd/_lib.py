@@ -120,6 +120,17 @@ class VggIO(C.Structure):
                 ("partial", C.c_void_p), ("loss", C.c_void_p), ("gloss", C.c_void_p), ("g", C.c_void_p * 2), ("dx", C.c_void_p)]
 
 
+class VggSplitCtx(C.Structure):
+    """cips3d_vgg_split_ctx (include/cips3d_hip.h)."""
+    _fields_ = [("w_fwd", C.c_void_p * VGG_CONVS), ("w_bwd", C.c_void_p * VGG_CONVS), ("bias", C.c_void_p * VGG_CONVS),
+                ("w_amax", C.c_void_p)]
+
+
+class VggSplitIO(C.Structure):
+    """cips3d_vgg_split_io (include/cips3d_hip.h)."""
+    _fields_ = [("io", VggIO), ("range", C.c_void_p)]
+
+
 class NerfBwdGeom(C.Structure):
     _fields_ = [("cam_poses", C.c_void_p), ("focals", C.c_void_p), ("near_", C.c_void_p), ("far_", C.c_void_p),
                 ("perturb_u", C.c_void_p), ("B", C.c_int32), ("img_size", C.c_int32), ("n_samples", C.c_int32),
@@ -288,10 +299,18 @@ _SIGS = {
     "cips3d_vgg_loss_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_sizeof_vgg_ctx": (c_int, []),
     "cips3d_sizeof_vgg_io": (c_int, []),
+    "cips3d_vgg_split_supported": (c_int, [c_int, c_int, c_int]),
+    "cips3d_vgg_split_range_bytes": (c_i64, [c_int]),
+    "cips3d_vgg_split_pack": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
+    "cips3d_vgg_split_features": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_vgg_split_loss_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_vgg_split_loss_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_sizeof_vgg_split_ctx": (c_int, []),
+    "cips3d_sizeof_vgg_split_io": (c_int, []),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 35           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 36           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -300,7 +319,7 @@ def _struct_table():
     from . import plan
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
-            11: MeshResolveParams, 12: VggCtx, 13: VggIO}
+            11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO}
 
 
 def load(build_if_missing=True):

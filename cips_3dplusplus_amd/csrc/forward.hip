@@ -31,6 +31,8 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 11: return (int64_t)sizeof(cips3d_mesh_resolve_params);
     case 12: return (int64_t)sizeof(cips3d_vgg_ctx);
     case 13: return (int64_t)sizeof(cips3d_vgg_io);
+    case 14: return (int64_t)sizeof(cips3d_vgg_split_ctx);
+    case 15: return (int64_t)sizeof(cips3d_vgg_split_io);
     default: return -1;
   }
 }

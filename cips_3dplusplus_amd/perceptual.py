@@ -1,4 +1,4 @@
-"""VGG16 conv perceptual loss of flip inversion on the HIP kernels of csrc/vgg.hip.
+"""VGG16 conv perceptual loss of flip inversion on the HIP kernels of csrc/vgg.hip and csrc/vgg_split.hip.
 
 Follows `VGG16ConvLoss` of exp/cips3d/models/vgg_per_loss.py:203-334 (arguments, defaults, the `layers` property, the four
 `loss_weight` tables, `forward` = the weighted, flattened, concatenated taps) and `get_perceptual_fea` of
@@ -9,6 +9,10 @@ taps at PRE-ReLU conv outputs (`features_N` = the output of `features.N`).
     net = VGG16ConvLoss('vgg16_conv', weights='vgg16-397923af.pth')      # a torchvision state dict the user has
     t = net.taps(target)                                     # constants of the loss, computed once
     loss = net.loss(x, t)                                    # ONE autograd node: sum_k w_k^2 sum (f_k(x) - t_k)^2
+
+`precision="fp32_exact"` (the default) runs every product on the fp32 matrix instruction; `precision="split_fp16"` runs convs
+1 .. 12 and their data gradients on three fp16 products per fp32 product (csrc/vgg_split.hip: fp32-accurate, several times
+faster, not bit-equal to the exact mode).  The mode belongs to the net: every method works in both.
 
 `loss` never builds the concatenated vector (8.0 M floats per image at 256^2); `forward` does, for callers who want it.
 There is no CPU path: tensors must live on the GPU.  `vgg16_relu` and `use_stat_loss` are not implemented.
@@ -29,6 +33,7 @@ TAP_CONV = {f"features_{n}": l for l, n in enumerate(CONV_INDEX)}   # tap name -
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 MODEL_NAMES = ("vgg16_relu", "vgg16_conv", "vgg16_conv_random")
+PRECISIONS = ("fp32_exact", "split_fp16")
 
 
 def conv_shapes(H, W, n_convs=13):
@@ -74,9 +79,31 @@ def weights_from_state_dict(sd):
     return ws
 
 
+def split_pack_reference(w):
+    """The operands `cips3d_vgg_split_pack` makes of one conv's [Cout,Cin,3,3] fp32 weights, restated in numpy: (fwd, bwd, e).
+    e puts max|w| 2^-e in [2^14, 2^15); hi = fp16(w 2^-e), lo = fp16(w 2^-e - hi).  Both arrays are fp16 in the order the lanes
+    of v_mfma_f32_16x16x32_f16 read, [M/16][K/32][tap][hi | lo][q][i][j] with m = 16 mt + i and k = 32 ks + 8 q + j: the forward
+    form holds w[m][k][tap] (M = Cout, K = Cin), the data-gradient form w[k][m][8 - tap] (M = Cin, K = Cout)."""
+    import numpy as np
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    cout, cin = w.shape[:2]
+    e = int(np.frexp(np.abs(w).max())[1]) - 1 - 14
+    s = (w * np.float32(2.0 ** -e)).reshape(cout, cin, 9)
+    hi = s.astype(np.float16)
+    lo = (s - hi.astype(np.float32)).astype(np.float16)
+
+    def form(a):                     # a[m][k][tap]
+        M, K = a.shape[:2]
+        return a.reshape(M // 16, 16, K // 32, 4, 8, 9).transpose(0, 2, 5, 3, 1, 4)       # mt, ks, tap, q, i, j
+
+    fwd = np.stack([form(hi), form(lo)], axis=3)
+    bwd = np.stack([form(hi[:, :, ::-1].transpose(1, 0, 2)), form(lo[:, :, ::-1].transpose(1, 0, 2))], axis=3)
+    return np.ascontiguousarray(fwd), np.ascontiguousarray(bwd), e
+
+
 class _Run:
     """The buffers of one forward call: the io struct, the pre-ReLU tensors z_l it points at, everything it must keep alive."""
-    __slots__ = ("io", "z", "keep", "shape")
+    __slots__ = ("io", "arg", "z", "keep", "shape")      # arg: the struct the C calls take (io itself, or the split io around it)
 
 
 class _VGGLossFn(Function):
@@ -94,8 +121,11 @@ class _VGGLossFn(Function):
 
 class VGG16ConvLoss(nn.Module):
     def __init__(self, model_name="vgg16_conv", downsample_size=-1, use_stat_loss=False, layers=None, loss_w_dict=None,
-                 weights=None, generator=None, **kwargs):
+                 weights=None, generator=None, precision="fp32_exact", **kwargs):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
         if model_name not in MODEL_NAMES:
             raise ValueError(f"model_name must be one of {MODEL_NAMES}, got {model_name!r}")
         if model_name == "vgg16_relu":
@@ -161,7 +191,8 @@ class VGG16ConvLoss(nn.Module):
         key = (device.type, device.index)
         if key not in self._packed:
             lib = _lib.load()
-            ctx, keep, srcs = _lib.VggCtx(), [], (C.c_void_p * _lib.VGG_CONVS)()
+            split = self.precision == "split_fp16"
+            ctx, keep, srcs = (_lib.VggSplitCtx() if split else _lib.VggCtx()), [], (C.c_void_p * _lib.VGG_CONVS)()
             for l in range(self.n_convs):
                 w, b = (t.to(device=device, dtype=torch.float32).contiguous() for t in self.conv_weights()[l])
                 n = w.numel()
@@ -171,7 +202,14 @@ class VGG16ConvLoss(nn.Module):
                 srcs[l] = w.data_ptr()
                 ctx.w_fwd[l], ctx.w_bwd[l], ctx.bias[l] = fwd.data_ptr(), (bwd.data_ptr() if l > 0 else None), b.data_ptr()
             with torch.cuda.device(device):
-                _lib.check(lib.cips3d_vgg_pack(C.byref(ctx), srcs, self.n_convs, _lib.stream_ptr()), "cips3d_vgg_pack")
+                if split:       # hi / lo fp16 halves take the bytes of the fp32 weights; the layers' maxima go with them
+                    w_amax = torch.zeros(_lib.VGG_CONVS, device=device, dtype=torch.int32)
+                    ctx.w_amax = w_amax.data_ptr()
+                    keep += [None, w_amax, None, None]
+                    _lib.check(lib.cips3d_vgg_split_pack(C.byref(ctx), srcs, self.n_convs, _lib.stream_ptr()),
+                               "cips3d_vgg_split_pack")
+                else:
+                    _lib.check(lib.cips3d_vgg_pack(C.byref(ctx), srcs, self.n_convs, _lib.stream_ptr()), "cips3d_vgg_pack")
                 torch.cuda.current_stream().synchronize()       # the fp32 sources are dropped below
             self._packed[key] = (ctx, [t for i, t in enumerate(keep) if i % 4 != 0])
         return self._packed[key][0]
@@ -202,7 +240,14 @@ class VGG16ConvLoss(nn.Module):
         pn = [al(B * shapes[l - 1][0] * shapes[l][1] * shapes[l][2]) for l in range(self.n_convs) if POOL_BEFORE[l]]
         buf = torch.empty(sum(zn) + sum(pn), device=x.device)
         run = _Run()
-        io = _lib.VggIO()
+        if self.precision == "split_fp16":
+            run.arg = _lib.VggSplitIO()
+            io = run.arg.io                  # (a view of the struct inside run.arg)
+            rng = torch.empty(int(_lib.load().cips3d_vgg_split_range_bytes(B)) // 4, device=x.device, dtype=torch.int32)
+            run.arg.range = rng.data_ptr()
+        else:
+            run.arg = io = _lib.VggIO()
+            rng = None
         io.x, io.B, io.H, io.W, io.n_convs, io.normalize = x.data_ptr(), B, H, W, self.n_convs, normalize
         off, run.z = 0, []
         for l, (c, h, w) in enumerate(shapes):
@@ -213,15 +258,19 @@ class VGG16ConvLoss(nn.Module):
         for k, n in enumerate(pn):
             io.pooled[k] = buf.data_ptr() + 4 * off
             off += n
-        run.io, run.keep, run.shape = io, [x, buf], (B, H, W)
+        run.io, run.keep, run.shape = io, [x, buf, rng], (B, H, W)
         return run
+
+    def _call(self, name, x, run):
+        """One C call of this net's precision mode: cips3d_vgg_<name> or cips3d_vgg_split_<name>."""
+        fn = ("cips3d_vgg_split_" if self.precision == "split_fp16" else "cips3d_vgg_") + name
+        with torch.cuda.device(x.device):
+            _lib.check(getattr(_lib.load(), fn)(C.byref(self._ctx(x.device)), C.byref(run.arg), _lib.stream_ptr()), fn)
 
     def _features(self, x, normalize):
         self._check_input(x)
         run = self._new_run(x, normalize)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().cips3d_vgg_features(C.byref(self._ctx(x.device)), C.byref(run.io), _lib.stream_ptr()),
-                       "cips3d_vgg_features")
+        self._call("features", x, run)
         return run
 
     def _tap_weights(self, loss_w_dict):
@@ -243,9 +292,7 @@ class VGG16ConvLoss(nn.Module):
         loss = torch.empty((), device=x.device)
         io.partial, io.loss = partial.data_ptr(), loss.data_ptr()
         run.keep += [partial, list(targets)]
-        with torch.cuda.device(x.device):
-            _lib.check(lib.cips3d_vgg_loss_forward(C.byref(self._ctx(x.device)), C.byref(io), _lib.stream_ptr()),
-                       "cips3d_vgg_loss_forward")
+        self._call("loss_forward", x, run)
         return run, loss
 
     def _loss_backward(self, run, gloss):
@@ -257,9 +304,7 @@ class VGG16ConvLoss(nn.Module):
         io = run.io
         io.gloss, io.dx = gloss.data_ptr(), dx.data_ptr()
         io.g[0], io.g[1] = g[0].data_ptr(), g[1].data_ptr()
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().cips3d_vgg_loss_backward(C.byref(self._ctx(x.device)), C.byref(io), _lib.stream_ptr()),
-                       "cips3d_vgg_loss_backward")
+        self._call("loss_backward", x, run)
         return dx
 
     # ---- public

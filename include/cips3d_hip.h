@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 35  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 36  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1275,6 +1275,39 @@ int cips3d_vgg_loss_forward(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, 
 int cips3d_vgg_loss_backward(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
 int cips3d_sizeof_vgg_ctx(void);
 int cips3d_sizeof_vgg_io(void);
+
+/* The same loss with convs 1 .. 12 and their data gradients on split-fp16 products (csrc/vgg_split.hip): w x = w_lo x_hi +
+ * w_hi x_lo + w_hi x_hi on v_mfma_f32_16x16x32_f16 with fp32 accumulation -- fp32-accurate, not bit-equal to the exact form
+ * above.  Same network, tensors, size contract, return codes and call pattern; conv 0, the pools and the tap loss are the same
+ * kernels.
+ *
+ * cips3d_vgg_split_pack    w_fwd[l] / w_bwd[l] (l >= 1): [M/16][K/32][tap][hi | lo][lane][8 fp16] of w 2^-e_l, 36 Cout Cin bytes
+ *                       each (lane 16 q + i, element j: forward form w[16 mt + i][32 ks + 8 q + j][tap]; data-gradient form
+ *                       w[32 ks + 8 q + j][16 mt + i][8 - tap]).  e_l puts max|w_l| 2^-e_l in [2^14, 2^15); the maximum is found
+ *                       on the device and kept as its bit pattern in w_amax[l] (CIPS3D_VGG_CONVS words).  w_fwd[0]: conv 0 as it
+ *                       is (1728 floats).
+ * range                 cips3d_vgg_split_range_bytes(B) of scratch, zeroed by the calls themselves: one word per (tensor,
+ *                       sample) holding the bit pattern of max|.|, from which each sample's operand gets its own power of two.
+ *                       The backward call reads the words the forward call of the same io left.
+ * Determinism: no float atomics (the range words are raised with integer maxima); a B = 2 call equals two B = 1 calls. */
+typedef struct cips3d_vgg_split_ctx {
+  void* w_fwd[CIPS3D_VGG_CONVS];
+  void* w_bwd[CIPS3D_VGG_CONVS];
+  const float* bias[CIPS3D_VGG_CONVS];
+  uint32_t* w_amax;                          /* [CIPS3D_VGG_CONVS] */
+} cips3d_vgg_split_ctx;
+typedef struct cips3d_vgg_split_io {
+  cips3d_vgg_io io;
+  void* range;                               /* cips3d_vgg_split_range_bytes(io.B) */
+} cips3d_vgg_split_io;
+int cips3d_vgg_split_supported(int B, int H, int W);
+int64_t cips3d_vgg_split_range_bytes(int B);
+int cips3d_vgg_split_pack(const cips3d_vgg_split_ctx* ctx, const float* const* weights, int n_convs, void* stream);
+int cips3d_vgg_split_features(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
+int cips3d_vgg_split_loss_forward(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
+int cips3d_vgg_split_loss_backward(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
+int cips3d_sizeof_vgg_split_ctx(void);
+int cips3d_sizeof_vgg_split_io(void);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,14 @@
 """BASELINE config 5: CompCars 256^2 generator + pose phase of the flip-inversion loop (steps/s).
 
     python tools/bench_inversion.py [--depth 6] [--steps 200] [--res 256] [--loss surrogate|vgg16_conv_random]
+                                     [--vgg-precision fp32_exact|split_fp16]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
 (SURVEY 8d): MSE(rgb) + 50 MSE(thumb) against fixed random targets.  Random-init weights.
 --loss vgg16_conv_random: the reference's VGG16 conv perceptual loss (projector.perceptual_loss) on a randomly initialised
-VGG16 instead, against the features of the same random target images and of their bicubic thumbnails."""
+VGG16 instead, against the features of the same random target images and of their bicubic thumbnails; --vgg-precision picks
+the arithmetic of its convolutions (perceptual.VGG16ConvLoss(precision=...))."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,6 +23,7 @@ ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--n-samples", type=int, default=24)
 ap.add_argument("--app-steps", type=int, default=0)
 ap.add_argument("--loss", choices=("surrogate", "vgg16_conv_random"), default="surrogate")
+ap.add_argument("--vgg-precision", choices=("fp32_exact", "split_fp16"), default="fp32_exact")
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -34,7 +37,8 @@ if a.loss == "surrogate":
     loss_fn = surrogate_loss(t_rgb, t_thumb)
 else:
     from cips_3dplusplus_amd.perceptual import VGG16ConvLoss
-    net = VGG16ConvLoss(a.loss, generator=torch.Generator().manual_seed(2))
+    net = VGG16ConvLoss(a.loss, generator=torch.Generator().manual_seed(2), precision=a.vgg_precision)
+    assert net.precision == a.vgg_precision
     loss_fn = perceptual_loss(net, t_rgb, img_size=a.res)
 proj = FlipProjector(G, dev)
 marks = {}
@@ -51,5 +55,5 @@ dt = time.perf_counter() - marks["t0"]
 n = a.steps + a.app_steps - 1 - marks["s0"]
 print(json.dumps({"metric": "flip-inversion steps/s (fwd + bwd + Adam, batch 2)", "value": n / dt, "unit": "steps/s",
                   "ms_per_step": dt / n * 1e3, "config": {"workload": f"compcars_r{a.res}_D{a.depth}_N{a.n_samples}_B2_pose_phase",
-                  "steps": a.steps, "app_steps": a.app_steps, **({} if a.loss == "surrogate" else {"loss": a.loss})}, "dtype": "f32", "data": "synthetic",
+                  "steps": a.steps, "app_steps": a.app_steps, **({} if a.loss == "surrogate" else {"loss": a.loss, "vgg_precision": a.vgg_precision})}, "dtype": "f32", "data": "synthetic",
                   "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}))

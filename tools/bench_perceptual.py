@@ -1,10 +1,11 @@
 """The VGG16 conv perceptual loss of a flip-inversion step, alone: forward + backward at B = 2, 256^2 image + 64^2 thumbnail.
 
-    python tools/bench_perceptual.py [--res 256] [--iters 30]
+    python tools/bench_perceptual.py [--res 256] [--iters 30] [--precision fp32_exact|split_fp16|both]
 
-Prints one JSON line: the HIP node (perceptual.VGG16ConvLoss.loss, csrc/vgg.hip) and, next to it, the same loss evaluated by
-torch's F.conv2d / max_pool2d / relu with autograd on the device -- the only alternative there is.  HIP events around each
-iteration, median after warm-up; both in one process on one device, interleaved by rounds."""
+Prints one JSON line: the HIP node (perceptual.VGG16ConvLoss.loss; csrc/vgg.hip for fp32_exact, csrc/vgg_split.hip for
+split_fp16: `hip_*` is the mode asked for, with `both` the exact one, next to `split_*`) and the same loss evaluated by torch's
+F.conv2d / max_pool2d / relu with autograd on the device -- the only alternative there is.  HIP events around each iteration,
+median after warm-up; everything in one process on one device, interleaved by rounds."""
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,14 +16,19 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--iters", type=int, default=30)
 ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--precision", choices=("fp32_exact", "split_fp16", "both"), default="fp32_exact")
 a = ap.parse_args()
 dev = "cuda"
-net = VGG16ConvLoss("vgg16_conv_random", generator=torch.Generator().manual_seed(2))
+modes = ("fp32_exact", "split_fp16") if a.precision == "both" else (a.precision,)
+nets = [VGG16ConvLoss("vgg16_conv_random", generator=torch.Generator().manual_seed(2), precision=m) for m in modes]
+assert [n.precision for n in nets] == list(modes)
+net = nets[0]
 g = torch.Generator(device=dev).manual_seed(1)
 target = torch.randn(2, 3, a.res, a.res, device=dev, generator=g).clamp(-1, 1)
 rgb = torch.randn(2, 3, a.res, a.res, device=dev, generator=g).clamp(-1, 1).requires_grad_(True)
 thumb = torch.randn(2, 3, 64, 64, device=dev, generator=g).clamp(-1, 1).requires_grad_(True)
-taps_rgb, taps_thumb = net.get_perceptual_taps(target, img_size=a.res)
+taps = [n.get_perceptual_taps(target, img_size=a.res) for n in nets]       # each mode against its own targets
+taps_rgb, taps_thumb = taps[0]
 ws = [(w.to(dev), b.to(dev)) for w, b in net.conv_weights()]
 wk = [float(net.loss_w_dict[k]) for k in net.layers]
 mean = torch.tensor(IMAGENET_MEAN, device=dev).view(1, 3, 1, 1)
@@ -43,9 +49,9 @@ def torch_loss(x, targets):
     return total
 
 
-def step_hip():
+def step_hip(k=0):
     rgb.grad = thumb.grad = None
-    (net.loss(rgb, taps_rgb) + net.loss(thumb, taps_thumb)).backward()
+    (nets[k].loss(rgb, taps[k][0]) + nets[k].loss(thumb, taps[k][1])).backward()
 
 
 def step_torch():
@@ -65,18 +71,31 @@ def timed(fn, iters):
 
 step_hip(); g_hip = rgb.grad.clone(); l_hip = float(net.loss(rgb, taps_rgb))
 step_torch(); g_torch = rgb.grad.clone(); l_torch = float(torch_loss(rgb, taps_rgb))
-for fn in (step_hip, step_torch):
+steps = [lambda k=k: step_hip(k) for k in range(len(nets))]
+if len(nets) == 2:
+    step_hip(1); g_split = rgb.grad.clone(); l_split = float(nets[1].loss(rgb, taps[1][0]))
+for fn in (*steps, step_torch):
     timed(fn, 5)
-res = {"hip": [], "torch": []}
+res = {"hip": [], "split": [], "torch": []}
 for _ in range(a.rounds):
-    res["hip"] += timed(step_hip, a.iters)
+    res["hip"] += timed(steps[0], a.iters)
+    if len(nets) == 2:
+        res["split"] += timed(steps[1], a.iters)
     res["torch"] += timed(step_torch, a.iters)
 shapes = [(2, a.res), (2, 64)]
 flop = sum(2 * B * 2.0 * 9 * sum((3 if l == 0 else net.conv_weights()[l][0].shape[1]) * net.conv_weights()[l][0].shape[0]
                                  * (S >> sum(POOL_BEFORE[:l + 1])) ** 2 for l in range(13)) for B, S in shapes)
 hip_ms, torch_ms = statistics.median(res["hip"]), statistics.median(res["torch"])
+split = {}
+if len(nets) == 2:
+    split_ms = statistics.median(res["split"])
+    split = {"split_ms": split_ms, "split_min_ms": min(res["split"]), "split_tflops": flop / split_ms / 1e9,
+             "split_fraction_of_833_tflops": flop / split_ms / 1e9 / 833.0, "exact_over_split": hip_ms / split_ms,
+             "split_over_torch": split_ms / torch_ms, "split_median_below_exact_min": split_ms < min(res["hip"]),
+             "loss_split": l_split, "grad_rel_l2_split_vs_torch": float((g_split - g_torch).norm() / g_torch.norm())}
 print(json.dumps({"metric": "VGG16 conv perceptual loss, forward + backward, B=2 image + 64^2 thumbnail", "res": a.res,
+                  "precision": a.precision,
                   "hip_ms": hip_ms, "torch_conv2d_ms": torch_ms, "hip_min_ms": min(res["hip"]), "torch_min_ms": min(res["torch"]),
                   "flop_fwd_plus_data_grad": flop, "hip_tflops": flop / hip_ms / 1e9,
                   "loss_hip": l_hip, "loss_torch": l_torch,
-                  "grad_rel_l2_hip_vs_torch": float((g_hip - g_torch).norm() / g_torch.norm()), "device": torch.cuda.get_device_name(0)}))
+                  "grad_rel_l2_hip_vs_torch": float((g_hip - g_torch).norm() / g_torch.norm()), "device": torch.cuda.get_device_name(0), **split}))
