@@ -58,6 +58,11 @@ class AdamHyper(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int32)]
 
 
+class NoiseBuf(C.Structure):
+    """cips3d_noise_buf (include/cips3d_hip.h)."""
+    _fields_ = [("v", C.c_void_p), ("d", C.c_void_p), ("B", C.c_int32), ("S", C.c_int32)]
+
+
 class ActBwd(C.Structure):
     """cips3d_actbwd: operands of the activation-backward epilogue (include/cips3d_hip.h)."""
     _fields_ = [("y", C.c_void_p), ("rgb_w", C.c_void_p), ("drgb", C.c_void_p), ("d_bias", C.c_void_p),
@@ -274,6 +279,13 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_sqdiff_pair_bwd": (c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_noise_reg_supported": (c_int, [c_int, c_int]),
+    "cips3d_noise_reg_launches": (c_int, [c_int, c_int, c_int]),
+    "cips3d_noise_reg_workspace": (c_i64, [C.c_void_p, c_int]),
+    "cips3d_noise_reg": (c_int, [C.c_void_p, c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_noise_reg_bwd": (c_int, [C.c_void_p, c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_mask_blend": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
+    "cips3d_mask_blend_bwd": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
     "cips3d_sizeof_plan": (c_i64, []),
     "cips3d_sizeof_io": (c_i64, []),
     "cips3d_sizeof_struct": (c_i64, [c_int]),
@@ -310,7 +322,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 36           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 37           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

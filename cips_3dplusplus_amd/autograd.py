@@ -445,6 +445,42 @@ def weighted_mse_pair(a0, b0, w0, a1, b1, w1):
     return SqDiffPairFn.apply(a0, b0, w0 / a0.numel(), a1, b1, w1 / a1.numel())
 
 
+class NoiseRegFn(Function):
+    """weight x the noise regulariser (projector_v10.py:1183-1195) over a list of noise buffers as one node
+    (cips3d_noise_reg / _bwd, csrc/inversion_loss.hip): at most four launches forward and one backward per 32 buffers, where the
+    torch expression issues ~10 per level and buffer each way.  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, weight, *bufs):
+        bufs = [b.detach() for b in bufs]
+        loss, ws = hip.noise_reg(bufs, weight)
+        ctx.save_for_backward(ws, *bufs)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        ws, *bufs = ctx.saved_tensors
+        grads = hip.noise_reg_bwd(bufs, ctx.weight, ws, g.contiguous().float())
+        return (None, *[d if need else None for d, need in zip(grads, ctx.needs_input_grad[1:])])
+
+
+class MaskBlendFn(Function):
+    """x m + x.detach() (1 - m), m = bicubic(1 - mask) at x's resolution (projector_v10.py:1164-1167 with the mask of :268-273):
+    the value is x up to rounding, the gradient is g m.  One launch each way; the full-resolution mask is never built."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        x, mask = _c(x), _c(mask.detach())
+        ctx.save_for_backward(mask)
+        return hip.mask_blend(x, mask)
+
+    @staticmethod
+    def backward(ctx, g):
+        (mask,) = ctx.saved_tensors
+        return hip.mask_blend(_c(g), mask, backward=True), None
+
+
 class CameraFn(Function):
     """Camera.generate_camera_params for given `locations` (azim, elev), differentiable w.r.t. them."""
 

@@ -1436,6 +1436,77 @@ def sqdiff_pair_bwd(a0, b0, c0, a1, b1, c1, gloss):
     return d0, d1
 
 
+# ------------------------------------------------------------------------------- inversion loss terms (csrc/inversion_loss.hip)
+def noise_reg_supported(bufs):
+    """True when cips3d_noise_reg takes every buffer of the list: fp32 contiguous HIP tensors [B,1,S,S] whose pooled levels all
+    have even sides (cips3d_noise_reg_supported)."""
+    if len(bufs) == 0:
+        return False
+    lib = _lib.load()
+    return all(b.is_cuda and b.dtype == torch.float32 and b.dim() == 4 and b.shape[1] == 1 and b.shape[2] == b.shape[3]
+               and b.is_contiguous() and b.device == bufs[0].device
+               and lib.cips3d_noise_reg_supported(b.shape[0], b.shape[2]) == 1 for b in bufs)
+
+
+def _noise_table(bufs, grads=None):
+    tab = (_lib.NoiseBuf * len(bufs))()
+    for i, b in enumerate(bufs):
+        tab[i].v, tab[i].B, tab[i].S = dev_ptr(b, "noise buffer"), b.shape[0], b.shape[2]
+        tab[i].d = grads[i].data_ptr() if grads is not None else None
+    return tab
+
+
+def noise_reg(bufs, weight):
+    """weight x the noise regulariser of projector_v10.py:1183-1195 over the whole list `bufs` -> (loss: device scalar,
+    workspace: the pyramids and the per-level means noise_reg_bwd reads).  At most four launches per 32 buffers."""
+    lib = _lib.load()
+    tab = _noise_table(bufs)
+    nbytes = int(lib.cips3d_noise_reg_workspace(tab, len(bufs)))
+    if nbytes < 0:
+        raise RuntimeError("cips3d_noise_reg: unsupported noise buffer shape (hip.noise_reg_supported)")
+    ws = torch.empty(nbytes // 4, device=bufs[0].device)
+    loss = torch.empty((), device=bufs[0].device)
+    check(lib.cips3d_noise_reg(tab, len(bufs), float(weight), ws.data_ptr(), loss.data_ptr(), stream_ptr()), "cips3d_noise_reg")
+    return loss, ws
+
+
+def noise_reg_bwd(bufs, weight, ws, gloss):
+    """[gloss x d loss / d v for v in bufs] of noise_reg (same `bufs`, `weight` and its workspace), one launch per 32 buffers."""
+    lib = _lib.load()
+    grads = [torch.empty_like(b) for b in bufs]
+    tab = _noise_table(bufs, grads)
+    check(lib.cips3d_noise_reg_bwd(tab, len(bufs), float(weight), dev_ptr(ws, "workspace"), dev_ptr(gloss, "gloss"), stream_ptr()),
+          "cips3d_noise_reg_bwd")
+    return grads
+
+
+def mask_blend_factor(x, mask):
+    """The integer up-sampling factor of cips3d_mask_blend for image x [B,C,H,W] and mask [B,1,h,w], or 0 when the pair is not
+    one the kernel takes (fp32 contiguous HIP tensors, H / h = W / w an integer >= 1)."""
+    if not (x.is_cuda and mask.is_cuda and x.dtype == torch.float32 and mask.dtype == torch.float32 and x.dim() == 4
+            and mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[0] == x.shape[0] and x.device == mask.device):
+        return 0
+    H, W, h, w = x.shape[2], x.shape[3], mask.shape[2], mask.shape[3]
+    if h < 1 or w < 1 or H < h or H % h or W % w or H // h != W // w:
+        return 0
+    return H // h
+
+
+def mask_blend(x, mask, backward=False):
+    """x m + x (1 - m) -- or, with `backward`, x m for x = the incoming gradient -- with m the bicubic up-sampling of 1 - mask
+    evaluated inside the kernel (cips3d_mask_blend / _bwd: projector_v10.py:1164-1167, :268-273)."""
+    lib = _lib.load()
+    f = mask_blend_factor(x, mask)
+    if f == 0:
+        raise RuntimeError(f"cips3d_mask_blend: image {tuple(x.shape)} / mask {tuple(mask.shape)} is not an integer up-sampling")
+    B, Cc, H, W = x.shape
+    out = torch.empty_like(x)
+    fn = lib.cips3d_mask_blend_bwd if backward else lib.cips3d_mask_blend
+    check(fn(dev_ptr(x, "x"), dev_ptr(mask, "mask"), out.data_ptr(), B, Cc, H, W, f, stream_ptr()),
+          "cips3d_mask_blend_bwd" if backward else "cips3d_mask_blend")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- geometry export (csrc/mesh.hip)
 def align_volume(volume, near=0.88, far=1.12, out=None):
     """cips3d_align_volume: volume [B,h,w,d] fp32 -> the frustum-aligned volume of the same shape."""

@@ -11,7 +11,10 @@ The loss is a callable `loss_fn(rgb, thumb)`.  `perceptual_loss` is the referenc
 features of the image batch and of the 64^2 thumbnail against fixed target features, on the HIP kernels of csrc/vgg.hip
 (perceptual.VGG16ConvLoss; `vgg16_conv_random`, or the pretrained network when the user has its weights).  `surrogate_loss`
 (MSE on `rgb` + `thumb_weight` x MSE on `thumb_rgb` against fixed targets) stays the default of the
-benchmarks.  What is NOT here: the mask blending of :1160-1167; Streamlit charts, videos and PSNR logging.
+benchmarks.  The other terms of the step loss (:1164-1200) are knobs of `project_wplus` with the reference's names and off
+defaults: `mask_background` (`mask_blend`, :1164-1167), `mse_weight` + `target_images` (:1176-1181) and `optim_noise_bufs` +
+`regularize_noise_weight` (`noise_regulariser`, :1183-1195); on the GPU the blend and the regulariser are one autograd node
+each (csrc/inversion_loss.hip).  What is NOT here: `use_stat_loss` / `vgg16_relu`; Streamlit charts, videos and PSNR logging.
 
 The three Adam optimisers of the reference run as `optim.HipAdam` (csrc/optim.hip: torch.optim.Adam's update rule, one
 bandwidth-bound launch per 48 tensors; CIPS3D_HIP_ADAM=0: torch.optim.Adam, fused where torch offers it).
@@ -66,8 +69,11 @@ def _set_lr(opt, lr):
         g["lr"] = lr
 
 
-def noise_regulariser(noise_bufs):
-    """projector_v10.py:1179-1192 (StyleGAN2's multi-scale autocorrelation penalty)."""
+FUSED_NOISE_REG = os.environ.get("CIPS3D_FUSED_NOISE_REG", "1") != "0"      # 0: the torch expression (A/B knob)
+FUSED_MASK_BLEND = os.environ.get("CIPS3D_FUSED_MASK_BLEND", "1") != "0"    # 0: the torch expression (A/B knob)
+
+
+def _noise_regulariser_torch(noise_bufs):
     reg = 0
     for v in noise_bufs:
         noise = v
@@ -78,6 +84,41 @@ def noise_regulariser(noise_bufs):
                 break
             noise = torch.nn.functional.avg_pool2d(noise, kernel_size=2)
     return reg
+
+
+def noise_regulariser(noise_bufs, weight=1.0):
+    """weight x projector_v10.py:1183-1195 (StyleGAN2's multi-scale autocorrelation penalty).  fp32 HIP buffers [B,1,S,S] whose
+    pooled levels have even sides go through ONE autograd node for the whole list (autograd.NoiseRegFn, csrc/inversion_loss.hip:
+    at most four launches forward, one backward, the weight folded in); anything else -- CPU tensors, other dtypes, odd sides,
+    nothing that requires a gradient, CIPS3D_FUSED_NOISE_REG=0 -- is the torch expression."""
+    noise_bufs = list(noise_bufs)
+    if FUSED_NOISE_REG and len(noise_bufs) > 0 and any(b.requires_grad for b in noise_bufs):
+        from . import hip
+        if hip.noise_reg_supported(noise_bufs):
+            from . import autograd as AG
+            return AG.NoiseRegFn.apply(float(weight), *noise_bufs)
+    reg = _noise_regulariser_torch(noise_bufs)
+    return reg if weight == 1.0 else weight * reg
+
+
+def _mask_blend_torch(rgb, mask):
+    m = (1 - mask.detach()).expand(-1, rgb.shape[1], -1, -1)
+    m = torch.nn.functional.interpolate(m, scale_factor=rgb.shape[-1] / m.shape[-1], recompute_scale_factor=False, mode="bicubic")
+    return rgb * m + rgb.detach() * (1 - m)
+
+
+def mask_blend(rgb, mask):
+    """projector_v10.py:1164-1167 with the mask of `_G_forward` (:268-273): `rgb * m + rgb.detach() * (1 - m)` with m the bicubic
+    up-sampling of 1 - mask (the render's foreground mask [B,1,h,w], detached) to rgb's resolution -- the image itself up to
+    rounding, with the gradient g * m.  fp32 HIP tensors with an integer factor are one autograd node (autograd.MaskBlendFn: one
+    launch each way, m evaluated per pixel and never written out); CPU tensors, other factors and CIPS3D_FUSED_MASK_BLEND=0 are
+    the torch expression."""
+    if FUSED_MASK_BLEND and rgb.is_cuda:
+        from . import hip
+        if hip.mask_blend_factor(rgb, mask) >= 1:
+            from . import autograd as AG
+            return AG.MaskBlendFn.apply(rgb, mask)
+    return _mask_blend_torch(rgb, mask)
 
 
 FUSED_LOSS = os.environ.get("CIPS3D_FUSED_LOSS", "1") != "0"      # 0: the torch expression (A/B knob)
@@ -95,6 +136,14 @@ def surrogate_loss(target_rgb, target_thumb, rgb_weight=1.0, thumb_weight=50.0):
                                         thumb, target_thumb.to(thumb.device, torch.float32), thumb_weight)
         return rgb_weight * ((rgb - target_rgb) ** 2).mean() + thumb_weight * ((thumb - target_thumb) ** 2).mean()
     return loss
+
+
+def _weighted_mse(rgb, target, weight):
+    """weight x F.mse_loss(rgb, target) (projector_v10.py:1176-1179); on the GPU the squared-difference node with one tensor."""
+    if FUSED_LOSS and rgb.is_cuda and rgb.dtype == torch.float32 and target.dtype == torch.float32 and rgb.shape == target.shape:
+        from . import autograd as AG
+        return AG.SqDiffPairFn.apply(rgb, target, weight / rgb.numel(), None, None, 0.0)
+    return weight * torch.nn.functional.mse_loss(rgb, target)
 
 
 def perceptual_loss(net, target_images, rgb_weight=1.0, thumb_weight=1.0, img_size=1024):
@@ -174,8 +223,16 @@ class FlipProjector:
                       optim_render_params=False, optim_decoder_w=True, optim_decoder_params=True, optim_noise_bufs=False, zero_noise_bufs=True,
                       bs_cam=2, bs_render=1, bs_decoder=2, lr_cam=0.02, lr_render_w=0.001, lr_decoder_w=0.01,
                       lr_decoder_params=0.005, lr_noise=0.001, truncation_psi=1.0, flip_w_decoder_every=10,
-                      azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None):
-        """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise)."""
+                      azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
+                      mask_background=False, mse_weight=0.0, target_images=None):
+        """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
+        `mask_background`: from the appearance phase on, the image's gradient only flows where the render's foreground mask says
+        so (mask_blend; the thumbnail is not blended, as in the reference).  `mse_weight` > 0 adds mse_weight x
+        F.mse_loss(image, target_images) (projector_v10.py:1176-1181)."""
+        if mse_weight > 0 and target_images is None:
+            raise ValueError("project_wplus: mse_weight > 0 needs target_images")
+        if mse_weight > 0:
+            target_images = target_images.detach().to(self.device, torch.float32).contiguous()
         G = copy.deepcopy(self.G).eval().requires_grad_(False).to(self.device)
         if optim_render_params:                              # projector_v10.py:967-968
             G.renderer.requires_grad_(True)
@@ -210,12 +267,16 @@ class FlipProjector:
                 if (step + flip_w_decoder_every - 1) % flip_w_decoder_every == 0 and step != N_steps - 1:
                     flip_w_decoder = True
             # (one NeRF latent for both views, bs_render = 1: the generator broadcasts it inside the FiLM table's launch)
-            rgb, thumb, _ = self.g_forward(
+            rgb, thumb, mask = self.g_forward(
                 G, w_render, w_decoder if w_decoder.shape[0] == 2 else w_decoder.repeat(2, 1, 1), noise_bufs, cam_cfg, nerf_cfg,
                 rot=loc, flip_w_decoder=flip_w_decoder)
-            loss = loss_fn(rgb, thumb)
+            if mask_background and step >= N_steps_pose:
+                rgb = mask_blend(rgb, mask)
+            loss = loss_fn(rgb, thumb)                   # (term order of projector_v10.py:1200: perceptual + mse + regulariser)
+            if mse_weight > 0:
+                loss = loss + _weighted_mse(rgb, target_images, mse_weight)
             if optim_noise_bufs and regularize_noise_weight > 0:
-                loss = loss + regularize_noise_weight * noise_regulariser(noise_bufs)
+                loss = loss + noise_regulariser(noise_bufs, regularize_noise_weight)
             for o in opts:
                 o.zero_grad(set_to_none=True)
             loss.backward(one if loss.dim() == 0 and loss.dtype == one.dtype else None)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 36  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 37  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -909,6 +909,38 @@ int cips3d_sqdiff_pair(const float* a0, const float* b0, int64_t n0, float c0, c
                        float c1, float* partial, float* loss, void* stream);
 int cips3d_sqdiff_pair_bwd(const float* a0, const float* b0, int64_t n0, float c0, float* d0, const float* a1, const float* b1,
                            int64_t n1, float c1, float* d1, const float* gloss, void* stream);
+
+/* The noise regulariser of the inversion loss (models/projector_v10.py:1183-1195, StyleGAN2's multi-scale autocorrelation
+ * penalty) over a LIST of noise buffers at once (csrc/inversion_loss.hip).  For every buffer v [B,1,S,S] (fp32, contiguous) and
+ * every level n_0 = v, n_{l+1} = avg_pool2d(n_l, 2), down to and including the first level with side <= 8:
+ *   loss[0] = weight * sum ( mean(n_l * roll(n_l, 1, dim 3))^2 + mean(n_l * roll(n_l, 1, dim 2))^2 )      (circular rolls).
+ * `bufs` is a HOST array (copied into the kernel arguments, 32 buffers per launch).  Forward: per 32 buffers at most four
+ * launches (pyramid from level 0; pyramid from level 6 when a side exceeds 512; per-workgroup partial sums of every level;
+ * their fixed-order totals -> the 2 x levels means and the loss), backward: one, whatever the number of buffers and levels
+ * (cips3d_noise_reg_launches states the count for K buffers of largest side max_S).  No float atomics: value and gradient
+ * are bit-reproducible.  workspace: cips3d_noise_reg_workspace(bufs, K) bytes (pyramids, partials, means); _bwd reads the
+ * workspace the forward of the same `bufs` filled and OVERWRITES bufs[i].d with gloss[0] * d loss / d v_i (gloss: the loss'
+ * incoming gradient, a device scalar); the forward ignores `d`.  Supported (cips3d_noise_reg_supported): B >= 1 and every
+ * level that is pooled has an even side (S <= 8: any S), S <= 32768.  Unsupported buffers: CIPS3D_E_BADARG, nothing launched. */
+typedef struct cips3d_noise_buf {
+  const float* v;
+  float* d;
+  int32_t B, S;
+} cips3d_noise_buf;
+int cips3d_noise_reg_supported(int B, int S);
+int cips3d_noise_reg_launches(int K, int max_S, int backward);
+int64_t cips3d_noise_reg_workspace(const cips3d_noise_buf* bufs, int K);
+int cips3d_noise_reg(const cips3d_noise_buf* bufs, int K, float weight, void* workspace, float* loss, void* stream);
+int cips3d_noise_reg_bwd(const cips3d_noise_buf* bufs, int K, float weight, const void* workspace, const float* gloss,
+                         void* stream);
+
+/* The mask blending of the inversion loss (models/projector_v10.py:1164-1167 with the mask of :268-273):
+ *   out = x * m + x * (1 - m)   (the reference's `synth * mask + synth.detach() * (1 - mask)`: the image up to rounding),
+ *   m = F.interpolate(1 - mask, scale_factor = f, mode = 'bicubic') (align_corners = False, A = -0.75, taps clamped to the
+ *   border, result not clamped), evaluated per pixel from mask [B,1,H/f,W/f]: the full-resolution mask is never written.
+ * _bwd: dx = g * m.  x / out / g / dx: [B,C,H,W] fp32 contiguous; f >= 1 divides H and W.  One launch each. */
+int cips3d_mask_blend(const float* x, const float* mask, float* out, int B, int C, int H, int W, int f, void* stream);
+int cips3d_mask_blend_bwd(const float* g, const float* mask, float* dx, int B, int C, int H, int W, int f, void* stream);
 
 /* The decoder as ONE differentiable node (csrc/decoder_grad.hip): Decoder.forward with every StyledConv output kept, and the
  * whole backward -- gradients of the features, the W+ styles and every decoder parameter -- in one call each.

@@ -2,13 +2,18 @@
 
     python tools/bench_inversion.py [--depth 6] [--steps 200] [--res 256] [--loss surrogate|vgg16_conv_random]
                                      [--vgg-precision fp32_exact|split_fp16]
+                                     [--optim-noise-bufs] [--mask-background] [--mse-weight W]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
 (SURVEY 8d): MSE(rgb) + 50 MSE(thumb) against fixed random targets.  Random-init weights.
 --loss vgg16_conv_random: the reference's VGG16 conv perceptual loss (projector.perceptual_loss) on a randomly initialised
 VGG16 instead, against the features of the same random target images and of their bicubic thumbnails; --vgg-precision picks
-the arithmetic of its convolutions (perceptual.VGG16ConvLoss(precision=...))."""
+the arithmetic of its convolutions (perceptual.VGG16ConvLoss(precision=...)).
+--optim-noise-bufs: the noise buffers are optimised (random start) and the noise regulariser is part of the loss;
+--mask-background: the image is mask-blended before the loss in every step (N_steps_pose = 0: the steps are appearance steps);
+--mse-weight W: W x MSE against the target images is added.  CIPS3D_FUSED_NOISE_REG=0 / CIPS3D_FUSED_MASK_BLEND=0 run the torch
+expressions of the first two instead of the HIP nodes (A/B).  With none of the three the run is what it was without them."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,6 +29,9 @@ ap.add_argument("--n-samples", type=int, default=24)
 ap.add_argument("--app-steps", type=int, default=0)
 ap.add_argument("--loss", choices=("surrogate", "vgg16_conv_random"), default="surrogate")
 ap.add_argument("--vgg-precision", choices=("fp32_exact", "split_fp16"), default="fp32_exact")
+ap.add_argument("--optim-noise-bufs", action="store_true")
+ap.add_argument("--mask-background", action="store_true")
+ap.add_argument("--mse-weight", type=float, default=0.0)
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -48,12 +56,27 @@ def on_step(step, loss, azim, elev):
         torch.cuda.synchronize(); marks["t0"] = time.perf_counter(); marks["s0"] = step
     marks["last"] = float(loss.detach()) if step % 50 == 0 else marks.get("last")
 
-out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=a.steps, N_steps_app=a.app_steps,
-                         w_avg_samples=2000, on_step=on_step, azim_init=(-1.0, 3.0))
+extra, knobs = {}, {}
+if a.optim_noise_bufs:
+    extra.update(optim_noise_bufs=True, zero_noise_bufs=False)
+    knobs["optim_noise_bufs"] = True
+if a.mse_weight > 0:
+    extra.update(mse_weight=a.mse_weight, target_images=t_rgb)
+    knobs["mse_weight"] = a.mse_weight
+n_pose, n_app = a.steps, a.app_steps
+if a.mask_background:                   # the blend runs from the appearance phase on: time appearance steps
+    extra.update(mask_background=True)
+    knobs["mask_background"] = True
+    n_pose, n_app = 0, a.steps + a.app_steps
+if knobs:
+    from cips_3dplusplus_amd import projector as _P
+    knobs["fused_noise_reg"], knobs["fused_mask_blend"] = _P.FUSED_NOISE_REG, _P.FUSED_MASK_BLEND
+out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=n_pose, N_steps_app=n_app,
+                         w_avg_samples=2000, on_step=on_step, azim_init=(-1.0, 3.0), **extra)
 torch.cuda.synchronize()
 dt = time.perf_counter() - marks["t0"]
 n = a.steps + a.app_steps - 1 - marks["s0"]
 print(json.dumps({"metric": "flip-inversion steps/s (fwd + bwd + Adam, batch 2)", "value": n / dt, "unit": "steps/s",
                   "ms_per_step": dt / n * 1e3, "config": {"workload": f"compcars_r{a.res}_D{a.depth}_N{a.n_samples}_B2_pose_phase",
-                  "steps": a.steps, "app_steps": a.app_steps, **({} if a.loss == "surrogate" else {"loss": a.loss, "vgg_precision": a.vgg_precision})}, "dtype": "f32", "data": "synthetic",
+                  "steps": a.steps, "app_steps": a.app_steps, **knobs, **({} if a.loss == "surrogate" else {"loss": a.loss, "vgg_precision": a.vgg_precision})}, "dtype": "f32", "data": "synthetic",
                   "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}))
