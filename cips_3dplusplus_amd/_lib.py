@@ -319,10 +319,14 @@ _SIGS = {
     "cips3d_vgg_split_loss_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_sizeof_vgg_split_ctx": (c_int, []),
     "cips3d_sizeof_vgg_split_io": (c_int, []),
+    "cips3d_image_metrics": (c_int, [C.c_void_p, c_int, C.c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_void_p, C.c_void_p,
+                                     c_i64, C.c_void_p]),
+    "cips3d_image_metrics_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "cips3d_image_metrics_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 37           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 38           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

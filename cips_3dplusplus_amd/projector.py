@@ -14,7 +14,9 @@ features of the image batch and of the 64^2 thumbnail against fixed target featu
 benchmarks.  The other terms of the step loss (:1164-1200) are knobs of `project_wplus` with the reference's names and off
 defaults: `mask_background` (`mask_blend`, :1164-1167), `mse_weight` + `target_images` (:1176-1181) and `optim_noise_bufs` +
 `regularize_noise_weight` (`noise_regulariser`, :1183-1195); on the GPU the blend and the regulariser are one autograd node
-each (csrc/inversion_loss.hip).  What is NOT here: `use_stat_loss` / `vgg16_relu`; Streamlit charts, videos and PSNR logging.
+each (csrc/inversion_loss.hip).  `metrics_every` > 0 logs the PSNR and SSIM the reference charts (:1125-1139) and returns those of
+the final re-render (:1229-1242, 1266-1279), computed on the device (metrics.MetricsLog, csrc/metrics.hip) and read once after the
+loop.  What is NOT here: `use_stat_loss` / `vgg16_relu`; LPIPS; Streamlit charts and videos.
 
 The three Adam optimisers of the reference run as `optim.HipAdam` (csrc/optim.hip: torch.optim.Adam's update rule, one
 bandwidth-bound launch per 48 tensors; CIPS3D_HIP_ADAM=0: torch.optim.Adam, fused where torch offers it).
@@ -224,13 +226,28 @@ class FlipProjector:
                       bs_cam=2, bs_render=1, bs_decoder=2, lr_cam=0.02, lr_render_w=0.001, lr_decoder_w=0.01,
                       lr_decoder_params=0.005, lr_noise=0.001, truncation_psi=1.0, flip_w_decoder_every=10,
                       azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
-                      mask_background=False, mse_weight=0.0, target_images=None):
+                      mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0):
         """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
         `mask_background`: from the appearance phase on, the image's gradient only flows where the render's foreground mask says
         so (mask_blend; the thumbnail is not blended, as in the reference).  `mse_weight` > 0 adds mse_weight x
-        F.mse_loss(image, target_images) (projector_v10.py:1176-1181)."""
+        F.mse_loss(image, target_images) (projector_v10.py:1176-1181).
+        `metrics_every` > 0 (needs `target_images`): PSNR and SSIM (metrics.py: scikit-image's defaults on 8-bit images) of view 0
+        of the generator's image, before the mask blending, against target_images[0], at the steps with step % metrics_every == 0
+        and at the last one (the reference's logging condition, :1125-1139) -- two launches per logged step, no copy and no
+        synchronisation inside the loop.  After the loop the image is rendered once more under no_grad at the optimised pose and
+        styles (:1229-1242); the dict gains "psnr" and "ssim" of that image (floats, :1266-1279) and "metrics_history"
+        ({"steps", "psnr", "ssim"} of the logged steps), all from one read.  0: nothing new runs and the dict has no new keys."""
         if mse_weight > 0 and target_images is None:
             raise ValueError("project_wplus: mse_weight > 0 needs target_images")
+        metrics_log = None
+        if metrics_every < 0 or int(metrics_every) != metrics_every:
+            raise ValueError(f"project_wplus: metrics_every must be a non-negative integer, got {metrics_every}")
+        if metrics_every > 0:
+            if target_images is None:
+                raise ValueError("project_wplus: metrics_every > 0 needs target_images")
+            from .metrics import MetricsLog
+            n_logged = len([s for s in range(N_steps_pose + N_steps_app) if s % metrics_every == 0 or s == N_steps_pose + N_steps_app - 1])
+            metrics_log = MetricsLog(target_images[0:1].detach().to(self.device), n_logged + 1)      # (+ 1: the final re-render)
         if mse_weight > 0:
             target_images = target_images.detach().to(self.device, torch.float32).contiguous()
         G = copy.deepcopy(self.G).eval().requires_grad_(False).to(self.device)
@@ -270,6 +287,8 @@ class FlipProjector:
             rgb, thumb, mask = self.g_forward(
                 G, w_render, w_decoder if w_decoder.shape[0] == 2 else w_decoder.repeat(2, 1, 1), noise_bufs, cam_cfg, nerf_cfg,
                 rot=loc, flip_w_decoder=flip_w_decoder)
+            if metrics_log is not None and (step % metrics_every == 0 or step == N_steps - 1):
+                metrics_log.update(step, rgb[0:1])
             if mask_background and step >= N_steps_pose:
                 rgb = mask_blend(rgb, mask)
             loss = loss_fn(rgb, thumb)                   # (term order of projector_v10.py:1200: perceptual + mse + regulariser)
@@ -290,7 +309,17 @@ class FlipProjector:
                 on_step(step, loss, azim, elev)
             else:
                 history.append(loss.detach())
-        return {"azim": azim.clone(), "elev": elev.clone(), "w_render_opt": w_render.detach(),
-                "w_decoder_opt": w_decoder.detach(), "render_state_dict": G.renderer.state_dict(),
-                "decoder_state_dict": G.decoder.state_dict(), "noise_bufs": [b.detach() for b in noise_bufs], "padding": 0,
-                "loss_history": torch.stack(history).cpu() if history else None, "G": G}
+        out = {"azim": azim.clone(), "elev": elev.clone(), "w_render_opt": w_render.detach(),
+               "w_decoder_opt": w_decoder.detach(), "render_state_dict": G.renderer.state_dict(),
+               "decoder_state_dict": G.decoder.state_dict(), "noise_bufs": [b.detach() for b in noise_bufs], "padding": 0,
+               "loss_history": torch.stack(history).cpu() if history else None, "G": G}
+        if metrics_log is not None:
+            with torch.no_grad():                        # projector_v10.py:1229-1242: the clean re-render at the optimised state
+                proj_rgb, _, _ = self.g_forward(
+                    G, w_render, w_decoder if w_decoder.shape[0] == 2 else w_decoder.repeat(2, 1, 1), noise_bufs, cam_cfg, nerf_cfg,
+                    rot=loc)
+                metrics_log.update(N_steps, proj_rgb[0:1])
+            res = metrics_log.result()                   # the single device-to-host read
+            out["psnr"], out["ssim"] = float(res["psnr"][-1]), float(res["ssim"][-1])
+            out["metrics_history"] = {"steps": res["steps"][:-1], "psnr": res["psnr"][:-1], "ssim": res["ssim"][:-1]}
+        return out

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 37  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 38  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1340,6 +1340,26 @@ int cips3d_vgg_split_loss_forward(const cips3d_vgg_split_ctx* ctx, const cips3d_
 int cips3d_vgg_split_loss_backward(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
 int cips3d_sizeof_vgg_split_ctx(void);
 int cips3d_sizeof_vgg_split_io(void);
+
+/* PSNR and SSIM of image pairs on the device (csrc/metrics.hip): scikit-image's peak_signal_noise_ratio and
+ * structural_similarity at their defaults on 8-bit images (data range 255; win_size 7, uniform window, K1 = 0.01, K2 = 0.03,
+ * sample covariance), which is what the reference's project_wplus logs (models/projector_v10.py:1125-1139, 1266-1279).
+ *
+ * a, b [B,C,H,W], each either uint8 (x_is_u8 != 0) or fp32 in [-1, 1] (quantised on load with cips3d_rgb_to_uint8's arithmetic:
+ * clamp, (c + 1) * 127.5, round to nearest even; no uint8 copy is written).  For image i the call writes two 64-bit words into
+ * row `row + i` of `record` (rows of 16 bytes):
+ *     int64   SSE   the sum of squared differences over all channels and pixels (PSNR = 10 log10(255^2 C H W / SSE))
+ *     float64 SSIM  the mean over the C (H - 6) (W - 6) windows that lie inside the image
+ * Two launches on `stream`, no synchronisation, no atomics: the sums run in a fixed order (integers for the squared error and
+ * the window moments, fp32 inside a tile, fp64 across tiles), so a result is bit-identical run to run and does not depend on
+ * the batch the image sits in.  `workspace`: cips3d_image_metrics_workspace_bytes(B, C, H, W) bytes, 16-byte aligned, free
+ * again once the stream has passed the call.  cips3d_image_metrics_tile: the sides of a workgroup's tile of window origins
+ * (returns the threads per workgroup; a thread adds tile_h * tile_w / threads windows in sequence).
+ * CIPS3D_E_BADARG: a null pointer, B or C < 1, H or W < 7, row < 0; CIPS3D_E_UNSUPP: a misaligned pointer. */
+int cips3d_image_metrics(const void* a, int a_is_u8, const void* b, int b_is_u8, int B, int C, int H, int W, void* workspace,
+                         void* record, int64_t row, void* stream);
+int64_t cips3d_image_metrics_workspace_bytes(int B, int C, int H, int W);
+int cips3d_image_metrics_tile(int* tile_h, int* tile_w);
 
 #ifdef __cplusplus
 }

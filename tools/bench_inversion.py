@@ -2,7 +2,7 @@
 
     python tools/bench_inversion.py [--depth 6] [--steps 200] [--res 256] [--loss surrogate|vgg16_conv_random]
                                      [--vgg-precision fp32_exact|split_fp16]
-                                     [--optim-noise-bufs] [--mask-background] [--mse-weight W]
+                                     [--optim-noise-bufs] [--mask-background] [--mse-weight W] [--metrics-every K]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
@@ -13,7 +13,9 @@ the arithmetic of its convolutions (perceptual.VGG16ConvLoss(precision=...)).
 --optim-noise-bufs: the noise buffers are optimised (random start) and the noise regulariser is part of the loss;
 --mask-background: the image is mask-blended before the loss in every step (N_steps_pose = 0: the steps are appearance steps);
 --mse-weight W: W x MSE against the target images is added.  CIPS3D_FUSED_NOISE_REG=0 / CIPS3D_FUSED_MASK_BLEND=0 run the torch
-expressions of the first two instead of the HIP nodes (A/B).  With none of the three the run is what it was without them."""
+expressions of the first two instead of the HIP nodes (A/B).  With none of the three the run is what it was without them.
+--metrics-every K: PSNR / SSIM of the image against the target are logged on the device every K steps (project_wplus's
+`metrics_every`, metrics.MetricsLog); the JSON line gains the final re-render's "psnr" / "ssim" and the number of logged steps."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,6 +34,7 @@ ap.add_argument("--vgg-precision", choices=("fp32_exact", "split_fp16"), default
 ap.add_argument("--optim-noise-bufs", action="store_true")
 ap.add_argument("--mask-background", action="store_true")
 ap.add_argument("--mse-weight", type=float, default=0.0)
+ap.add_argument("--metrics-every", type=int, default=0)
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -63,12 +66,15 @@ if a.optim_noise_bufs:
 if a.mse_weight > 0:
     extra.update(mse_weight=a.mse_weight, target_images=t_rgb)
     knobs["mse_weight"] = a.mse_weight
+if a.metrics_every > 0:
+    extra.update(metrics_every=a.metrics_every, target_images=t_rgb)
+    knobs["metrics_every"] = a.metrics_every
 n_pose, n_app = a.steps, a.app_steps
 if a.mask_background:                   # the blend runs from the appearance phase on: time appearance steps
     extra.update(mask_background=True)
     knobs["mask_background"] = True
     n_pose, n_app = 0, a.steps + a.app_steps
-if knobs:
+if set(knobs) - {"metrics_every"}:
     from cips_3dplusplus_amd import projector as _P
     knobs["fused_noise_reg"], knobs["fused_mask_blend"] = _P.FUSED_NOISE_REG, _P.FUSED_MASK_BLEND
 out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=n_pose, N_steps_app=n_app,
@@ -79,4 +85,5 @@ n = a.steps + a.app_steps - 1 - marks["s0"]
 print(json.dumps({"metric": "flip-inversion steps/s (fwd + bwd + Adam, batch 2)", "value": n / dt, "unit": "steps/s",
                   "ms_per_step": dt / n * 1e3, "config": {"workload": f"compcars_r{a.res}_D{a.depth}_N{a.n_samples}_B2_pose_phase",
                   "steps": a.steps, "app_steps": a.app_steps, **knobs, **({} if a.loss == "surrogate" else {"loss": a.loss, "vgg_precision": a.vgg_precision})}, "dtype": "f32", "data": "synthetic",
+                  **({"psnr": out["psnr"], "ssim": out["ssim"], "metrics_logged": len(out["metrics_history"]["steps"])} if a.metrics_every > 0 else {}),
                   "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}))
