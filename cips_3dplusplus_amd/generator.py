@@ -78,6 +78,18 @@ class Generator(nn.Module):
         mean_d = self._run_style_decoder(zd).mean(0, keepdim=True)
         return mean_r, mean_d
 
+    def _make_mean_latents(self, device):
+        """The truncation means, made on first use on whichever stream calls first: fenced like the renderer's weight streams
+        (renderer.py), so that a forward on another stream -- pipeline.py's other lane -- does not read them half written."""
+        from . import hip
+        self.style_render_mean, self.style_decoder_mean = self.get_mean_latent(10000, device)
+        self.__dict__["_mean_fence"] = (self.style_render_mean, hip.BuildFence(self.style_render_mean, self.style_decoder_mean))
+
+    def _mean_latents_ready(self):
+        ent = self.__dict__.get("_mean_fence")
+        if ent is not None and ent[0] is self.style_render_mean:      # (preset means -- attributes set by the caller -- carry none)
+            ent[1].wait()
+
     def mapping_renderer(self, zs, truncation, style_render_mean=None, **kwargs):
         """model_v3.py:1402-1418."""
         m = style_render_mean.reshape(-1).contiguous() if truncation < 1 else None
@@ -105,7 +117,8 @@ class Generator(nn.Module):
             raise NotImplementedError
         if truncation < 1:
             if recompute_mean or not hasattr(self, "style_render_mean") or not hasattr(self, "style_decoder_mean"):
-                self.style_render_mean, self.style_decoder_mean = self.get_mean_latent(10000, zs[0].device)
+                self._make_mean_latents(zs[0].device)
+            self._mean_latents_ready()
             mean_r, mean_d = self.style_render_mean, self.style_decoder_mean
         else:
             mean_r = mean_d = None
@@ -319,8 +332,12 @@ class Generator(nn.Module):
             if key[0] == "obj":
                 verts, faces = _mesh.read_obj(path, device=dev)
             # (the pair stays alive with the entry: its addresses are the key)
-            ent = (key, _mesh.NoiseProjector(verts.to(dev), faces.to(dev), sizes), (verts, faces))
+            proj = _mesh.NoiseProjector(verts.to(dev), faces.to(dev), sizes)
+            from . import hip
+            fence = hip.BuildFence(*[t for m in proj.meshes.values() for t in m], *proj.vert_noise)
+            ent = (key, proj, (verts, faces), fence)
             self.__dict__["_noise_projector"] = ent
+        ent[3].wait()             # (its subdivided meshes and vertex noise are read from every stream that projects)
         return ent[1]
 
     def _project_noise(self, noise_bufs, cam_poses, mesh, noise_bound):
@@ -518,9 +535,15 @@ class Generator(nn.Module):
         if (style_render is None) != (style_decoder is None):
             raise NotImplementedError
         if plan is not None and inject_index is None:
-            if style_render is None and truncation < 1 and (
-                    recompute_mean or not hasattr(self, "style_render_mean") or not hasattr(self, "style_decoder_mean")):
-                self.style_render_mean, self.style_decoder_mean = self.get_mean_latent(10000, dev)
+            if style_render is None and truncation < 1:
+                if recompute_mean or not hasattr(self, "style_render_mean") or not hasattr(self, "style_decoder_mean"):
+                    self._make_mean_latents(dev)
+                self._mean_latents_ready()
+            if plan.lane == 0:
+                # lane 0's tables are the ones every per-op forward writes, whatever stream it ran on (below)
+                tail = self.__dict__.get("_per_op_tail")
+                if tail is not None:
+                    tail.wait()
             ret = self._planned_forward(plan, zs, cam_poses, per_view(focals), per_view(near), per_view(far), perturb_u,
                                         noise_bufs, truncation, style_render, style_decoder, return_sdf,
                                         return_xyz or shade is not None, fresh_perturb=fresh_perturb,
@@ -538,6 +561,11 @@ class Generator(nn.Module):
             perturb_u = torch.rand(B, img_size, img_size, 1, device=dev)
 
         # ---- per-op path (k=3 / untiled shapes / style mixing): same kernels, launched one by one
+        # It runs on the modules' LANE-0 tables (FiLM table, decoder modulations and their staging buffers) whatever stream it
+        # is issued on, so per-op forwards are ordered one behind the other: each waits for the end of the previous one when that
+        # ran on another stream, and -- issued on a stream other than lane 0's -- for the planned forwards lane 0 has in flight.
+        # Such calls gain nothing from pipeline.py's lanes; they are safe on them.
+        tail = self._per_op_enter()
         style_render, style_decoder = self.mapping_networks(
             zs=zs, truncation=truncation, inject_index=inject_index, style_render=style_render,
             style_decoder=style_decoder, recompute_mean=recompute_mean)
@@ -559,4 +587,23 @@ class Generator(nn.Module):
         if eikonal_reg or return_normal:
             self._geometry_terms(ret, eikonal_reg, return_normal, shade, xyz, cam_poses, per_view(focals), per_view(near),
                                  per_view(far), style_render, img_size, N, perturb_u, static)
+        tail.record()
         return ret
+
+    def _per_op_enter(self):
+        """Order the current stream behind everything that may still use the lane-0 tables; returns the tail to record at exit."""
+        from . import hip
+        tail = self.__dict__.get("_per_op_tail")
+        if tail is None:
+            tail = self.__dict__["_per_op_tail"] = hip.StreamTail()
+        self.__dict__["_per_op_calls"] = self.__dict__.get("_per_op_calls", 0) + 1
+        if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
+            return tail
+        tail.wait()
+        sid = hip.stream_ptr()
+        sid0 = next((s for s, lane in self.__dict__.get("_stream_lanes", {}).items() if lane == 0), sid)
+        if sid0 != sid and any(v is not None for v in self.__dict__.get("_plans", {}).values()):
+            # (lane 0 has planned forwards: they use the same tables)
+            s0 = torch.cuda.default_stream() if sid0 == 0 else torch.cuda.ExternalStream(sid0)
+            torch.cuda.current_stream().wait_stream(s0)
+        return tail

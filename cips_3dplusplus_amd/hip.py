@@ -127,6 +127,68 @@ import collections
 STYLE_EPOCHS = collections.defaultdict(int)
 
 
+class BuildFence:
+    """Marks the point of the building stream at which device buffers that are built once and then read from several streams
+    (the renderer's packed weight streams, the mean latents, a noise projector's meshes) are complete.  Made right after the
+    build, on the stream that ran it; `wait()` on a reader's side orders the current stream behind that point the FIRST time
+    the stream is seen, and is a set lookup afterwards.  `tensors` are marked as in use by every reading stream (allocator safety:
+    a cache that drops them must not hand their memory out while another stream's kernels still read it).  No device: no-op."""
+    __slots__ = ("event", "seen", "tensors")
+
+    def __init__(self, *tensors):
+        self.tensors = [t for t in tensors if torch.is_tensor(t) and t.is_cuda]
+        self.event, self.seen = None, set()
+        if torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing():
+            self.event = torch.cuda.Event()
+            self.event.record()
+            self.seen.add(stream_ptr())
+
+    def __reduce__(self):
+        # (a copied or unpickled owner: events are not copied.  Its parameters live at new addresses, so the owner's cache key
+        # no longer matches and the buffers are rebuilt with a fence of their own)
+        return (BuildFence, ())
+
+    def wait(self):
+        if self.event is None:
+            return
+        sid = stream_ptr()
+        if sid in self.seen:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            return              # (a capture cannot wait for work outside it: graphs run on lane 0's buffers, see Generator)
+        cur = torch.cuda.current_stream()
+        cur.wait_event(self.event)
+        for t in self.tensors:
+            t.record_stream(cur)
+        self.seen.add(sid)
+
+
+class StreamTail:
+    """The end of the last piece of work that went through state shared by all streams (Generator's per-op forwards: the lane-0
+    style tables).  `record()` marks the current stream's position, `wait()` orders the current stream behind the last mark when
+    that was made on another stream.  One event, re-recorded: a wait refers to the record that preceded it."""
+    __slots__ = ("event", "sid")
+
+    def __init__(self):
+        self.event, self.sid = None, None
+
+    def __reduce__(self):
+        return (StreamTail, ())
+
+    def record(self):
+        if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
+            return
+        if self.event is None:
+            self.event = torch.cuda.Event()
+        self.event.record()
+        self.sid = stream_ptr()
+
+    def wait(self):
+        if self.sid is None or self.sid == stream_ptr() or torch.cuda.is_current_stream_capturing():
+            return
+        torch.cuda.current_stream().wait_event(self.event)
+
+
 class LinearTable:
     """A device-resident table of independent dense heads evaluated by one launch."""
 

@@ -14,6 +14,11 @@ makes calls on different streams independent of each other; this class supplies 
 `submit` orders the lane's stream behind everything the caller's stream has been given so far (the call's inputs), runs the
 forward there, and marks the returned tensors as in use by the caller's stream (allocator safety).  Nothing makes the caller's
 stream wait until `drain()` -- a wait per view would put every view behind the previous one again.
+Forwards WITHOUT a forward plan (kernel_size = 3 decoders, untiled widths, `inject_index` style mixing) run on the modules' lane-0
+tables whatever stream they are on.  They gain nothing from lanes: `Generator.forward` orders each behind the previous one, and
+`run` orders a lane behind the lane of the previous call when that call was such a forward, so they execute one after the other.
+Device buffers that are built once and read by every lane (the renderer's packed weight streams, the truncation means, a noise
+projector) carry a fence (hip.BuildFence): a lane waits for the build the first time it reads them, then never again.
 Measured (MI355X, FFHQ 1024^2, D = 2, N = 24, batch 1): 0.318 ms per view with two lanes against 0.363 with one (+14 % views/s);
 a third lane adds nothing.  The lanes' streams are tested to run concurrently (`lane_streams`): two HIP streams may share a
 hardware queue, and a pipeline on such a pair is slower than no pipeline.
@@ -60,21 +65,41 @@ def _overtakes(a, b, dev):
 
 
 def lane_streams(device, n):
-    """`n` streams of `device` that run concurrently with each other (see above); fewer distinct queues than lanes: the rest are
-    taken as they come."""
+    """`n` DISTINCT streams of `device` that run concurrently with each other (see above); fewer distinct queues than lanes: the
+    rest are taken as they come.  torch hands its streams out of a fixed set per device, round-robin: in a process that has made
+    many, a new `torch.cuda.Stream` can be one the pool already holds -- two lanes on it would share one forward plan -- so
+    candidates are compared by their raw handle."""
     dev = torch.device(device)
     pool = _LANE_STREAMS.setdefault(str(dev), [])
+
+    def new(s):
+        return all(p.cuda_stream != s.cuda_stream for p in pool)
+
     tries = 0
     while len(pool) < n and tries < 24:
         tries += 1
         s = torch.cuda.Stream(device=dev)
-        if all(_overtakes(p, s, dev) for p in pool):
+        if new(s) and all(_overtakes(p, s, dev) for p in pool):
             pool.append(s)
         else:
             _REJECTED.append(s)
-    while len(pool) < n:
-        pool.append(torch.cuda.Stream(device=dev))
+    for s in _REJECTED:                                   # (they share a queue with a lane, but they are streams of their own)
+        if len(pool) < n and s.device == pool_device(dev) and new(s):
+            pool.append(s)
+    tries = 0
+    while len(pool) < n and tries < 64:
+        tries += 1
+        s = torch.cuda.Stream(device=dev)
+        if new(s):
+            pool.append(s)
+    if len(pool) < n:
+        raise RuntimeError(f"{n} lanes asked for, but only {len(pool)} distinct streams could be had on {dev}")
     return pool[:n]
+
+
+def pool_device(dev):
+    """`dev` with its index filled in (a stream's .device always carries one)."""
+    return dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())
 
 
 class ViewPipeline:
@@ -87,6 +112,7 @@ class ViewPipeline:
         self.streams = lane_streams(self.device, lanes) if self.device.type == "cuda" and lanes > 1 else []
         self._next = 0
         self._dirty = set()
+        self._per_op_lane = None               # the lane of the previous call when that call ran a forward without a plan
         self._callers = {}                     # raw stream id -> torch.cuda.Stream of a calling stream (the object costs ~10 us to build)
 
     def _caller_stream(self):
@@ -128,16 +154,20 @@ class ViewPipeline:
         cur = self._caller_stream()
         if wait_inputs:
             s.wait_stream(cur)                   # the call's inputs (and whatever else the caller enqueued before)
+        if self._per_op_lane is not None and self._per_op_lane != i:
+            s.wait_stream(self.streams[self._per_op_lane])      # (unplanned forwards share the lane-0 tables: one after the other)
         torch.cuda.set_stream(s)                 # (the `with torch.cuda.stream(s)` context costs ~25 us of host time per use)
         G = self.G
         if G is not None:
             G._views_in_flight = self.lanes if _HINT else 1     # (a hint for the forward's launches: cips3d_forward_io.views_in_flight)
+            per_op = G.__dict__.get("_per_op_calls", 0)
         try:
             out = fn()
         finally:
             torch.cuda.set_stream(cur)
             if G is not None:
                 G._views_in_flight = 1
+        self._per_op_lane = i if G is not None and G.__dict__.get("_per_op_calls", 0) != per_op else None
         vals = out.values() if isinstance(out, dict) else (out if isinstance(out, (tuple, list)) else (out,))
         for v in vals:                           # (allocated on the lane's stream, read on the caller's)
             if torch.is_tensor(v):

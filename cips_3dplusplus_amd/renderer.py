@@ -109,9 +109,11 @@ class VolumeFeatureRenderer(nn.Module):
         self.sigmoid_beta = nn.Parameter(0.1 * torch.ones(1))
         self.network = SirenGenerator(D=N_layers_renderer, W=hidden_dim, style_dim=style_dim, input_ch=input_dim,
                                       input_ch_views=view_dim, output_features=output_features)
-        self._derived = None      # (key, packed, layer_bias)
-        self._packed_t = None
-        self._packed32 = None     # (key, exact-fp32 weight stream): built on first use in "fp32_exact" precision
+        # Built on first use, on whichever stream calls first, and read from every stream a forward is issued on (pipeline.py's
+        # lanes): each entry carries a hip.BuildFence, and every accessor below orders the calling stream behind the build once.
+        self._derived = None      # (key, packed, layer_bias, fence)
+        self._packed_t = None     # (transposed stream, fence)
+        self._packed32 = None     # (key, exact-fp32 weight stream, fence): built on first use in "fp32_exact" precision
         self.exact_fp32 = False
         self._tables = {}         # B -> (styles_buf, film_buf, LinearTable)
 
@@ -150,7 +152,9 @@ class VolumeFeatureRenderer(nn.Module):
             D, H = self.N_layers_renderer, self.hidden_dim
             with torch.no_grad():
                 w_hidden = torch.stack([l.weight for l in net.pts_linears[1:]]).contiguous() if D > 1 else None
-                self._packed32 = (key, hip.nerf_pack_weights32(w_hidden, net.views_linears.weight.detach().contiguous(), H, D))
+                p32 = hip.nerf_pack_weights32(w_hidden, net.views_linears.weight.detach().contiguous(), H, D)
+            self._packed32 = (key, p32, hip.BuildFence(p32))
+        self._packed32[2].wait()
         return self._packed32[1]
 
     def _derived_buffers(self):
@@ -162,8 +166,9 @@ class VolumeFeatureRenderer(nn.Module):
                 w_hidden = torch.stack([l.weight for l in net.pts_linears[1:]]).contiguous() if D > 1 else None
                 packed = hip.nerf_pack_weights(w_hidden, net.views_linears.weight.detach().contiguous(), H, D)
                 layer_bias = torch.stack([l.bias for l in net.pts_linears] + [net.views_linears.bias]).contiguous()
-            self._derived = (key, packed, layer_bias)
+            self._derived = (key, packed, layer_bias, hip.BuildFence(packed, layer_bias))
             self._packed_t = None
+        self._derived[3].wait()
         return self._derived[1], self._derived[2]
 
     def _packed_transposed(self):
@@ -174,8 +179,10 @@ class VolumeFeatureRenderer(nn.Module):
             D, H = self.N_layers_renderer, self.hidden_dim
             with torch.no_grad():
                 w_hidden = torch.stack([l.weight for l in net.pts_linears[1:]]).contiguous() if D > 1 else None
-                self._packed_t = hip.nerf_pack_weights_t(w_hidden, net.views_linears.weight.detach().contiguous(), packed, H, D)
-        return self._packed_t
+                pt = hip.nerf_pack_weights_t(w_hidden, net.views_linears.weight.detach().contiguous(), packed, H, D)
+            self._packed_t = (pt, hip.BuildFence(pt))
+        self._packed_t[1].wait()
+        return self._packed_t[0]
 
     def _film_table(self, B, device, lane=0):
         net = self.network

@@ -30,6 +30,24 @@ def test_cpu_pipeline_runs_inline_and_in_order():
     pipe.wait_lane(0); pipe.drain()                        # no-ops without streams
 
 
+def test_fences_are_noops_without_a_device_and_survive_a_copy():
+    """hip.BuildFence / hip.StreamTail (the cross-lane ordering of shared buffers and of per-op forwards): nothing to order on a
+    CPU generator, and a copied or pickled owner gets fresh ones instead of a copy of a device event."""
+    import copy
+    import pickle
+    from cips_3dplusplus_amd import hip
+    fence, tail = hip.BuildFence(torch.zeros(2)), hip.StreamTail()
+    fence.wait(); tail.wait(); tail.record(); tail.wait()
+    if not torch.cuda.is_available():
+        assert fence.event is None and fence.tensors == [] and tail.event is None
+    holder = torch.nn.Linear(2, 2)
+    holder.cache = ("key", torch.zeros(1), fence, tail)
+    for clone in (copy.deepcopy(holder), pickle.loads(pickle.dumps(holder))):
+        assert isinstance(clone.cache[2], hip.BuildFence) and clone.cache[2] is not fence
+        assert isinstance(clone.cache[3], hip.StreamTail) and clone.cache[3].sid is None
+        clone.cache[2].wait(); clone.cache[3].wait()
+
+
 def test_lane_count_is_validated():
     with pytest.raises(ValueError):
         ViewPipeline(_G(), lanes=0)
