@@ -136,6 +136,16 @@ class VggSplitIO(C.Structure):
     _fields_ = [("io", VggIO), ("range", C.c_void_p)]
 
 
+LPIPS_LAYERS = 5                # CIPS3D_LPIPS_LAYERS
+
+
+class LpipsIO(C.Structure):
+    """cips3d_lpips_io (include/cips3d_hip.h)."""
+    _fields_ = [("trunk", C.c_void_p), ("lin", C.c_void_p * LPIPS_LAYERS), ("target", C.c_void_p * LPIPS_LAYERS),
+                ("map", C.c_void_p * LPIPS_LAYERS), ("partial", C.c_void_p), ("record", C.c_void_p), ("row", C.c_int64),
+                ("B", C.c_int32), ("target_broadcast", C.c_int32), ("heads_only", C.c_int32), ("pad_", C.c_int32)]
+
+
 class NerfBwdGeom(C.Structure):
     _fields_ = [("cam_poses", C.c_void_p), ("focals", C.c_void_p), ("near_", C.c_void_p), ("far_", C.c_void_p),
                 ("perturb_u", C.c_void_p), ("B", C.c_int32), ("img_size", C.c_int32), ("n_samples", C.c_int32),
@@ -323,10 +333,17 @@ _SIGS = {
                                      c_i64, C.c_void_p]),
     "cips3d_image_metrics_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "cips3d_image_metrics_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "cips3d_lpips_supported": (c_int, [c_int, c_int, c_int]),
+    "cips3d_lpips_partial_bytes": (c_i64, [c_int]),
+    "cips3d_lpips_head": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "cips3d_lpips": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_lpips_split": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_sizeof_lpips_io": (c_int, []),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 38           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 39           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -335,7 +352,7 @@ def _struct_table():
     from . import plan
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
-            11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO}
+            11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO}
 
 
 def load(build_if_missing=True):

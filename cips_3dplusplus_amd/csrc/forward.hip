@@ -33,6 +33,7 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 13: return (int64_t)sizeof(cips3d_vgg_io);
     case 14: return (int64_t)sizeof(cips3d_vgg_split_ctx);
     case 15: return (int64_t)sizeof(cips3d_vgg_split_io);
+    case 16: return (int64_t)sizeof(cips3d_lpips_io);
     default: return -1;
   }
 }

@@ -350,3 +350,267 @@ class VGG16ConvLoss(nn.Module):
         if image_thumb is None:
             image_thumb = self._thumb(image, img_size)
         return self.taps(image), self.taps(image_thumb)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# LPIPS v0.1, net = 'vgg' (csrc/lpips.hip): the trunk above plus a head on the taps behind five ReLUs.
+#
+#     net = LPIPS('vgg', weights='vgg16-397923af.pth', lin_weights='vgg.pth')      # files the user has
+#     net = LPIPS('vgg_random', generator=g)                                       # Kaiming convs, random lin weights >= 0
+#     d = net(a, b)                                # float64 [B] on the CPU, one read
+#     t = net.prepare(target);  d = net(x, t)      # the target's taps computed once; the same bits as net(x, target)
+#
+# The scaling layer of LPIPS, (x - shift) / scale on images in [-1, 1], is the trunk's own normalisation: 2 mean - 1 = shift and
+# 2 std = scale with the ImageNet constants.  Not built: 'alex' / 'squeeze', the up-sampled spatial map (`spatial=True` returns
+# the five maps at their own sizes), LPIPS as a differentiable loss.
+LPIPS_CONVS = (1, 3, 6, 9, 12)                    # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+LPIPS_CHANNELS = tuple(CHANNELS[l] for l in LPIPS_CONVS)
+LPIPS_NETS = ("vgg", "vgg_random", "alex", "squeeze")
+_LPIPS_ROW = _lib.LPIPS_LAYERS + 1                # a record row: {total, layer 0 .. 4} float64
+
+
+def lin_weights_from_state_dict(sd):
+    """[lin_k [C_k]] fp32 from the lpips package's vgg.pth layout, `lin{k}.model.1.weight` of shape [1, C_k, 1, 1]; any other
+    key is ignored.  A missing key or a wrong width raises."""
+    out = []
+    for k, c in enumerate(LPIPS_CHANNELS):
+        key = f"lin{k}.model.1.weight"
+        if key not in sd:
+            raise KeyError(f"LPIPS lin state dict has no '{key}' (expected the lpips package's vgg.pth layout)")
+        if tuple(sd[key].shape) != (1, c, 1, 1):
+            raise ValueError(f"'{key}' has shape {tuple(sd[key].shape)}, expected {(1, c, 1, 1)}")
+        out.append(sd[key].detach().float().reshape(c).clone())
+    return out
+
+
+def random_lin_weights(generator=None):
+    """Non-negative lin weights rand(C_k) * 2 / C_k (mean 1 / C_k, so a layer's value stays of the order of 1)."""
+    return [torch.rand(c, generator=generator) * (2.0 / c) for c in LPIPS_CHANNELS]
+
+
+def _load_sd(obj):
+    return torch.load(obj, map_location="cpu") if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__") else obj
+
+
+def _lpips_check_supported(B, H, W):
+    code = _lib.load().cips3d_lpips_supported(int(B), int(H), int(W))
+    if code != 0:
+        raise ValueError(f"LPIPS: B = {B}, H = {H}, W = {W} is outside the size contract of the VGG16 trunk (B >= 1, H and W "
+                         f"multiples of 16): {_lib.load().cips3d_strerror(code).decode()}")
+
+
+def _lpips_image(x, name):
+    """[B,3,H,W] or [3,H,W], fp32 in [-1, 1] or uint8 (x / 127.5 - 1, the pairing of metrics.py) -> [B,3,H,W] fp32 on the GPU."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor, got {type(x).__name__}")
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{name} must be [B,3,H,W] or [3,H,W], got {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{name} must be float32 (in [-1, 1]) or uint8, got {x.dtype}")
+    _lpips_check_supported(x.shape[0], x.shape[2], x.shape[3])
+    if not x.is_cuda:
+        raise RuntimeError("LPIPS runs on the GPU only (the cips3d HIP path has no CPU fallback)")
+    x = x.detach()
+    if x.dtype == torch.uint8:
+        x = x.float() / 127.5 - 1.0
+    return x.contiguous()
+
+
+class LPIPSTarget:
+    """The five pre-ReLU taps of a prepared target ([Bt,C_k,H_k,W_k] on the device) and the image size they belong to."""
+    __slots__ = ("taps", "shape")
+
+    def __init__(self, taps, shape):
+        self.taps, self.shape = taps, tuple(shape)
+
+
+def lpips_layer_distance(za, zb, lin):
+    """One layer of the head on given maps: za, zb [B,C,H,W] fp32 PRE-ReLU (the ReLU is applied on load), lin [C], C in {64,
+    128, 256, 512} -> (map [B,1,H,W] fp32, mean [B] float64), both on the device; two launches, no synchronisation."""
+    if za.dim() != 4 or za.shape != zb.shape:
+        raise ValueError(f"za and zb must be [B,C,H,W] of one shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    B, Cc, H, W = za.shape
+    if lin.numel() != Cc:
+        raise ValueError(f"lin has {lin.numel()} weights for {Cc} channels")
+    lib = _lib.load()
+    lin = lin.reshape(Cc)
+    pa, pb, pl = _lib.dev_ptr(za, "za"), _lib.dev_ptr(zb, "zb"), _lib.dev_ptr(lin, "lin")
+    dmap = torch.empty(B, 1, H, W, device=za.device)
+    mean = torch.empty(B, device=za.device, dtype=torch.float64)
+    nbytes = int(lib.cips3d_lpips_partial_bytes(B))
+    if nbytes < 0:
+        raise RuntimeError(f"cips3d_lpips_partial_bytes({B}) failed ({nbytes})")
+    partial = torch.empty(nbytes // 8, device=za.device, dtype=torch.float64)
+    with torch.cuda.device(za.device):
+        _lib.check(lib.cips3d_lpips_head(pa, pb, pl, B, Cc, H, W, dmap.data_ptr(), partial.data_ptr(), mean.data_ptr(),
+                                         _lib.stream_ptr()), "cips3d_lpips_head")
+    return dmap, mean
+
+
+class LPIPS(nn.Module):
+    def __init__(self, net="vgg", weights=None, lin_weights=None, generator=None, precision="fp32_exact"):
+        super().__init__()
+        if net not in LPIPS_NETS:
+            raise ValueError(f"net must be one of {LPIPS_NETS}, got {net!r}")
+        if net in ("alex", "squeeze"):
+            raise NotImplementedError(f"LPIPS(net={net!r}) is not implemented: only the VGG16 form is built ('vgg', 'vgg_random')")
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        self.net, self.precision = net, precision
+        if net == "vgg_random":
+            self.trunk = VGG16ConvLoss("vgg16_conv_random", generator=generator, precision=precision)
+            lins = random_lin_weights(generator)
+        else:
+            if weights is None or lin_weights is None:
+                raise RuntimeError(
+                    "LPIPS('vgg') needs two pretrained files: pass weights= (a path to, or the state dict of, torchvision's "
+                    "vgg16 checkpoint with features.N.weight / features.N.bias) and lin_weights= (a path to, or the state dict "
+                    "of, the lpips package's weights/v0.1/vgg.pth with lin{k}.model.1.weight), or use net='vgg_random' for a "
+                    "randomly initialised network")
+            self.trunk = VGG16ConvLoss("vgg16_conv", weights=weights, precision=precision)
+            lins = lin_weights_from_state_dict(_load_sd(lin_weights))
+        for k, w in enumerate(lins):
+            self.register_buffer(f"lin_{k}", w.contiguous())
+        self._lin_dev = {}                 # device -> the five lin tensors there
+
+    def lin_weights(self):
+        return [getattr(self, f"lin_{k}") for k in range(_lib.LPIPS_LAYERS)]
+
+    def _lins(self, device):
+        """The five lin vectors on `device`.  Copies are kept per device and made again when a buffer was replaced or written
+        (load_state_dict, .to(), an in-place edit): the stamp is every buffer's (data_ptr, _version)."""
+        key = (device.type, device.index)
+        stamp = tuple((w.data_ptr(), w._version) for w in self.lin_weights())
+        if key not in self._lin_dev or self._lin_dev[key][0] != stamp:
+            self._lin_dev[key] = (stamp, [w.to(device=device, dtype=torch.float32).contiguous() for w in self.lin_weights()])
+        return self._lin_dev[key][1]
+
+    def _enqueue(self, x, target, record, row, partial, maps=None, run=None, heads_only=False):
+        """The trunk on x ([2B,3,H,W]: a then b; with `target`, [B,3,H,W]) and the head, rows `row` .. of `record`.  Only
+        enqueues: no host copy, no synchronisation.  `run`: the trunk's buffers of an earlier `_new_run(x, 1)` on this very x
+        (None: allocated here); `heads_only`: the trunk is not run, `run` holds its maps already."""
+        if run is None:
+            run = self.trunk._new_run(x, 1)
+        lio = _lib.LpipsIO()
+        lio.heads_only = int(heads_only)
+        lio.trunk = C.addressof(run.arg)
+        B = x.shape[0] if target is not None else x.shape[0] // 2
+        for k, w in enumerate(self._lins(x.device)):
+            lio.lin[k] = w.data_ptr()
+            if target is not None:
+                lio.target[k] = target.taps[k].data_ptr()
+            if maps is not None:
+                lio.map[k] = maps[k].data_ptr()
+        lio.partial, lio.record, lio.row, lio.B = partial.data_ptr(), record.data_ptr(), int(row), B
+        lio.target_broadcast = int(target is not None and target.taps[0].shape[0] == 1 and B > 1)
+        fn = "cips3d_lpips_split" if self.precision == "split_fp16" else "cips3d_lpips"
+        with torch.cuda.device(x.device):
+            _lib.check(getattr(_lib.load(), fn)(C.byref(self.trunk._ctx(x.device)), C.byref(lio), _lib.stream_ptr()), fn)
+
+    def _partial(self, B, device):
+        return torch.empty(int(_lib.load().cips3d_lpips_partial_bytes(B)) // 8, device=device, dtype=torch.float64)
+
+    def _check_target(self, a, target):
+        if not isinstance(target, LPIPSTarget):
+            raise ValueError("the second argument must be an image tensor or the result of LPIPS.prepare")
+        Bt, H, W = target.shape
+        if (H, W) != tuple(a.shape[2:]):
+            raise ValueError(f"the prepared target is {H} x {W}, the image {a.shape[2]} x {a.shape[3]}")
+        if Bt not in (1, a.shape[0]):
+            raise ValueError(f"the prepared target holds {Bt} images, the batch {a.shape[0]}")
+        if target.taps[0].device != a.device:
+            raise ValueError(f"the prepared target is on {target.taps[0].device}, the image on {a.device}")
+
+    def prepare(self, target):
+        """The target's five taps, computed once: `forward(image, prepared)` then runs the trunk on `image` alone and gives the
+        bits of `forward(image, target)` (the trunk does not depend on the batch).  One image serves every sample of a batch."""
+        t = _lpips_image(target, "target")
+        with torch.no_grad():
+            run = self.trunk._features(t, 1)
+            return LPIPSTarget([run.z[l].clone() for l in LPIPS_CONVS], (t.shape[0], t.shape[2], t.shape[3]))
+
+    def forward(self, a, b, return_layers=False, spatial=False):
+        """LPIPS of a against b (an image batch like a, or `prepare(b)`): float64 [B] on the CPU through one read; with
+        `return_layers` also the five layers' values [B, 5]; with `spatial` also the five distance maps [B,1,H_k,W_k] on the
+        device, at their own sizes."""
+        a = _lpips_image(a, "a")
+        B, _, H, W = a.shape
+        if isinstance(b, torch.Tensor):
+            b = _lpips_image(b, "b")
+            if a.shape != b.shape:
+                raise ValueError(f"the images differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+            if a.device != b.device:
+                raise ValueError(f"the images are on different devices: {a.device} and {b.device}")
+            x, target = torch.cat([a, b], dim=0), None
+        else:
+            self._check_target(a, b)
+            x, target = a, b
+        maps = [torch.empty(B, 1, h, w, device=a.device) for _, h, w in (conv_shapes(H, W)[l] for l in LPIPS_CONVS)] \
+            if spatial else None
+        record = torch.empty(B, _LPIPS_ROW, device=a.device, dtype=torch.float64)
+        self._enqueue(x, target, record, 0, self._partial(B, a.device), maps)
+        rec = record.cpu()                          # the single device-to-host read
+        out = (rec[:, 0].contiguous(),)
+        if return_layers:
+            out += (rec[:, 1:].contiguous(),)
+        if spatial:
+            out += (maps,)
+        return out[0] if len(out) == 1 else out
+
+
+class LPIPSLog:
+    """LPIPS of a sequence of images against one target, kept on the device until `result()` (metrics.MetricsLog's pattern).
+
+    `target`: [1,3,H,W] or [3,H,W], prepared once; the record, the scratch and the trunk's buffers are allocated here.
+    `update(step, image)` copies the image into the log's own input buffer and enqueues the trunk and the head on the current
+    stream, then returns -- no device-to-host copy, no synchronisation, no allocation for an fp32 image; `result()` makes the
+    single read.  Updates belong on one stream (they share the buffers)."""
+
+    def __init__(self, net, target, capacity):
+        if not isinstance(net, LPIPS):
+            raise ValueError(f"net must be an LPIPS instance, got {type(net).__name__}")
+        if int(capacity) < 1:
+            raise ValueError(f"capacity must be at least 1, got {capacity}")
+        if isinstance(target, torch.Tensor) and target.dim() == 4 and target.shape[0] != 1:
+            raise ValueError(f"target must be one image, got a batch of {target.shape[0]}")
+        self.net, self.capacity = net, int(capacity)
+        self.target = net.prepare(target)
+        device = self.target.taps[0].device
+        self.steps = {}                      # row -> step, in the order of the updates
+        self._record = torch.zeros(self.capacity, _LPIPS_ROW, dtype=torch.float64, device=device)
+        self._partial = net._partial(1, device)
+        # the image's staging copy and the trunk's buffers, allocated once: an update never meets the allocator's slow path
+        self._x = torch.empty(1, 3, self.target.shape[1], self.target.shape[2], device=device)
+        self._run = net.trunk._new_run(self._x, 1)
+
+    def _next_row(self):
+        for row in range(self.capacity):
+            if row not in self.steps:
+                return row
+        raise ValueError(f"the record is full ({self.capacity} rows)")
+
+    def update(self, step, image, row=None):
+        """Record the LPIPS of `image` (one image of the target's size) under `step`, in the next free row or in `row`."""
+        image = _lpips_image(image, "image")
+        if image.shape[0] != 1:
+            raise ValueError(f"image must be one image, got a batch of {image.shape[0]}")
+        self.net._check_target(image, self.target)
+        row = self._next_row() if row is None else int(row)
+        if not 0 <= row < self.capacity:
+            raise ValueError(f"row {row} is outside the record ({self.capacity} rows)")
+        self._x.copy_(image)                 # (device to device, on the current stream)
+        self.net._enqueue(self._x, self.target, self._record, row, self._partial, run=self._run)
+        self.steps.pop(row, None)            # (a row written again moves to the end of the order)
+        self.steps[row] = int(step)
+        return row
+
+    def result(self):
+        """-> {"steps": [..], "lpips": float64 [n], "lpips_layers": float64 [n, 5]} of the rows written, in update order."""
+        rows = list(self.steps)
+        if not rows:
+            return {"steps": [], "lpips": torch.empty(0, dtype=torch.float64),
+                    "lpips_layers": torch.empty(0, _lib.LPIPS_LAYERS, dtype=torch.float64)}
+        rec = self._record.cpu()[torch.tensor(rows)]
+        return {"steps": [self.steps[r] for r in rows], "lpips": rec[:, 0].contiguous(), "lpips_layers": rec[:, 1:].contiguous()}

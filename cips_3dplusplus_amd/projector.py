@@ -226,7 +226,7 @@ class FlipProjector:
                       bs_cam=2, bs_render=1, bs_decoder=2, lr_cam=0.02, lr_render_w=0.001, lr_decoder_w=0.01,
                       lr_decoder_params=0.005, lr_noise=0.001, truncation_psi=1.0, flip_w_decoder_every=10,
                       azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
-                      mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0):
+                      mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0, lpips_metric=None):
         """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
         `mask_background`: from the appearance phase on, the image's gradient only flows where the render's foreground mask says
         so (mask_blend; the thumbnail is not blended, as in the reference).  `mse_weight` > 0 adds mse_weight x
@@ -236,7 +236,11 @@ class FlipProjector:
         and at the last one (the reference's logging condition, :1125-1139) -- two launches per logged step, no copy and no
         synchronisation inside the loop.  After the loop the image is rendered once more under no_grad at the optimised pose and
         styles (:1229-1242); the dict gains "psnr" and "ssim" of that image (floats, :1266-1279) and "metrics_history"
-        ({"steps", "psnr", "ssim"} of the logged steps), all from one read.  0: nothing new runs and the dict has no new keys."""
+        ({"steps", "psnr", "ssim"} of the logged steps), all from one read.  0: nothing new runs and the dict has no new keys.
+        `lpips_metric` (the reference's argument, :694-707, 1267-1280; needs `target_images`): a perceptual.LPIPS instance.  The
+        final re-render's LPIPS of view 0 against target_images[0] becomes "lpips" (a float); with `metrics_every` > 0 the logged
+        steps' values go to metrics_history["lpips"], enqueued beside the PSNR / SSIM launches (perceptual.LPIPSLog) and read
+        once.  None: no network is built (the reference's default downloads one) and nothing changes."""
         if mse_weight > 0 and target_images is None:
             raise ValueError("project_wplus: mse_weight > 0 needs target_images")
         metrics_log = None
@@ -248,6 +252,16 @@ class FlipProjector:
             from .metrics import MetricsLog
             n_logged = len([s for s in range(N_steps_pose + N_steps_app) if s % metrics_every == 0 or s == N_steps_pose + N_steps_app - 1])
             metrics_log = MetricsLog(target_images[0:1].detach().to(self.device), n_logged + 1)      # (+ 1: the final re-render)
+        lpips_log = None
+        if lpips_metric is not None:
+            if target_images is None:
+                raise ValueError("project_wplus: lpips_metric needs target_images")
+            from .perceptual import LPIPS, LPIPSLog
+            if not isinstance(lpips_metric, LPIPS):
+                raise ValueError(f"project_wplus: lpips_metric must be a perceptual.LPIPS instance, got {type(lpips_metric).__name__}")
+            n_logged = len([s for s in range(N_steps_pose + N_steps_app) if s % metrics_every == 0 or s == N_steps_pose + N_steps_app - 1]) \
+                if metrics_every > 0 else 0
+            lpips_log = LPIPSLog(lpips_metric, target_images[0:1].detach().to(self.device), n_logged + 1)
         if mse_weight > 0:
             target_images = target_images.detach().to(self.device, torch.float32).contiguous()
         G = copy.deepcopy(self.G).eval().requires_grad_(False).to(self.device)
@@ -289,6 +303,8 @@ class FlipProjector:
                 rot=loc, flip_w_decoder=flip_w_decoder)
             if metrics_log is not None and (step % metrics_every == 0 or step == N_steps - 1):
                 metrics_log.update(step, rgb[0:1])
+                if lpips_log is not None:
+                    lpips_log.update(step, rgb[0:1])
             if mask_background and step >= N_steps_pose:
                 rgb = mask_blend(rgb, mask)
             loss = loss_fn(rgb, thumb)                   # (term order of projector_v10.py:1200: perceptual + mse + regulariser)
@@ -313,13 +329,22 @@ class FlipProjector:
                "w_decoder_opt": w_decoder.detach(), "render_state_dict": G.renderer.state_dict(),
                "decoder_state_dict": G.decoder.state_dict(), "noise_bufs": [b.detach() for b in noise_bufs], "padding": 0,
                "loss_history": torch.stack(history).cpu() if history else None, "G": G}
-        if metrics_log is not None:
+        if metrics_log is not None or lpips_log is not None:
             with torch.no_grad():                        # projector_v10.py:1229-1242: the clean re-render at the optimised state
                 proj_rgb, _, _ = self.g_forward(
                     G, w_render, w_decoder if w_decoder.shape[0] == 2 else w_decoder.repeat(2, 1, 1), noise_bufs, cam_cfg, nerf_cfg,
                     rot=loc)
-                metrics_log.update(N_steps, proj_rgb[0:1])
+                if metrics_log is not None:
+                    metrics_log.update(N_steps, proj_rgb[0:1])
+                if lpips_log is not None:
+                    lpips_log.update(N_steps, proj_rgb[0:1])
+        if metrics_log is not None:
             res = metrics_log.result()                   # the single device-to-host read
             out["psnr"], out["ssim"] = float(res["psnr"][-1]), float(res["ssim"][-1])
             out["metrics_history"] = {"steps": res["steps"][:-1], "psnr": res["psnr"][:-1], "ssim": res["ssim"][:-1]}
+        if lpips_log is not None:
+            res = lpips_log.result()
+            out["lpips"] = float(res["lpips"][-1])
+            if metrics_log is not None:
+                out["metrics_history"]["lpips"] = res["lpips"][:-1]
         return out

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 38  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 39  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1360,6 +1360,48 @@ int cips3d_image_metrics(const void* a, int a_is_u8, const void* b, int b_is_u8,
                          void* record, int64_t row, void* stream);
 int64_t cips3d_image_metrics_workspace_bytes(int B, int C, int H, int W);
 int cips3d_image_metrics_tile(int* tile_h, int* tile_w);
+
+/* LPIPS v0.1, net = 'vgg', spatial = False, on the device (csrc/lpips.hip): the VGG16 trunk above plus a head on the taps
+ * BEHIND the ReLUs of convs 1, 3, 6, 9, 12 (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; C_k = 64, 128, 256, 512, 512).  For
+ * images a, b in [-1, 1] (io.normalize = 1 is LPIPS's own scaling layer: 2 mean - 1 = shift, 2 std = scale), per layer k:
+ *     f = relu(z);  n(p) = sqrt(sum_c f[c,p]^2) + 1e-10;  d_k(p) = sum_c lin_k[c] (fa[c,p] / na(p) - fb[c,p] / nb(p))^2
+ * layer value = mean_p d_k(p), LPIPS = the sum of the five.  Two passes over the channels (norms, then differences), fp32 per
+ * pixel, fp64 across pixels through per-workgroup partial sums added in a fixed order: no atomics, bit-identical run to run,
+ * independent of the batch a sample sits in, exactly 0 for identical inputs, symmetric in (a, b) bit for bit.
+ *
+ * cips3d_lpips_head     one layer on given maps: za, zb [B,C,H,W] PRE-ReLU (the ReLU is applied on load), lin [C], C in {64,
+ *                       128, 256, 512}, any H, W >= 1 -> map [B,1,H,W] (optional) and mean [B] (fp64).  Two launches.
+ * cips3d_lpips          the whole metric: the trunk of `io->trunk` (a cips3d_vgg_io with n_convs = 13; for cips3d_lpips_split
+ *                       a cips3d_vgg_split_io) and then five heads and one finalising launch.  target[k] all NULL: the trunk's
+ *                       batch is 2 B, images a (samples 0 .. B - 1) then b.  target[k] all given: the trunk's batch is B and
+ *                       target[k] holds b's pre-ReLU maps of conv 1, 3, 6, 9, 12 from an earlier trunk call ([B,C_k,H_k,W_k], or
+ *                       [1,C_k,H_k,W_k] for every sample with target_broadcast != 0); both forms give the same bits.  Sample i
+ *                       writes row `row + i` of `record`, rows of 6 float64: {LPIPS, layer 0 .. 4}.  map[k]: optional
+ *                       [B,1,H_k,W_k] distance maps.  partial: cips3d_lpips_partial_bytes(B) of scratch (the partial sums are
+ *                       keyed by sample: 80 KB each).  heads_only != 0: the trunk is not run, its z[1, 3, 6, 9, 12] are read as
+ *                       an earlier call left them (timing the head, re-weighting with other lin vectors).
+ * Nothing allocates or synchronises.  CIPS3D_E_BADARG, nothing launched: a null required pointer, B < 1, C outside the list, row
+ * < 0, a trunk io whose n_convs or batch does not fit, some but not all targets.  CIPS3D_E_UNSUPP: outside
+ * cips3d_lpips_supported (the trunk's contract: H, W multiples of 16; B <= 32767), or H W >= 2^31 - 64 / B > 65535 for the head. */
+#define CIPS3D_LPIPS_LAYERS 5
+typedef struct cips3d_lpips_io {
+  const void* trunk;                         /* cips3d_vgg_io (cips3d_lpips) / cips3d_vgg_split_io (cips3d_lpips_split) */
+  const float* lin[CIPS3D_LPIPS_LAYERS];     /* [C_k] */
+  const float* target[CIPS3D_LPIPS_LAYERS];  /* all NULL: the pair form */
+  float* map[CIPS3D_LPIPS_LAYERS];           /* NULL: no map of layer k */
+  void* partial;
+  void* record;                              /* rows of 6 float64 */
+  int64_t row;
+  int32_t B, target_broadcast;
+  int32_t heads_only, pad_;                  /* heads_only != 0: trunk->z already holds the maps; the six head launches alone */
+} cips3d_lpips_io;
+int cips3d_lpips_supported(int B, int H, int W);
+int64_t cips3d_lpips_partial_bytes(int B);
+int cips3d_lpips_head(const float* za, const float* zb, const float* lin, int B, int C, int H, int W, float* map, void* partial,
+                      double* mean, void* stream);
+int cips3d_lpips(const cips3d_vgg_ctx* ctx, const cips3d_lpips_io* io, void* stream);
+int cips3d_lpips_split(const cips3d_vgg_split_ctx* ctx, const cips3d_lpips_io* io, void* stream);
+int cips3d_sizeof_lpips_io(void);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
     python tools/bench_inversion.py [--depth 6] [--steps 200] [--res 256] [--loss surrogate|vgg16_conv_random]
                                      [--vgg-precision fp32_exact|split_fp16]
                                      [--optim-noise-bufs] [--mask-background] [--mse-weight W] [--metrics-every K]
+                                     [--lpips random]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
@@ -15,7 +16,9 @@ the arithmetic of its convolutions (perceptual.VGG16ConvLoss(precision=...)).
 --mse-weight W: W x MSE against the target images is added.  CIPS3D_FUSED_NOISE_REG=0 / CIPS3D_FUSED_MASK_BLEND=0 run the torch
 expressions of the first two instead of the HIP nodes (A/B).  With none of the three the run is what it was without them.
 --metrics-every K: PSNR / SSIM of the image against the target are logged on the device every K steps (project_wplus's
-`metrics_every`, metrics.MetricsLog); the JSON line gains the final re-render's "psnr" / "ssim" and the number of logged steps."""
+`metrics_every`, metrics.MetricsLog); the JSON line gains the final re-render's "psnr" / "ssim" and the number of logged steps.
+--lpips random: LPIPS against the target is reported too (project_wplus's `lpips_metric`: a perceptual.LPIPS('vgg_random') of
+--vgg-precision; logged beside PSNR / SSIM with --metrics-every); the JSON line gains the final re-render's "lpips"."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,6 +38,7 @@ ap.add_argument("--optim-noise-bufs", action="store_true")
 ap.add_argument("--mask-background", action="store_true")
 ap.add_argument("--mse-weight", type=float, default=0.0)
 ap.add_argument("--metrics-every", type=int, default=0)
+ap.add_argument("--lpips", choices=("random",), default=None)
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -69,12 +73,17 @@ if a.mse_weight > 0:
 if a.metrics_every > 0:
     extra.update(metrics_every=a.metrics_every, target_images=t_rgb)
     knobs["metrics_every"] = a.metrics_every
+if a.lpips:
+    from cips_3dplusplus_amd.perceptual import LPIPS
+    extra.update(lpips_metric=LPIPS("vgg_random", generator=torch.Generator().manual_seed(3), precision=a.vgg_precision),
+                 target_images=t_rgb)
+    knobs["lpips"] = a.lpips
 n_pose, n_app = a.steps, a.app_steps
 if a.mask_background:                   # the blend runs from the appearance phase on: time appearance steps
     extra.update(mask_background=True)
     knobs["mask_background"] = True
     n_pose, n_app = 0, a.steps + a.app_steps
-if set(knobs) - {"metrics_every"}:
+if set(knobs) - {"metrics_every", "lpips"}:
     from cips_3dplusplus_amd import projector as _P
     knobs["fused_noise_reg"], knobs["fused_mask_blend"] = _P.FUSED_NOISE_REG, _P.FUSED_MASK_BLEND
 out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=n_pose, N_steps_app=n_app,
@@ -86,4 +95,5 @@ print(json.dumps({"metric": "flip-inversion steps/s (fwd + bwd + Adam, batch 2)"
                   "ms_per_step": dt / n * 1e3, "config": {"workload": f"compcars_r{a.res}_D{a.depth}_N{a.n_samples}_B2_pose_phase",
                   "steps": a.steps, "app_steps": a.app_steps, **knobs, **({} if a.loss == "surrogate" else {"loss": a.loss, "vgg_precision": a.vgg_precision})}, "dtype": "f32", "data": "synthetic",
                   **({"psnr": out["psnr"], "ssim": out["ssim"], "metrics_logged": len(out["metrics_history"]["steps"])} if a.metrics_every > 0 else {}),
+                  **({"lpips": out["lpips"]} if a.lpips else {}),
                   "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}))
