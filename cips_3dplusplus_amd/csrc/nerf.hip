@@ -544,41 +544,25 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
   } else {
     const float focal = P.focals[b];
     const float* cw = P.cam_poses + 12 * b;
-    const int pi = rayc / S, pj = rayc - pi * S;
-    const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-    const float dcx = (px - (float)S * 0.5f) / focal;
-    const float dcy = -(py - (float)S * 0.5f) / focal;
-    const float dcz = -1.f;
-    dx = (dcx * cw[0] + dcy * cw[1]) + dcz * cw[2];
-    dy = (dcx * cw[4] + dcy * cw[5]) + dcz * cw[6];
-    dz = (dcx * cw[8] + dcy * cw[9]) + dcz * cw[10];
+    const NerfCamRay cam = nerf_cam_ray(focal, cw, S, rayc);
+    dx = cam.dx; dy = cam.dy; dz = cam.dz;
     ox = cw[3]; oy = cw[7]; oz = cw[11];
-    vx = P.static_viewdirs ? dcx : dx; vy = P.static_viewdirs ? dcy : dy; vz = P.static_viewdirs ? dcz : dz;
-    const float n = fmaxf(sqrtf((vx * vx + vy * vy) + vz * vz), 1e-12f);
-    vx /= n; vy /= n; vz /= n;
+    nerf_viewdir(cam, P.static_viewdirs, vx, vy, vz);
   }
-  const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);
+  const float dnorm = nerf_norm3(dx, dy, dz);
   const float u = (P.perturb_u && !explicit_geom) ? P.perturb_u[bray] : 0.f;
   // Wave-uniform floats that come out of the VALU live in VGPRs and, under this kernel's register pressure, get spilled
   // to scratch and reloaded one dependent round trip at a time at every sample start: pin them in SGPRs.
-  auto uniform = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-  const float span = uniform(farv - nearv);
+  const float span = cips3d_uniform(farv - nearv);
   const int N = P.n_samples;
-  // torch.linspace(0, 1 - 1/N, N): symmetric evaluation around the midpoint
-  const float t_end = a.t_end, t_step = a.t_step;
-  auto zbase = [&](int k) -> float {  // un-perturbed depth of sample k; k == N gives `far`
-    if (k >= N) return farv;
-    const float t = (k < N / 2) ? t_step * (float)k : t_end - t_step * (float)(N - 1 - k);
-    return nearv * (1.f - t) + farv * t;
-  };
+  const NerfDepths zs{nearv, farv, a.t_end, a.t_step, N};
   auto zsample = [&](int k) -> float {
     if (explicit_geom) {         // (opaque row index: the 64-bit row pointer would be a loop-invariant scratch spill)
       int64_t br = bray;
       asm volatile("" : "+v"(br));
       return P.x_z_vals[br * N + (k < N ? k : N - 1)];
     }
-    const float z0 = zbase(k);
-    return P.perturb_u ? z0 + (zbase(k + 1) - z0) * u : z0;
+    return zs.z(k, P.perturb_u != nullptr, u);
   };
 
   // ---- per-lane compositing state
@@ -707,7 +691,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
       // the hardware exp / log: the library forms held enough temporaries here to spill four registers of the default path
       sigma = sdf > 20.f ? sdf : __logf(1.f + __expf(sdf));
     } else {
-      sigma = sigmoidf_acc(-sdf / sig_beta) / sig_beta;
+      sigma = nerf_sdf_density(sdf, sig_beta);
     }
     const float alpha = 1.f - expf(-sigma * delta);
     const float w = live ? alpha * T : 0.f;
@@ -725,7 +709,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     c0 += b_rgb0; c1 += b_rgb1; c2 += b_rgb2;
 
     STAMP(4);   // view layer
-    cr = fmaf(w, sigmoidf_acc(c0), cr); cg = fmaf(w, sigmoidf_acc(c1), cg); cb = fmaf(w, sigmoidf_acc(c2), cb);
+    cr = fmaf(w, nerf_sigmoid(c0), cr); cg = fmaf(w, nerf_sigmoid(c1), cg); cb = fmaf(w, nerf_sigmoid(c2), cb);
     ax = fmaf(w, ptx, ax); ay = fmaf(w, pty, ay); az = fmaf(w, ptz, az);
     if (sg == N - 1) wlast = w;
     if (P.sdf && live && qd == 0) {
@@ -1111,8 +1095,7 @@ extern "C" int cips3d_nerf_render(const cips3d_nerf_params* p, void* stream) {
   a.tasks_per_view = ceil_div(a.groups * P.n_chunks, WAVES) * WAVES;
   a.chunk = ceil_div(P.n_samples, P.n_chunks);
   a.fuse_finish = fuse;
-  a.t_end = (float)(1.0 - 1.0 / (double)P.n_samples);
-  a.t_step = P.n_samples > 1 ? a.t_end / (float)(P.n_samples - 1) : 0.f;
+  nerf_linspace_consts(P.n_samples, a.t_end, a.t_step);
   hipStream_t st = as_stream(stream);
   switch (P.hidden) {
     case 32: return launch_render<2, 2>(a, st);

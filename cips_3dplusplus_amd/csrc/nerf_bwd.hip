@@ -17,6 +17,7 @@
 //   cips3d_nerf_bwd_camera     d(points), d(viewdirs) -> d(cam_poses)
 //   cips3d_camera_params_bwd   d(cam_poses) -> d(azim, elev)     (nerf_utils.py:344-436, forward-mode duals)
 #include "common.h"
+#include "nerf_geom.h"
 
 namespace {
 
@@ -29,50 +30,13 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-struct RayGeom {
-  float ox, oy, oz, dx, dy, dz, dcx, dcy, dcz, vx, vy, vz, vnorm, dnorm, nearv, farv, u, t_end, t_step;
-  int N, has_u;
-  __device__ __forceinline__ float zbase(int k) const {
-    if (k >= N) return farv;
-    const float t = (k < N / 2) ? t_step * (float)k : t_end - t_step * (float)(N - 1 - k);
-    return nearv * (1.f - t) + farv * t;
-  }
-  __device__ __forceinline__ float z(int k) const {
-    const float z0 = zbase(k);
-    return has_u ? z0 + (zbase(k + 1) - z0) * u : z0;
-  }
-};
-
-// identical arithmetic to the ray setup of nerf_render_kernel (nerf.hip; nerf_utils.py:38-121)
+// the ray of (view b, pixel `ray`): nerf_geom.h
 __device__ __forceinline__ RayGeom ray_geom(const cips3d_nerf_bwd_geom& G, int b, int ray) {
-  RayGeom r;
-  const int S = G.img_size;
-  const float focal = G.focals[b];
-  r.nearv = G.near_[b]; r.farv = G.far_[b];
-  const float* cw = G.cam_poses + 12 * b;
-  const int pi = ray / S, pj = ray - pi * S;
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  r.dcx = (px - (float)S * 0.5f) / focal;
-  r.dcy = -(py - (float)S * 0.5f) / focal;
-  r.dcz = -1.f;
-  r.dx = (r.dcx * cw[0] + r.dcy * cw[1]) + r.dcz * cw[2];
-  r.dy = (r.dcx * cw[4] + r.dcy * cw[5]) + r.dcz * cw[6];
-  r.dz = (r.dcx * cw[8] + r.dcy * cw[9]) + r.dcz * cw[10];
-  r.ox = cw[3]; r.oy = cw[7]; r.oz = cw[11];
-  const float rx = G.static_viewdirs ? r.dcx : r.dx, ry = G.static_viewdirs ? r.dcy : r.dy,
-              rz = G.static_viewdirs ? r.dcz : r.dz;
-  r.vnorm = fmaxf(sqrtf((rx * rx + ry * ry) + rz * rz), 1e-12f);
-  r.vx = rx / r.vnorm; r.vy = ry / r.vnorm; r.vz = rz / r.vnorm;
-  r.dnorm = sqrtf((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
-  r.has_u = G.perturb_u != nullptr;
-  r.u = r.has_u ? G.perturb_u[(int64_t)b * S * S + ray] : 0.f;
-  r.N = G.n_samples;
-  r.t_end = (float)(1.0 - 1.0 / (double)r.N);
-  r.t_step = r.N > 1 ? r.t_end / (float)(r.N - 1) : 0.f;
+  RayGeom r = ray_geom(G.cam_poses, G.focals, G.near_, G.far_, G.perturb_u, G.img_size, G.n_samples, G.static_viewdirs, b, ray,
+                       0.f, 0.f);
+  nerf_linspace_consts(r.N, r.t_end, r.t_step);   // (computed here, on the device: these kernels take no such arguments)
   return r;
 }
-
-__device__ __forceinline__ float sigmoid_acc(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---------------------------------------------------------------------------------------------- points + layer 0
 // grid (ceil(P/256), B).  ptsn [B,3,P]; pre0, h0 [B,H,P]; viewdirs [B,3,R].
@@ -228,7 +192,7 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
   for (int k = 0; k < N; ++k) {
     const float delta = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f) * r.dnorm;
     const float v = sp[(int64_t)k * R];
-    const float sigma = raw ? (v > 20.f ? v : log1pf(expf(v))) : sigmoid_acc(-v / beta) / beta;
+    const float sigma = raw ? nerf_softplus(v) : nerf_sdf_density(v, beta);
     const float alpha = 1.f - expf(-sigma * delta);
     tp[(int64_t)k * R] = T;
     wp[(int64_t)k * R] = alpha * T;
@@ -245,12 +209,12 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
     const int64_t o = (int64_t)k * R;
     const float dz = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f);
     const float delta = dz * r.dnorm;
-    const float sg = raw ? sigmoid_acc(sp[o]) : sigmoid_acc(-sp[o] / beta);
-    const float sigma = raw ? (sp[o] > 20.f ? sp[o] : log1pf(expf(sp[o]))) : sg / beta;
+    const float sg = raw ? nerf_sigmoid(sp[o]) : nerf_sigmoid(-sp[o] / beta);
+    const float sigma = raw ? nerf_softplus(sp[o]) : sg / beta;
     const float e = expf(-sigma * delta);
     const float alpha = 1.f - e;
     const float Tk = tp[o], wk = wp[o];
-    const float s0 = sigmoid_acc(cp[o]), s1 = sigmoid_acc(cp[P + o]), s2 = sigmoid_acc(cp[2 * P + o]);
+    const float s0 = nerf_sigmoid(cp[o]), s1 = nerf_sigmoid(cp[P + o]), s2 = nerf_sigmoid(cp[2 * P + o]);
     const float Gk = g[(int64_t)b * P + ray + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
     const float dalpha = Tk * Gk - S / ((1.f - alpha) + 1e-10f);
     S = fmaf(wk, Gk, S);
@@ -302,8 +266,8 @@ __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geo
   const float dz = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f);
   const float delta = dz * r.dnorm;
   const float v = sdf[(int64_t)b * P + o];
-  const float sg = raw ? sigmoid_acc(v) : sigmoid_acc(-v / beta);
-  const float sigma = raw ? (v > 20.f ? v : log1pf(expf(v))) : sg / beta;
+  const float sg = raw ? nerf_sigmoid(v) : nerf_sigmoid(-v / beta);
+  const float sigma = raw ? nerf_softplus(v) : sg / beta;
   const float e = expf(-sigma * delta);
   const float alpha = 1.f - e;
   const float f = (1.f - alpha) + 1e-10f;
@@ -311,7 +275,7 @@ __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geo
   const float d0 = dthumb[((int64_t)b * 3 + 0) * R + ray], d1 = dthumb[((int64_t)b * 3 + 1) * R + ray],
               d2 = dthumb[((int64_t)b * 3 + 2) * R + ray];
   const float* cp = crgb + (int64_t)b * 3 * P + o;
-  const float s0 = sigmoid_acc(cp[0]), s1 = sigmoid_acc(cp[P]), s2 = sigmoid_acc(cp[2 * P]);
+  const float s0 = nerf_sigmoid(cp[0]), s1 = nerf_sigmoid(cp[P]), s2 = nerf_sigmoid(cp[2 * P]);
   const float Gk = g[(int64_t)b * P + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
   Gl[li] = Gk;
   __syncthreads();

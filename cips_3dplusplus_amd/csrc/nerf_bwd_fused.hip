@@ -40,18 +40,6 @@
 #define cips3d_cos(x) ((x) * 0.001f)
 #endif
 
-// the forward recompute evaluates FiLM + sine like the render kernel (nerf.hip: CIPS3D_FILM_REVOLUTIONS)
-#ifndef CIPS3D_FILM_REVOLUTIONS
-#define CIPS3D_FILM_REVOLUTIONS 1
-#endif
-#if CIPS3D_FILM_REVOLUTIONS && !defined(CIPS3D_EXACT_SINE) && !defined(CIPS3D_REDUCED_SINE)
-#define STASH_FILM_UNIT 0.159154943091895336f
-#define STASH_FILM_SIN sin_revolutions
-#else
-#define STASH_FILM_UNIT 1.f
-#define STASH_FILM_SIN cips3d_sin
-#endif
-
 namespace {
 
 struct FusedArgs {
@@ -59,7 +47,7 @@ struct FusedArgs {
   int groups;          // ray groups of 16 per view
   int tasks_per_view;  // groups * n_chunks rounded up to a multiple of WAVES
   int chunk;           // samples per chunk
-  float t_end, t_step;
+  float t_end, t_step; // nerf_linspace_consts (nerf_geom.h)
   // partition of p.scratch
   float* tables;       // [10][H]: w_first^T [3][H], 2^s * view-direction columns [3][H], w_sigma [H], w_rgb [3][H]
   float* dFt;          // [B][R][H]
@@ -172,46 +160,10 @@ __global__ void __launch_bounds__(256) finalize_film_kernel(const float* __restr
   dfilm[o + H] = s2;
 }
 
-// ------------------------------------------------------------------------------------------------ ray set-up (both kernels)
-// identical arithmetic to nerf_render_kernel (nerf.hip; nerf_utils.py:38-121)
-struct Ray {
-  float ox, oy, oz, dx, dy, dz, vx, vy, vz, dnorm, nearv, farv, u, t_end, t_step;
-  int N, has_u;
-  __device__ __forceinline__ float zbase(int k) const {
-    if (k >= N) return farv;
-    const float t = (k < N / 2) ? t_step * (float)k : t_end - t_step * (float)(N - 1 - k);
-    return nearv * (1.f - t) + farv * t;
-  }
-  __device__ __forceinline__ float z(int k) const {
-    const float z0 = zbase(k);
-    return has_u ? z0 + (zbase(k + 1) - z0) * u : z0;
-  }
-};
-
-__device__ __forceinline__ Ray make_ray(const cips3d_nerf_bwd_geom& G, int b, int ray, float t_end, float t_step) {
-  Ray r;
-  const int S = G.img_size;
-  const float focal = G.focals[b];
-  r.nearv = G.near_[b]; r.farv = G.far_[b];
-  const float* cw = G.cam_poses + 12 * b;
-  const int pi = ray / S, pj = ray - pi * S;
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const float dcx = (px - (float)S * 0.5f) / focal;
-  const float dcy = -(py - (float)S * 0.5f) / focal;
-  const float dcz = -1.f;
-  r.dx = (dcx * cw[0] + dcy * cw[1]) + dcz * cw[2];
-  r.dy = (dcx * cw[4] + dcy * cw[5]) + dcz * cw[6];
-  r.dz = (dcx * cw[8] + dcy * cw[9]) + dcz * cw[10];
-  r.ox = cw[3]; r.oy = cw[7]; r.oz = cw[11];
-  float vx = G.static_viewdirs ? dcx : r.dx, vy = G.static_viewdirs ? dcy : r.dy, vz = G.static_viewdirs ? dcz : r.dz;
-  const float n = fmaxf(sqrtf((vx * vx + vy * vy) + vz * vz), 1e-12f);
-  r.vx = vx / n; r.vy = vy / n; r.vz = vz / n;
-  r.dnorm = sqrtf((r.dx * r.dx + r.dy * r.dy) + r.dz * r.dz);
-  r.has_u = G.perturb_u != nullptr;
-  r.u = r.has_u ? G.perturb_u[(int64_t)b * S * S + ray] : 0.f;
-  r.N = G.n_samples;
-  r.t_end = t_end; r.t_step = t_step;
-  return r;
+// ray set-up of both kernels: nerf_geom.h
+__device__ __forceinline__ RayGeom make_ray(const cips3d_nerf_bwd_geom& G, int b, int ray, float t_end, float t_step) {
+  return ray_geom(G.cam_poses, G.focals, G.near_, G.far_, G.perturb_u, G.img_size, G.n_samples, G.static_viewdirs, b, ray, t_end,
+                  t_step);
 }
 
 // stage the FiLM table of view b: s_film[l][0][o] = gamma' (gamma 2^-s for the MFMA layers), s_film[l][1][o] = gamma bias + beta
@@ -334,7 +286,7 @@ __device__ __forceinline__ void stash_layer(const h8 (&Xh)[NT / 2], const h8 (&X
         const f32x4 d4 = *reinterpret_cast<const f32x4*>(dF_ray + o4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float f = STASH_FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
+          const float f = FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
           gdot = fmaf(d4[i], f, gdot);
           chead[0] = fmaf(w0[i], f, chead[0]);
           chead[1] = fmaf(w1[i], f, chead[1]);
@@ -342,7 +294,7 @@ __device__ __forceinline__ void stash_layer(const h8 (&Xh)[NT / 2], const h8 (&X
         }
       } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) res[tt * 4 + i] = STASH_FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
+        for (int i = 0; i < 4; ++i) res[tt * 4 + i] = FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
         if (last) {
           const f32x4 ws4 = *reinterpret_cast<const f32x4*>(s_ws + o4);
 #pragma unroll
@@ -405,11 +357,11 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_stash_kernel(FusedArgs a) 
   const int N = G.n_samples;
   const int64_t Pn = (int64_t)R * N;
   const int ray = g * RAYS + pl;                       // R % 16 == 0: always a valid ray
-  stage_film(P, b, H, D, s_film, tid, STASH_FILM_UNIT);
+  stage_film(P, b, H, D, s_film, tid, FILM_UNIT);
   for (int i = tid; i < 10 * H; i += WAVES * 64) s_tab[i] = a.tables[i];
 
   const float b_sigma = P.b_sigma[0], b_rgb0 = P.b_rgb[0], b_rgb1 = P.b_rgb[1], b_rgb2 = P.b_rgb[2];
-  const Ray ry = make_ray(G, b, ray, a.t_end, a.t_step);
+  const RayGeom ry = make_ray(G, b, ray, a.t_end, a.t_step);
   const float span = ry.farv - ry.nearv;
   const float* dF_ray = a.dFt + ((int64_t)b * R + ray) * H;
 
@@ -453,7 +405,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_stash_kernel(FusedArgs a) 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float pre = fmaf(wz[i], nz, fmaf(wy[i], ny, wx[i] * nx));
-          v8[hf * 4 + i] = STASH_FILM_SIN(fmaf(g4[i], pre, c4[i]));
+          v8[hf * 4 + i] = FILM_SIN(fmaf(g4[i], pre, c4[i]));
         }
         if (D == 1) {
           const f32x4 ws4 = *reinterpret_cast<const f32x4*>(s_ws + o4);
@@ -767,7 +719,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_bwd_kernel(FusedArgs a) {
   stage_film(P, b, H, D, s_film, tid);
   for (int i = tid; i < L * 2 * H; i += WAVES * 64) s_sum[i] = 0.f;
 
-  const Ray ry = make_ray(G, b, ray, a.t_end, a.t_step);
+  const RayGeom ry = make_ray(G, b, ray, a.t_end, a.t_step);
   const float span = ry.farv - ry.nearv;
   const float* dF_ray = a.dFt + ((int64_t)b * Rn + ray) * H;
   const float* tscales = P.packed_t + (int64_t)D * H * H;     // [j][2]
@@ -976,8 +928,7 @@ extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, voi
   a.groups = (int)(R / RAYS);
   a.tasks_per_view = ceil_div(a.groups * P.n_chunks, WAVES) * WAVES;
   a.chunk = ceil_div(G.n_samples, P.n_chunks);
-  a.t_end = (float)(1.0 - 1.0 / (double)G.n_samples);
-  a.t_step = G.n_samples > 1 ? a.t_end / (float)(G.n_samples - 1) : 0.f;
+  nerf_linspace_consts(G.n_samples, a.t_end, a.t_step);
   float* s = P.scratch;
   auto take = [&](int64_t n) { float* r = s; s += align4(n); return r; };
   a.tables = take(10 * H);

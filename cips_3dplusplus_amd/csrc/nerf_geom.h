@@ -1,0 +1,103 @@
+// The per-ray geometry of the NeRF half, stated ONCE (reference: Render.get_rays_in_world / get_z_vals / volume_integration,
+// cips3d/nerf_utils.py:18-121, 264-307): pixel -> camera direction -> world direction, the view direction, |rays_d|, the
+// torch.linspace(0, 1 - 1/N, N) constants, the un-perturbed depth of a sample and its offset-sampled form, the sigmoid and the
+// SDF density.  Every kernel that recomputes a ray instead of reading it takes these expressions from here -- the render kernel
+// (nerf.hip), both backwards (nerf_bwd.hip, nerf_bwd_fused.hip), the SDF gradient (nerf_sdf_grad.hip), the normals
+// (nerf_normals.hip) and the stand-alone Render.* ops (render_ops.hip) -- because they must agree BIT FOR BIT: the fused backward
+// refills the forward's stash, the materialised one recomposites with the forward's delta, the normals weight samples with the
+// render kernel's z, and the stand-alone ops are what the fused kernel does in registers.  fp32, contraction off, the
+// association written out: change an expression here and it changes everywhere at once.
+#pragma once
+#include "common.h"
+
+namespace {
+
+// torch.linspace(0, 1 - 1/N, N): last value and step.  The hot kernels take them as kernel arguments (see NerfArgs, nerf_mlp.h).
+__host__ __device__ __forceinline__ void nerf_linspace_consts(int N, float& t_end, float& t_step) {
+  t_end = (float)(1.0 - 1.0 / (double)N);
+  t_step = N > 1 ? t_end / (float)(N - 1) : 0.f;
+}
+
+__device__ __forceinline__ float nerf_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+// with_sdf density (nerf_utils.py:276-286), and F.softplus of the raw density (:288-297; torch's threshold 20: identity above it)
+__device__ __forceinline__ float nerf_sdf_density(float sdf, float beta) { return nerf_sigmoid(-sdf / beta) / beta; }
+__device__ __forceinline__ float nerf_softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }
+
+__device__ __forceinline__ float nerf_norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
+
+// Sample depths of one view.
+struct NerfDepths {
+  float nearv, farv, t_end, t_step;
+  int N;
+  // un-perturbed depth of sample k (linspace evaluated symmetrically around the midpoint, as torch); k == N gives `far`
+  __device__ __forceinline__ float zbase(int k) const {
+    if (k >= N) return farv;
+    const float t = (k < N / 2) ? t_step * (float)k : t_end - t_step * (float)(N - 1 - k);
+    return nearv * (1.f - t) + farv * t;
+  }
+  // offset sampling (nerf_utils.py:88-96): one uniform u per ray moves every sample the same fraction towards the next (z1)
+  __device__ static __forceinline__ float zoffset(float z0, float z1, float u) { return z0 + (z1 - z0) * u; }
+  // depth of sample k of a ray (a kernel that reads u only when there is one spells this line itself, with the read as zoffset's
+  // last argument)
+  __device__ __forceinline__ float z(int k, bool has_u, float u) const {
+    const float z0 = zbase(k);
+    return has_u ? zoffset(z0, zbase(k + 1), u) : z0;
+  }
+};
+
+// Ray of pixel `ray` = row * S + column of a view with focal length focals[b] and pose cw = cam_poses + 12 b
+// (nerf_utils.py:38-66): direction in the camera frame (dc*) and in the world (d*).  The origin is (cw[3], cw[7], cw[11]).
+struct NerfCamRay {
+  float dcx, dcy, dcz, dx, dy, dz;
+};
+__device__ __forceinline__ NerfCamRay nerf_cam_ray(float focal, const float* cw, int S, int ray) {
+  NerfCamRay c;
+  const int pi = ray / S, pj = ray - pi * S;
+  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
+  c.dcx = (px - (float)S * 0.5f) / focal;
+  c.dcy = -(py - (float)S * 0.5f) / focal;
+  c.dcz = -1.f;
+  c.dx = (c.dcx * cw[0] + c.dcy * cw[1]) + c.dcz * cw[2];
+  c.dy = (c.dcx * cw[4] + c.dcy * cw[5]) + c.dcz * cw[6];
+  c.dz = (c.dcx * cw[8] + c.dcy * cw[9]) + c.dcz * cw[10];
+  return c;
+}
+
+// F.normalize (eps 1e-12) of the camera-frame direction (static_viewdirs) or of the world direction; returns the clamped length
+__device__ __forceinline__ float nerf_viewdir(const NerfCamRay& c, int static_viewdirs, float& vx, float& vy, float& vz) {
+  const float rx = static_viewdirs ? c.dcx : c.dx, ry = static_viewdirs ? c.dcy : c.dy, rz = static_viewdirs ? c.dcz : c.dz;
+  const float vnorm = fmaxf(nerf_norm3(rx, ry, rz), 1e-12f);
+  vx = rx / vnorm; vy = ry / vnorm; vz = rz / vnorm;
+  return vnorm;
+}
+
+// Everything about one camera ray.  Fields a kernel does not read cost nothing once this is inlined.
+struct RayGeom {
+  float ox, oy, oz, dx, dy, dz, dcx, dcy, dcz, vx, vy, vz, vnorm, dnorm, nearv, farv, u, t_end, t_step;
+  int N, has_u;
+  __device__ __forceinline__ NerfDepths depths() const { return NerfDepths{nearv, farv, t_end, t_step, N}; }
+  __device__ __forceinline__ float zbase(int k) const { return depths().zbase(k); }
+  __device__ __forceinline__ float z(int k) const { return depths().z(k, has_u, u); }
+};
+
+__device__ __forceinline__ RayGeom ray_geom(const float* cam_poses, const float* focals, const float* near_, const float* far_,
+                                            const float* perturb_u, int S, int N, int static_viewdirs, int b, int ray,
+                                            float t_end, float t_step) {
+  RayGeom r;
+  const float focal = focals[b];
+  r.nearv = near_[b]; r.farv = far_[b];
+  const float* cw = cam_poses + 12 * b;
+  const NerfCamRay c = nerf_cam_ray(focal, cw, S, ray);
+  r.dcx = c.dcx; r.dcy = c.dcy; r.dcz = c.dcz;
+  r.dx = c.dx; r.dy = c.dy; r.dz = c.dz;
+  r.ox = cw[3]; r.oy = cw[7]; r.oz = cw[11];
+  r.vnorm = nerf_viewdir(c, static_viewdirs, r.vx, r.vy, r.vz);
+  r.dnorm = nerf_norm3(r.dx, r.dy, r.dz);
+  r.has_u = perturb_u != nullptr;
+  r.u = r.has_u ? perturb_u[(int64_t)b * S * S + ray] : 0.f;
+  r.N = N;
+  r.t_end = t_end; r.t_step = t_step;
+  return r;
+}
+
+}  // namespace

@@ -3,6 +3,7 @@
 // work decomposition and the arithmetic.
 #pragma once
 #include "common.h"
+#include "nerf_geom.h"
 
 // CIPS3D_FILM_REVOLUTIONS: the staged FiLM table carries gamma' / 2 pi and c / 2 pi, so that the epilogue's FMA yields the
 // sine argument in revolutions and v_sin_f32(fract(.)) takes it as it is -- one multiplication less per activation.  The extra
@@ -34,7 +35,7 @@ struct NerfArgs {
   int chunk;           // samples per chunk (uniform trip count)
   int fuse_finish;     // the workgroup's eight chunk waves combine their partials in LDS and write the final maps
   int pad_;             // (keeps the 8-byte alignment of what follows explicit)
-  float t_end, t_step; // torch.linspace(0, 1 - 1/N, N): last value and step, computed on the host (kernel arguments are
+  float t_end, t_step; // nerf_linspace_consts (nerf_geom.h), computed on the host (kernel arguments are
                        // re-readable scalars; computed in the kernel they ended up as spilled VGPR copies)
 };
 
@@ -75,8 +76,6 @@ __device__ __forceinline__ void stage_slab(const float* __restrict__ gsrc, float
     if (PIECES % NW == 0 || piece < PIECES) stage_piece(gsrc, lds_dst, piece, lane);
   }
 }
-
-__device__ __forceinline__ float sigmoidf_acc(float v) { return 1.f / (1.f + expf(-v)); }
 
 // Per-wave streaming state of the weight ring.
 struct Ring {

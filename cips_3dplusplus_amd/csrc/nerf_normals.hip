@@ -1,7 +1,7 @@
 // Composited surface normals and the Phong-shaded geometry frame of a rendered view (cips3d_nerf_normals).
 //
 //   normal_raw[b,:,r] = sum_i w_i grad[b,r,i,:]     w = the compositing weights of nerf_utils.py:276-286 (the render
-//                                                   kernel's arithmetic: csrc/nerf.hip), grad = d sdf / d pts of
+//                                                   kernel's rays and depths: csrc/nerf_geom.h), grad = d sdf / d pts of
 //                                                   csrc/nerf_sdf_grad.hip
 //   normal = normal_raw / max(|normal_raw|, 1e-12)  (F.normalize)
 //   shade  = pytorch3d's Phong for a white vertex colour at p = xyz[b,:,r], seen from `eye`, lit from `light`
@@ -13,6 +13,7 @@
 // cancel against the 1e10 last interval.  The weighted sum is a butterfly over the segment.  Every ray's operation order is
 // fixed by N alone: no atomics, bit-reproducible, independent of the grid.  Accurate expf / powf throughout.
 #include "common.h"
+#include "nerf_geom.h"
 
 namespace {
 
@@ -22,10 +23,8 @@ struct NormalsArgs {
   cips3d_normals_params p;
   int64_t rays;              // B * R
   int R;
-  float t_end, t_step;       // torch.linspace(0, 1 - 1/N, N) as csrc/nerf.hip evaluates it
+  float t_end, t_step;       // nerf_linspace_consts (nerf_geom.h)
 };
-
-__device__ __forceinline__ float sigmoid_acc(float v) { return 1.f / (1.f + expf(-v)); }
 
 // F.normalize of a 3-vector (eps 1e-12)
 __device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
@@ -54,31 +53,18 @@ __global__ void __launch_bounds__(NRM_WAVES * 64) nerf_normals_kernel(NormalsArg
     if constexpr (XG) {
       dx = P.x_rays_d[brc * 3]; dy = P.x_rays_d[brc * 3 + 1]; dz = P.x_rays_d[brc * 3 + 2];
     } else {
-      // the render kernel's ray direction (nerf_utils.py:38-66)
-      const float focal = P.focals[b];
-      const float* cw = P.cam_poses + 12 * b;
-      const int pi = ray / S, pj = ray - pi * S;
-      const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-      const float dcx = (px - (float)S * 0.5f) / focal;
-      const float dcy = -(py - (float)S * 0.5f) / focal;
-      const float dcz = -1.f;
-      dx = (dcx * cw[0] + dcy * cw[1]) + dcz * cw[2];
-      dy = (dcx * cw[4] + dcy * cw[5]) + dcz * cw[6];
-      dz = (dcx * cw[8] + dcy * cw[9]) + dcz * cw[10];
+      // the render kernel's ray direction (nerf_geom.h)
+      const NerfCamRay cam = nerf_cam_ray(P.focals[b], P.cam_poses + 12 * b, S, ray);
+      dx = cam.dx; dy = cam.dy; dz = cam.dz;
       if (P.perturb_u) u = P.perturb_u[brc];
     }
-    const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);
-    auto zbase = [&](int k) -> float {      // un-perturbed depth of sample k; k == N gives `far`
-      if (k >= N) return farv;
-      const float t = (k < N / 2) ? a.t_step * (float)k : a.t_end - a.t_step * (float)(N - 1 - k);
-      return nearv * (1.f - t) + farv * t;
-    };
+    const float dnorm = nerf_norm3(dx, dy, dz);
+    const NerfDepths zs{nearv, farv, a.t_end, a.t_step, N};
     auto zsample = [&](int k) -> float {
       if constexpr (XG) {
         return P.x_z_vals[brc * N + k];
       } else {
-        const float z0 = zbase(k);
-        return P.perturb_u ? z0 + (zbase(k + 1) - z0) * u : z0;
+        return zs.z(k, P.perturb_u != nullptr, u);
       }
     };
 
@@ -93,7 +79,7 @@ __global__ void __launch_bounds__(NRM_WAVES * 64) nerf_normals_kernel(NormalsArg
         const float* gp = P.grad + pt * 3;
         gx = gp[0]; gy = gp[1]; gz = gp[2];
         const float delta = (sk < N - 1 ? zsample(sk + 1) - zsample(sk) : 1e10f) * dnorm;
-        const float sigma = sigmoid_acc(-sdf / beta) / beta;
+        const float sigma = nerf_sdf_density(sdf, beta);
         alpha = 1.f - expf(-sigma * delta);
         f = (1.f - alpha) + 1e-10f;
       }
@@ -171,8 +157,7 @@ extern "C" int cips3d_nerf_normals(const cips3d_normals_params* p, void* stream)
   a.rays = (int64_t)P.B * R;
   if (R > INT32_MAX || a.rays > INT32_MAX) return CIPS3D_E_UNSUPP;
   a.R = (int)R;
-  a.t_end = (float)(1.0 - 1.0 / (double)P.n_samples);
-  a.t_step = P.n_samples > 1 ? a.t_end / (float)(P.n_samples - 1) : 0.f;
+  nerf_linspace_consts(P.n_samples, a.t_end, a.t_step);
   hipStream_t st = as_stream(stream);
   const int N = P.n_samples;
   if (N <= 1) return launch_normals<1>(a, st);

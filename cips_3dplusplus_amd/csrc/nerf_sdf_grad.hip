@@ -40,7 +40,7 @@ struct SdfGradArgs {
   int wgs_per_view;
   int iters;            // steps per workgroup (uniform over the grid)
   int pad_;
-  float t_end, t_step;  // torch.linspace(0, 1 - 1/N, N), as in NerfArgs
+  float t_end, t_step;  // nerf_linspace_consts (nerf_geom.h)
 };
 
 // sin(x) on the value lanes (bit for bit sin_accurate), cos(x) on the tangent lanes: the same two-constant Cody-Waite reduction
@@ -218,12 +218,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_sdf_grad_kernel(SdfGradArg
 
   const float nearv = P.near_[b], farv = P.far_[b];
   const float span = cips3d_uniform(farv - nearv);
-  const float t_end = a.t_end, t_step = a.t_step;
-  auto zbase = [&](int k) -> float {      // nerf.hip: un-perturbed depth of sample k; k == N gives `far`
-    if (k >= N) return farv;
-    const float t = (k < N / 2) ? t_step * (float)k : t_end - t_step * (float)(N - 1 - k);
-    return nearv * (1.f - t) + farv * t;
-  };
+  const NerfDepths zs{nearv, farv, a.t_end, a.t_step, N};
 
   Ring ring;
   ring.packed = P.packed32;
@@ -246,21 +241,14 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_sdf_grad_kernel(SdfGradArg
       const float* pp = P.x_pts + ((int64_t)b * a.points + pt) * 3;
       ptx = pp[0]; pty = pp[1]; ptz = pp[2];
     } else {
-      // nerf_utils.py:38-66 and the offset sampling, in the render kernel's arithmetic
+      // the render kernel's ray and offset sampling (nerf_geom.h)
       const int ray = pt / N, sk = pt - ray * N;
       const float focal = P.focals[b];
       const float* cw = P.cam_poses + 12 * b;
-      const int pi = ray / S, pj = ray - pi * S;
-      const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-      const float dcx = (px - (float)S * 0.5f) / focal;
-      const float dcy = -(py - (float)S * 0.5f) / focal;
-      const float dcz = -1.f;
-      const float dx = (dcx * cw[0] + dcy * cw[1]) + dcz * cw[2];
-      const float dy = (dcx * cw[4] + dcy * cw[5]) + dcz * cw[6];
-      const float dz = (dcx * cw[8] + dcy * cw[9]) + dcz * cw[10];
-      const float z0 = zbase(sk);
-      const float z = P.perturb_u ? z0 + (zbase(sk + 1) - z0) * P.perturb_u[(int64_t)b * R + ray] : z0;
-      ptx = cw[3] + dx * z; pty = cw[7] + dy * z; ptz = cw[11] + dz * z;
+      const NerfCamRay cam = nerf_cam_ray(focal, cw, S, ray);
+      const float z0 = zs.zbase(sk);
+      const float z = P.perturb_u ? zs.zoffset(z0, zs.zbase(sk + 1), P.perturb_u[(int64_t)b * R + ray]) : z0;
+      ptx = cw[3] + cam.dx * z; pty = cw[7] + cam.dy * z; ptz = cw[11] + cam.dz * z;
     }
     const float nx = ptx * 2.f / span, ny = pty * 2.f / span, nz = ptz * 2.f / span;
     const float dn = 2.f / span;                          // d p_n / d p
@@ -385,7 +373,6 @@ extern "C" int cips3d_nerf_sdf_grad(const cips3d_nerf_params* p, float* grad, vo
   a.wgs_per_view = (int)ceil_div<int64_t>(steps, a.iters);
   if ((int64_t)P.B * a.wgs_per_view > 0x7fffffff) return CIPS3D_E_UNSUPP;
   a.pad_ = 0;
-  a.t_end = (float)(1.0 - 1.0 / (double)P.n_samples);
-  a.t_step = P.n_samples > 1 ? a.t_end / (float)(P.n_samples - 1) : 0.f;
+  nerf_linspace_consts(P.n_samples, a.t_end, a.t_step);
   return launch_sdf_grad<16, 4>(a, as_stream(stream));
 }

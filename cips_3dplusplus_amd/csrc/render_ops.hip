@@ -8,10 +8,9 @@
 // (101 MB per view at C=256, N=24) with one wave per ray: lanes cover 4 channels each (16-byte loads, 1 KB contiguous
 // per sample) and the N compositing weights are computed once per ray and kept in LDS.
 #include "common.h"
+#include "nerf_geom.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf_exact(float x) { return 1.f / (1.f + expf(-x)); }
 
 // thread per ray; outputs [B,S,S,3] (reference layout, ray-major, xyz fastest)
 __global__ void __launch_bounds__(256) rays_kernel(const float* __restrict__ cam_poses, const float* __restrict__ focals,
@@ -23,17 +22,11 @@ __global__ void __launch_bounds__(256) rays_kernel(const float* __restrict__ cam
   const int b = (int)(i / R), ray = (int)(i % R);
   const float focal = focals[b];
   const float* cw = cam_poses + 12 * b;
-  const int pi = ray / S, pj = ray - pi * S;
-  const float px = (float)pj + 0.5f, py = (float)pi + 0.5f;
-  const float dcx = (px - (float)S * 0.5f) / focal, dcy = -(py - (float)S * 0.5f) / focal, dcz = -1.f;
-  const float dx = (dcx * cw[0] + dcy * cw[1]) + dcz * cw[2];
-  const float dy = (dcx * cw[4] + dcy * cw[5]) + dcz * cw[6];
-  const float dz = (dcx * cw[8] + dcy * cw[9]) + dcz * cw[10];
-  float vx = static_viewdirs ? dcx : dx, vy = static_viewdirs ? dcy : dy, vz = static_viewdirs ? dcz : dz;
-  const float n = fmaxf(sqrtf((vx * vx + vy * vy) + vz * vz), 1e-12f);
-  vx /= n; vy /= n; vz /= n;
+  const NerfCamRay cam = nerf_cam_ray(focal, cw, S, ray);
+  float vx, vy, vz;
+  nerf_viewdir(cam, static_viewdirs, vx, vy, vz);
   float* o = rays_o + i * 3; o[0] = cw[3]; o[1] = cw[7]; o[2] = cw[11];
-  float* d = rays_d + i * 3; d[0] = dx; d[1] = dy; d[2] = dz;
+  float* d = rays_d + i * 3; d[0] = cam.dx; d[1] = cam.dy; d[2] = cam.dz;
   float* v = viewdirs + i * 3; v[0] = vx; v[1] = vy; v[2] = vz;
 }
 
@@ -47,16 +40,11 @@ __global__ void __launch_bounds__(256) z_vals_kernel(const float* __restrict__ n
   const int64_t br = i / N;
   const int b = (int)(br / R);
   const float nearv = near_[b], farv = far_[b];
-  // torch.linspace(0, 1 - 1/N, N): symmetric evaluation around the midpoint (same as nerf.hip)
-  const float t_end = (float)(1.0 - 1.0 / (double)N);
-  const float t_step = N > 1 ? t_end / (float)(N - 1) : 0.f;
-  auto zbase = [&](int kk) -> float {
-    if (kk >= N) return farv;
-    const float t = (kk < N / 2) ? t_step * (float)kk : t_end - t_step * (float)(N - 1 - kk);
-    return nearv * (1.f - t) + farv * t;
-  };
-  const float z0 = zbase(k);
-  z[i] = u ? z0 + (zbase(k + 1) - z0) * u[br] : z0;
+  float t_end, t_step;
+  nerf_linspace_consts(N, t_end, t_step);
+  const NerfDepths zs{nearv, farv, t_end, t_step, N};
+  const float z0 = zs.zbase(k);
+  z[i] = u ? zs.zoffset(z0, zs.zbase(k + 1), u[br]) : z0;
 }
 
 // the classic NeRF stratified branch (offset_sampling = False, nerf_utils.py:98-117): t = linspace(0, 1, N) (symmetric
@@ -114,15 +102,13 @@ __global__ void __launch_bounds__(256) integrate_kernel(const float* __restrict_
   if (r >= BR) return;
   const bool raw_density = flags & CIPS3D_VI_RAW_DENSITY;
   const float beta = raw_density ? 1.f : sigmoid_beta[0];
-  const float dnorm = sqrtf((rays_d[r * 3] * rays_d[r * 3] + rays_d[r * 3 + 1] * rays_d[r * 3 + 1]) +
-                            rays_d[r * 3 + 2] * rays_d[r * 3 + 2]);
+  const float dnorm = nerf_norm3(rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]);
   // alpha_k for this lane's samples, then the transmittance scan by lane 0 (N is small: 24 .. 128)
   for (int k = lane; k < N; k += 64) {
     const float delta = (k < N - 1 ? z[r * N + k + 1] - z[r * N + k] : 1e10f) * dnorm;
     const float v = sdf[r * N + k];
-    // with_sdf: density = sigmoid(-sdf / beta) / beta (nerf_utils.py:276-286); else F.softplus of the raw output (:288-297;
-    // torch's threshold 20: identity above it)
-    const float sigma = raw_density ? (v > 20.f ? v : log1pf(expf(v))) : sigmoidf_exact(-v / beta) / beta;
+    // with_sdf: the SDF density; else F.softplus of the raw output (nerf_geom.h)
+    const float sigma = raw_density ? nerf_softplus(v) : nerf_sdf_density(v, beta);
     s_w[wv][k] = 1.f - expf(-sigma * delta);
   }
   __builtin_amdgcn_wave_barrier();
@@ -146,7 +132,7 @@ __global__ void __launch_bounds__(256) integrate_kernel(const float* __restrict_
     if (lane < 3) {
       for (int k = 0; k < N; ++k) {
         const float w = s_w[wv][k];
-        cr = fmaf(w, sigmoidf_exact(rgb[(r * N + k) * 3 + lane]), cr);
+        cr = fmaf(w, nerf_sigmoid(rgb[(r * N + k) * 3 + lane]), cr);
         cx = fmaf(w, pts[(r * N + k) * 3 + lane], cx);
       }
       rgb_map[r * 3 + lane] = -1.f + 2.f * cr;

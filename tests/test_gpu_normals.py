@@ -199,6 +199,40 @@ def test_normal_map_camera_form_against_fp64_oracle(D, S, N, perturb):
         assert torch.equal(out[k], again[k]) and torch.equal(out[k], twice[k]) and torch.equal(out[k], other[k]), k
 
 
+_GEOM_CAM = []
+
+
+@pytest.mark.parametrize("perturb", [False, True])
+@pytest.mark.parametrize("N", [1, 5, 24])
+def test_camera_form_equals_explicit_form_on_the_stand_alone_geometry(N, perturb):
+    """The camera form builds its rays and depths in the kernel; the explicit form reads what hip.rays_in_world and hip.z_vals
+    wrote.  Both evaluate the expressions of csrc/nerf_geom.h in fp32 with contraction off (division and square root correctly
+    rounded), so the two forms must give the same bits, not merely close ones."""
+    from cips_3dplusplus_amd.camera import Camera
+    B, S = 2, 8
+    R = S * S
+    if not _GEOM_CAM:
+        _GEOM_CAM.append(Camera.generate_camera_params(S, DEV, locations=torch.tensor([[0.3, 0.1], [-0.2, 0.05]], device=DEV))[:4])
+    extr, focal, near, far = _GEOM_CAM[0]
+    beta = cu(SG.synth_renderer_sd(2)["renderer.sigmoid_beta"].reshape(1).float())
+    sdf = cu(weights.det_normal("nrmgeom.sdf", (B, R, N), 1.0, N)) * beta
+    grad = cu(weights.det_normal("nrmgeom.grad", (B, R, N, 3), 1.0, N))
+    u = cu(weights.det_unit_uniform("nrmgeom.u", (B, R), N)) if perturb else None
+    common = dict(sdf=sdf, grad=grad, sigmoid_beta=beta, B=B, n_samples=N)
+    cam = hip.nerf_normals(img_size=S, cam_poses=extr.float().contiguous(), focals=focal.float().reshape(B).contiguous(),
+                           near_=near.float().reshape(B).contiguous(), far_=far.float().reshape(B).contiguous(), perturb_u=u,
+                           **common)
+    rays_d = hip.rays_in_world(extr, focal, S)[1].reshape(B, R, 3).contiguous()
+    z = hip.z_vals(near, far, B, R, N, u)
+    exp = hip.nerf_normals(x_rays_d=rays_d, x_z_vals=z, n_rays=R, **common)
+    torch.cuda.synchronize()
+    for k in ("normal_raw", "normal"):
+        d = float((cam[k] - exp[k]).abs().max())
+        print(f"N={N} perturb={perturb} {k}: max |camera - explicit| {d:.3e}, max |{k}| {float(cam[k].abs().max()):.3e}")
+        assert torch.isfinite(cam[k]).all() and float(cam[k].abs().max()) > 0
+        assert torch.equal(cam[k], exp[k]), f"{k}: camera and explicit forms differ by {d:.3e}"
+
+
 # ------------------------------------------------------------------------------------------------ 4. shading in isolation
 def phong64(n_raw, xyz, eye, light, ka, kd, ks, s):
     """n_raw (B,R,3), xyz (B,R,3), eye / light (B,3), all fp64 -> shade (B,R)."""
