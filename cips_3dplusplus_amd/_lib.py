@@ -340,10 +340,16 @@ _SIGS = {
     "cips3d_lpips": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_lpips_split": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_sizeof_lpips_io": (c_int, []),
+    "cips3d_ssim_loss_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
+    "cips3d_ssim_loss_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int, c_int]),
+    "cips3d_ssim_loss": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, C.c_float, C.c_float, C.c_void_p, c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_ssim_loss_bwd": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 39           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 40           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

@@ -481,6 +481,27 @@ class MaskBlendFn(Function):
         return hip.mask_blend(_c(g), mask, backward=True), None
 
 
+class SsimLossFn(Function):
+    """weight x mean_i (1 - ssim_i), ssim the Gaussian-window SSIM of image a against target b (cips3d_ssim_loss / _bwd,
+    csrc/ssim_loss.hip): two launches forward, one backward.  Differentiable with respect to a; b is a target.  The upstream
+    gradient stays on the device.  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, data_range):
+        a, b = _c(a.detach()), _c(b.detach())
+        need = bool(ctx.needs_input_grad[0])
+        loss, _, ws, _ = hip.ssim_loss(a, b, weight, data_range, need_grad=need)
+        if need:
+            ctx.save_for_backward(a, b, ws)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, ws = ctx.saved_tensors
+        return hip.ssim_loss_bwd(a, b, ctx.weight, ws, g.contiguous().float()), None, None, None
+
+
 class CameraFn(Function):
     """Camera.generate_camera_params for given `locations` (azim, elev), differentiable w.r.t. them."""
 

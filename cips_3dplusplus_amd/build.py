@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(PKG, "libcips3d_hip.so")
 ARCH = "gfx950"
-SOURCES = ["bias_act.hip", "upfirdn2d.hip", "linear.hip", "camera.hip", "nerf.hip", "nerf_sdf_grad.hip", "nerf_normals.hip", "decoder.hip", "chain.hip", "conv3x3.hip", "forward.hip", "backward.hip", "decoder_grad.hip", "nerf_bwd.hip", "nerf_bwd_fused.hip", "render_ops.hip", "rng.hip", "optim.hip", "mesh.hip", "mesh_raster.hip", "vgg.hip", "vgg_split.hip", "inversion_loss.hip", "metrics.hip", "lpips.hip"]
+SOURCES = ["bias_act.hip", "upfirdn2d.hip", "linear.hip", "camera.hip", "nerf.hip", "nerf_sdf_grad.hip", "nerf_normals.hip", "decoder.hip", "chain.hip", "conv3x3.hip", "forward.hip", "backward.hip", "decoder_grad.hip", "nerf_bwd.hip", "nerf_bwd_fused.hip", "render_ops.hip", "rng.hip", "optim.hip", "mesh.hip", "mesh_raster.hip", "vgg.hip", "vgg_split.hip", "inversion_loss.hip", "metrics.hip", "lpips.hip", "ssim_loss.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function", "-fno-gpu-rdc", "-fgpu-flush-denormals-to-zero" if False else ""]
 FLAGS = [f for f in FLAGS if f] + os.environ.get("CIPS3D_HIPCC_FLAGS", "").split()
@@ -62,9 +62,10 @@ def up_to_date():
 # the bf16 chain kernel (named and reproduced by hand in profiles/r05_slp_fold_cause.md); the shipped fold spells its FMAs in inline
 # asm as well, and tests/test_host.py checks the kernel's assembly for the form
 # metrics.hip: its fp32 window arithmetic is promised bit-identical run to run; SLP packed it into v_pk_mul_f32 / v_pk_add_f32 too, so
-# it is built without SLP vectorisation as well; lpips.hip promises the same of its per-pixel fp32 sums
+# it is built without SLP vectorisation as well; lpips.hip promises the same of its per-pixel fp32 sums, ssim_loss.hip of its windows
 FILE_FLAGS = {"chain.hip": [] if os.environ.get("CIPS3D_CHAIN_SLP") == "1" else ["-fno-slp-vectorize"],
-              "metrics.hip": ["-fno-slp-vectorize"], "lpips.hip": ["-fno-slp-vectorize"]}
+              "metrics.hip": ["-fno-slp-vectorize"], "lpips.hip": ["-fno-slp-vectorize"],
+              "ssim_loss.hip": ["-fno-slp-vectorize"]}
 
 
 def _compile(src, keep_temps):

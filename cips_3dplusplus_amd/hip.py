@@ -1569,6 +1569,60 @@ def mask_blend(x, mask, backward=False):
     return out
 
 
+# ------------------------------------------------------------------------------- Gaussian-window SSIM loss (csrc/ssim_loss.hip)
+SSIM_WIN = 11                   # taps of the window; a side below it has no window
+
+
+def ssim_loss_tile():
+    """(tile_h, tile_w, threads) of cips3d_ssim_loss: the sides of a workgroup's tile of window origins and its thread count."""
+    th, tw = C.c_int(0), C.c_int(0)
+    threads = _lib.load().cips3d_ssim_loss_tile(C.byref(th), C.byref(tw))
+    return th.value, tw.value, threads
+
+
+def ssim_loss_supported(a, b):
+    """True when cips3d_ssim_loss takes the pair: fp32 HIP tensors [B,C,H,W] of equal shape on one device, C in {1, 3}, both
+    sides >= 11."""
+    return (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda and a.device == b.device
+            and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 4 and a.shape == b.shape
+            and a.shape[0] >= 1 and a.shape[1] in (1, 3) and a.shape[2] >= SSIM_WIN and a.shape[3] >= SSIM_WIN)
+
+
+def ssim_loss_workspace_bytes(B, Cc, H, W, need_grad):
+    n = int(_lib.load().cips3d_ssim_loss_workspace_bytes(B, Cc, H, W, int(bool(need_grad))))
+    if n < 0:
+        raise RuntimeError(f"cips3d_ssim_loss_workspace_bytes({B}, {Cc}, {H}, {W}) failed ({n})")
+    return n
+
+
+def ssim_loss(a, b, weight=1.0, data_range=2.0, need_grad=False, return_map=False):
+    """weight x mean_i (1 - ssim_i) of the Gaussian-window SSIM of a against b (cips3d_ssim_loss: two launches, nothing read back)
+    -> (loss: fp32 device scalar, ssim: float64 [B] on the device, workspace, map or None).  `need_grad`: the workspace also
+    holds the three derivative maps ssim_loss_bwd reads.  `return_map`: S per window, [B,C,H-10,W-10]."""
+    lib = _lib.load()
+    if not ssim_loss_supported(a, b):
+        raise RuntimeError("cips3d_ssim_loss: fp32 HIP tensors [B,C,H,W] of equal shape, C in {1, 3}, sides >= 11 (hip.ssim_loss_supported)")
+    B, Cc, H, W = a.shape
+    ws = torch.empty((ssim_loss_workspace_bytes(B, Cc, H, W, need_grad) + 3) // 4, device=a.device)
+    ssim = torch.empty(B, dtype=torch.float64, device=a.device)
+    loss = torch.empty((), device=a.device)
+    smap = torch.empty(B, Cc, H - SSIM_WIN + 1, W - SSIM_WIN + 1, device=a.device) if return_map else None
+    check(lib.cips3d_ssim_loss(dev_ptr(a, "a"), dev_ptr(b, "b"), B, Cc, H, W, float(weight), float(data_range), ws.data_ptr(),
+                               int(bool(need_grad)), dev_ptr(smap, "map", True), ssim.data_ptr(), loss.data_ptr(), stream_ptr()),
+          "cips3d_ssim_loss")
+    return loss, ssim, ws, smap
+
+
+def ssim_loss_bwd(a, b, weight, ws, gloss):
+    """gloss x d loss / d a of ssim_loss(a, b, weight, need_grad=True) with its workspace `ws`; gloss a device scalar.  One launch."""
+    lib = _lib.load()
+    B, Cc, H, W = a.shape
+    da = torch.empty_like(a)
+    check(lib.cips3d_ssim_loss_bwd(dev_ptr(a, "a"), dev_ptr(b, "b"), B, Cc, H, W, float(weight), dev_ptr(ws, "workspace"),
+                                   dev_ptr(gloss, "gloss"), da.data_ptr(), stream_ptr()), "cips3d_ssim_loss_bwd")
+    return da
+
+
 # ---------------------------------------------------------------------------------------------- geometry export (csrc/mesh.hip)
 def align_volume(volume, near=0.88, far=1.12, out=None):
     """cips3d_align_volume: volume [B,h,w,d] fp32 -> the frustum-aligned volume of the same shape."""

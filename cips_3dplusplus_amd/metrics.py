@@ -10,7 +10,11 @@ The reference's `project_wplus` logs tl2's `sk_psnr` / `sk_ssim` of the projecte
 * PSNR = 10 log10(R^2 C H W / SSE) per image, SSE the integer sum of squared differences (SSE = 0: +inf);
 * SSIM: win_size 7, uniform window, K1 = 0.01, K2 = 0.03, sample covariance (n - 1 = 48), the mean over the C (H - 6) (W - 6)
   windows that lie wholly inside the image (scikit-image crops the 3-pixel border, so its padding never matters); H or
-  W < 7 raises ValueError, as scikit-image does.  The Gaussian-window and multi-scale variants are not built.
+  W < 7 raises ValueError, as scikit-image does.  The multi-scale variant is not built.
+
+`ssim_gaussian` is the other published form (Wang et al. 2004; scikit-image's `gaussian_weights=True, sigma=1.5,
+use_sample_covariance=False`) on CONTINUOUS fp32 images -- nothing quantised, nothing clamped, 11-tap Gaussian window, data range
+2 for images in [-1, 1] -- from csrc/ssim_loss.hip, whose other face is the differentiable loss `projector.ssim_loss`.
 
 SSE is exact; SSIM is within (12 + d) 2^-24 of the float64 evaluation (d = 16, the depth of a tile's fp32 sum), and both are
 bit-identical run to run and independent of the batch (tests/test_gpu_image_metrics.py).
@@ -183,3 +187,79 @@ class MetricsLog:
         _, psnr_, ssim_ = _read(self._record, self.target[0].numel())
         idx = torch.tensor(rows)
         return {"steps": [self.steps[r] for r in rows], "psnr": psnr_[idx], "ssim": ssim_[idx]}
+
+
+# ------------------------------------------------------------------------------------ Gaussian-window SSIM (csrc/ssim_loss.hip)
+GAUSS_WIN, GAUSS_SIGMA = 11, 1.5
+
+
+def gaussian_window(dtype=torch.float64, device="cpu"):
+    """The 11 taps g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), normalised to sum 1 (computed in float64)."""
+    d = torch.arange(GAUSS_WIN, dtype=torch.float64) - GAUSS_WIN // 2
+    g = torch.exp(-(d * d) / (2.0 * GAUSS_SIGMA ** 2))
+    return (g / g.sum()).to(device=device, dtype=dtype)
+
+
+def _check_pair_gaussian(a, b, data_range=2.0):
+    """The argument errors of the Gaussian-window SSIM, raised before the library is touched. -> (a, b) as [B, C, H, W]."""
+    for x, name in ((a, "a"), (b, "b")):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(x).__name__}")
+        if not x.is_floating_point():
+            raise ValueError(f"{name} must be a floating-point image, got {x.dtype}")
+    if a.dim() == 3:
+        a = a.unsqueeze(0)
+    if b.dim() == 3:
+        b = b.unsqueeze(0)
+    if a.dim() != 4:
+        raise ValueError(f"a must be [B, C, H, W] or [C, H, W], got {tuple(a.shape)}")
+    if a.shape != b.shape:
+        raise ValueError(f"the images differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+    B, Cc, H, W = a.shape
+    if B < 1:
+        raise ValueError("an empty batch has no metrics")
+    if Cc not in (1, 3):
+        raise ValueError(f"images have 1 or 3 channels, got {Cc}")
+    if H < GAUSS_WIN or W < GAUSS_WIN:
+        raise ValueError(f"win_size {GAUSS_WIN} exceeds the image extent {H} x {W}")
+    if a.device != b.device:
+        raise ValueError(f"the images are on different devices: {a.device} and {b.device}")
+    if not data_range > 0:
+        raise ValueError(f"data_range must be positive, got {data_range}")
+    return a, b
+
+
+def _ssim_gaussian_torch(a, b, data_range=2.0):
+    """The definition as a plain torch expression (F.conv2d, groups = C), on any device and in a's dtype (fp64 included), with
+    autograd: -> (ssim [B], S [B, C, H - 10, W - 10]).  The fallback of `ssim_gaussian` / `projector.ssim_loss` and the A/B
+    partner of the kernels."""
+    import torch.nn.functional as F
+    Cc = a.shape[1]
+    b = b.to(a.dtype)
+    g = gaussian_window(a.dtype, a.device)
+    wr, wc = g.reshape(1, 1, 1, -1).repeat(Cc, 1, 1, 1), g.reshape(1, 1, -1, 1).repeat(Cc, 1, 1, 1)
+
+    def E(x):
+        return F.conv2d(F.conv2d(x, wr, groups=Cc), wc, groups=Cc)
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    mx, my = E(a), E(b)
+    vx, vy, vxy = E(a * a) - mx * mx, E(b * b) - my * my, E(a * b) - mx * my
+    S = ((2 * mx * my + c1) * (2 * vxy + c2)) / ((mx * mx + my * my + c1) * (vx + vy + c2))
+    return S.mean(dim=(1, 2, 3)), S
+
+
+def ssim_gaussian(a, b, data_range=2.0, return_map=False):
+    """Gaussian-window SSIM of a against b, image by image -> float64 [B] on the CPU (one device-to-host read); with
+    `return_map` also S per window, [B, C, H - 10, W - 10] on the images' device.  a, b: [B, C, H, W] or [C, H, W], C in {1, 3},
+    continuous values (no quantisation, no clamp).  fp32 HIP tensors run csrc/ssim_loss.hip; anything else is the torch
+    expression."""
+    a, b = _check_pair_gaussian(a, b, data_range)
+    from . import hip
+    if hip.ssim_loss_supported(a, b):
+        _, ssim_, _, smap = hip.ssim_loss(a.detach().contiguous(), b.detach().contiguous(), 1.0, data_range, return_map=return_map)
+        ssim_ = ssim_.cpu()
+    else:
+        with torch.no_grad():
+            ssim_, smap = _ssim_gaussian_torch(a, b, data_range)
+        ssim_ = ssim_.double().cpu()
+    return (ssim_, smap) if return_map else ssim_

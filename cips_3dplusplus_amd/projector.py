@@ -14,7 +14,8 @@ features of the image batch and of the 64^2 thumbnail against fixed target featu
 benchmarks.  The other terms of the step loss (:1164-1200) are knobs of `project_wplus` with the reference's names and off
 defaults: `mask_background` (`mask_blend`, :1164-1167), `mse_weight` + `target_images` (:1176-1181) and `optim_noise_bufs` +
 `regularize_noise_weight` (`noise_regulariser`, :1183-1195); on the GPU the blend and the regulariser are one autograd node
-each (csrc/inversion_loss.hip).  `metrics_every` > 0 logs the PSNR and SSIM the reference charts (:1125-1139) and returns those of
+each (csrc/inversion_loss.hip).  `ssim_weight` + `target_images` is not the reference's: ssim_weight x mean (1 - SSIM), the
+Gaussian-window SSIM on continuous values as one more autograd node (`ssim_loss`, csrc/ssim_loss.hip).  `metrics_every` > 0 logs the PSNR and SSIM the reference charts (:1125-1139) and returns those of
 the final re-render (:1229-1242, 1266-1279), computed on the device (metrics.MetricsLog, csrc/metrics.hip) and read once after the
 loop.  What is NOT here: `use_stat_loss` / `vgg16_relu`; LPIPS; Streamlit charts and videos.
 
@@ -148,6 +149,25 @@ def _weighted_mse(rgb, target, weight):
     return weight * torch.nn.functional.mse_loss(rgb, target)
 
 
+FUSED_SSIM = os.environ.get("CIPS3D_FUSED_SSIM", "1") != "0"      # 0: the torch expression (A/B knob)
+
+
+def ssim_loss(rgb, target, weight, data_range=2.0):
+    """weight x mean_i (1 - ssim_i) with ssim the Gaussian-window SSIM of metrics.ssim_gaussian (Wang et al. 2004: 11 taps, sigma
+    1.5, continuous values, data range 2 for images in [-1, 1]): the structural term people add to an inversion loss to get back
+    the local contrast MSE blurs away.  Differentiable with respect to `rgb`.  fp32 HIP tensors with a target that needs no
+    gradient are one autograd node (autograd.SsimLossFn, csrc/ssim_loss.hip: two launches forward, one backward); anything else
+    -- CPU tensors, other dtypes, CIPS3D_FUSED_SSIM=0 -- is the torch expression."""
+    from .metrics import _check_pair_gaussian, _ssim_gaussian_torch
+    rgb, target = _check_pair_gaussian(rgb, target, data_range)
+    if FUSED_SSIM and not target.requires_grad:
+        from . import hip
+        if hip.ssim_loss_supported(rgb, target):
+            from . import autograd as AG
+            return AG.SsimLossFn.apply(rgb, target, float(weight), float(data_range))
+    return weight * (1 - _ssim_gaussian_torch(rgb, target, data_range)[0]).mean()
+
+
 def perceptual_loss(net, target_images, rgb_weight=1.0, thumb_weight=1.0, img_size=1024):
     """rgb_weight sum (fea(rgb) - fea(target))^2 + thumb_weight sum (fea(thumb) - fea(target_thumb))^2 with `net` a
     perceptual.VGG16ConvLoss (projector_v10.py:1170-1174).  The target features -- of `target_images` [B,3,S,S] in [-1, 1] and of
@@ -226,11 +246,14 @@ class FlipProjector:
                       bs_cam=2, bs_render=1, bs_decoder=2, lr_cam=0.02, lr_render_w=0.001, lr_decoder_w=0.01,
                       lr_decoder_params=0.005, lr_noise=0.001, truncation_psi=1.0, flip_w_decoder_every=10,
                       azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
-                      mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0, lpips_metric=None):
+                      mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0, lpips_metric=None,
+                      ssim_weight=0.0):
         """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
         `mask_background`: from the appearance phase on, the image's gradient only flows where the render's foreground mask says
         so (mask_blend; the thumbnail is not blended, as in the reference).  `mse_weight` > 0 adds mse_weight x
-        F.mse_loss(image, target_images) (projector_v10.py:1176-1181).
+        F.mse_loss(image, target_images) (projector_v10.py:1176-1181).  `ssim_weight` > 0 (needs `target_images`) adds
+        ssim_weight x mean (1 - SSIM) of the same image -- after the mask blending -- against target_images (`ssim_loss`:
+        Gaussian window, continuous values), between the MSE term and the regulariser; 0: nothing new runs.
         `metrics_every` > 0 (needs `target_images`): PSNR and SSIM (metrics.py: scikit-image's defaults on 8-bit images) of view 0
         of the generator's image, before the mask blending, against target_images[0], at the steps with step % metrics_every == 0
         and at the last one (the reference's logging condition, :1125-1139) -- two launches per logged step, no copy and no
@@ -243,6 +266,8 @@ class FlipProjector:
         once.  None: no network is built (the reference's default downloads one) and nothing changes."""
         if mse_weight > 0 and target_images is None:
             raise ValueError("project_wplus: mse_weight > 0 needs target_images")
+        if ssim_weight > 0 and target_images is None:
+            raise ValueError("project_wplus: ssim_weight > 0 needs target_images")
         metrics_log = None
         if metrics_every < 0 or int(metrics_every) != metrics_every:
             raise ValueError(f"project_wplus: metrics_every must be a non-negative integer, got {metrics_every}")
@@ -262,7 +287,7 @@ class FlipProjector:
             n_logged = len([s for s in range(N_steps_pose + N_steps_app) if s % metrics_every == 0 or s == N_steps_pose + N_steps_app - 1]) \
                 if metrics_every > 0 else 0
             lpips_log = LPIPSLog(lpips_metric, target_images[0:1].detach().to(self.device), n_logged + 1)
-        if mse_weight > 0:
+        if mse_weight > 0 or ssim_weight > 0:
             target_images = target_images.detach().to(self.device, torch.float32).contiguous()
         G = copy.deepcopy(self.G).eval().requires_grad_(False).to(self.device)
         if optim_render_params:                              # projector_v10.py:967-968
@@ -310,6 +335,8 @@ class FlipProjector:
             loss = loss_fn(rgb, thumb)                   # (term order of projector_v10.py:1200: perceptual + mse + regulariser)
             if mse_weight > 0:
                 loss = loss + _weighted_mse(rgb, target_images, mse_weight)
+            if ssim_weight > 0:
+                loss = loss + ssim_loss(rgb, target_images, ssim_weight)
             if optim_noise_bufs and regularize_noise_weight > 0:
                 loss = loss + noise_regulariser(noise_bufs, regularize_noise_weight)
             for o in opts:

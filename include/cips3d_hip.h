@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 39  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 40  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1402,6 +1402,47 @@ int cips3d_lpips_head(const float* za, const float* zb, const float* lin, int B,
 int cips3d_lpips(const cips3d_vgg_ctx* ctx, const cips3d_lpips_io* io, void* stream);
 int cips3d_lpips_split(const cips3d_vgg_split_ctx* ctx, const cips3d_lpips_io* io, void* stream);
 int cips3d_sizeof_lpips_io(void);
+
+/* Gaussian-window SSIM of fp32 image pairs as a differentiable loss (csrc/ssim_loss.hip): Wang et al. 2004, which is scikit-image's
+ * structural_similarity(gaussian_weights = True, sigma = 1.5, use_sample_covariance = False, data_range = R).  a, b [B,C,H,W]
+ * fp32, continuous values, nothing quantised or clamped.  The window is g (x) g with 11 taps g[i] ~ exp(-(i - 5)^2 / 4.5), sum
+ * g = 1; only the (H - 10) (W - 10) windows per channel that lie wholly inside the image count.  Per window, with E the weighted
+ * mean: mux, muy, vx = E[x^2] - mux^2, vy, vxy = E[xy] - mux muy, C1 = (0.01 R)^2, C2 = (0.03 R)^2,
+ *     S = (2 mux muy + C1) (2 vxy + C2) / ((mux^2 + muy^2 + C1) (vx + vy + C2)),
+ * ssim[i] = the mean of S over image i's C (H - 10) (W - 10) windows, loss = weight * mean_i (1 - ssim[i]).
+ *
+ * The moments are taken of x - cx, y - cy with cx, cy the first pixel of the workgroup's tile in each image -- pixel (tile_y *
+ * tile_h, tile_x * tile_w) of the plane, the tile being the one that holds the window's origin: variances and the covariance
+ * are shift-invariant, only the means add the constant back, and E[x^2] - mux^2 no longer cancels on a bright flat region (a
+ * flat image has vx = vy = vxy = 0 exactly).  Equal images give S = 1, ssim = 1 and loss = 0 exactly.
+ *
+ * cips3d_ssim_loss        two launches: one workgroup per (image, channel, tile of tile_h x tile_w window origins) writes one
+ *                         fp32 partial (the windows added in a fixed order: tile_h * tile_w / threads in the thread, the wave's
+ *                         butterfly, the waves), then one workgroup adds each image's partials in fp64 in a fixed order ->
+ *                         ssim [B] (fp64, optional) and loss (fp32 scalar, optional; at least one of the two).  No atomics: the
+ *                         results are bit-identical run to run, and ssim[i] does not depend on the batch.  map: optional
+ *                         [B,C,H-10,W-10], receives S.  need_grad != 0: the forward also stores the three per-window maps
+ *                         the backward reads, [B,C,H-10,W-10] fp32 each, behind the partials in `workspace`:
+ *                             D2 = dS/dvx = -S / B2,  D3 = dS/dvxy = 2 A1 / (B1 B2),  D1 = dS/dmux - 2 (mux - kx) D2 - (muy - ky) D3
+ *                         (A1, B1, B2: the factors of S in the order written above; dS/dmux = (2 / B1) (muy A2 / B2 - mux S)),
+ *                         i.e. dS/dmux with E[x^2], E[xy] held fixed, for the images shifted by kx, ky = the first pixel of
+ *                         the plane (image, channel) of a and b -- a(p) - mux cancels the way the variance does.
+ * cips3d_ssim_loss_bwd    one launch, one workgroup per (image, channel, tile of tile_h x tile_w pixels):
+ *                             da(p) = coef gloss[0] sum_{w holds p} g(x)g(p - w) (D1(w) + 2 (a(p) - kx) D2(w) + (b(p) - ky) D3(w)),
+ *                         coef = -weight / (B C (H - 10) (W - 10)): the transposed ("full") convolution of the three maps,
+ *                         zero outside the valid origins.  gloss: the upstream gradient, a device scalar (never read on the
+ *                         host).  `workspace`, a, b, the shape and weight: as the forward call with need_grad != 0 left / had
+ *                         them.  There is no gradient with respect to b.
+ * `workspace`: cips3d_ssim_loss_workspace_bytes(B, C, H, W, need_grad) bytes, 16-byte aligned (3 x 4 bytes per window with
+ * need_grad: 37 MB per 1024^2 RGB image).  cips3d_ssim_loss_tile: the tile's sides; returns the threads per workgroup.
+ * CIPS3D_E_BADARG, nothing launched: a null required pointer, B or C < 1, H or W < 11, data_range <= 0, a grid beyond 2^31 - 1
+ * workgroups (workspace_bytes returns it as a negative size).  CIPS3D_E_UNSUPP: a misaligned workspace or ssim pointer. */
+int cips3d_ssim_loss_tile(int* tile_h, int* tile_w);
+int64_t cips3d_ssim_loss_workspace_bytes(int B, int C, int H, int W, int need_grad);
+int cips3d_ssim_loss(const float* a, const float* b, int B, int C, int H, int W, float weight, float data_range, void* workspace,
+                     int need_grad, float* map, double* ssim, float* loss, void* stream);
+int cips3d_ssim_loss_bwd(const float* a, const float* b, int B, int C, int H, int W, float weight, const void* workspace,
+                         const float* gloss, float* da, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """PSNR and SSIM of two image files on the GPU (cips_3dplusplus_amd/metrics.py: scikit-image's defaults for 8-bit images).
 
-    python tools/image_metrics.py A.png B.png [--gray] [--time [--reps 11]] [--lpips VGG_PTH LIN_PTH]
+    python tools/image_metrics.py A.png B.png [--gray] [--time [--reps 11]] [--lpips VGG_PTH LIN_PTH] [--gaussian]
     python tools/image_metrics.py --size 1024 [--gray] [--time [--reps 11]]      (a seeded random pair, +-3 grey levels apart)
 
 Both files are read with PIL as 8-bit RGB (`--gray`: as 8-bit luminance) and must have the same size.  The last stdout line is
@@ -8,7 +8,9 @@ one JSON object: {"psnr", "ssim", "sse", "size", "channels"}.  `--time` adds, fo
 synchronise on both sides) of `metrics.image_metrics` on device-resident uint8 images (`gpu_ms`, its one read included) and of
 the host route it replaces for an fp32 image -- `hip.rgb_to_uint8` -> `.cpu()` -> a float64 numpy / scipy SSIM (`host_ms`).
 `--lpips VGG_PTH LIN_PTH` adds "lpips": LPIPS v0.1 (net = 'vgg') of the pair from torchvision's vgg16 checkpoint and the lpips
-package's vgg.pth (perceptual.LPIPS; RGB only, both sides multiples of 16)."""
+package's vgg.pth (perceptual.LPIPS; RGB only, both sides multiples of 16).  `--gaussian` adds "ssim_gaussian": the Gaussian-window
+SSIM (metrics.ssim_gaussian: 11 taps, sigma 1.5, population covariance) of the images as continuous values x / 127.5 - 1 with
+data range 2; with `--time` also its wall time, `gaussian_gpu_ms`."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -48,6 +50,7 @@ if __name__ == "__main__":
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--lpips", nargs=2, metavar=("VGG_PTH", "LIN_PTH"))
+    ap.add_argument("--gaussian", action="store_true")
     args = ap.parse_args()
     mode = "L" if args.gray else "RGB"
     if args.size > 0:
@@ -70,6 +73,11 @@ if __name__ == "__main__":
             ap.error("--lpips needs RGB images")
         from cips_3dplusplus_amd.perceptual import LPIPS
         out["lpips"] = float(LPIPS("vgg", weights=args.lpips[0], lin_weights=args.lpips[1])(ta, tb)[0])
+    if args.gaussian:
+        ga, gb = ta.float() / 127.5 - 1.0, tb.float() / 127.5 - 1.0
+        out["ssim_gaussian"] = float(metrics.ssim_gaussian(ga, gb)[0])
+        if args.time:
+            out["gaussian_gpu_ms"] = median_ms(lambda: metrics.ssim_gaussian(ga, gb), args.reps)
     if args.time:
         fa, fb = ta.float() / 127.5 - 1.0, tb.float() / 127.5 - 1.0
         out["gpu_ms"] = median_ms(lambda: metrics.image_metrics(ta, tb), args.reps)
