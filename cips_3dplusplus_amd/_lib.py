@@ -157,7 +157,7 @@ class NerfBwdFusedParams(C.Structure):
         "w_first", "packed", "packed_t", "w_view", "film", "layer_bias", "w_sigma", "b_sigma", "w_rgb", "b_rgb",
         "sigmoid_beta", "d_features", "d_thumb", "stash", "scratch", "dfilm", "dcam")] + [
         ("hidden", C.c_int32), ("depth", C.c_int32), ("n_chunks", C.c_int32), ("pad_", C.c_int32),
-        ("fwd_sdf", C.c_void_p), ("fwd_crgb", C.c_void_p)]
+        ("fwd_sdf", C.c_void_p), ("fwd_crgb", C.c_void_p), ("d_mask", C.c_void_p), ("d_xyz", C.c_void_p), ("xyz", C.c_void_p)]
 
 
 _SIGS = {
@@ -271,11 +271,15 @@ _SIGS = {
     "cips3d_nerf_bwd_dot": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_i64, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_composite": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                           c_f32p, c_f32p, C.c_void_p]),
+    "cips3d_nerf_bwd_composite_geo": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                              c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_row_dots": (c_int, [c_f32p, c_f32p, c_int, c_i64, c_f32p, c_int, c_int, c_i64, C.c_void_p]),
     "cips3d_nerf_bwd_film_grad": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                           c_f32p, c_f32p, c_int, c_int, c_int, c_i64, C.c_void_p]),
     "cips3d_nerf_bwd_camera": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_camera_acc": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "cips3d_nerf_bwd_camera_geo": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
+                                           c_f32p, C.c_void_p]),
     "cips3d_camera_params_bwd": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_fused_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "cips3d_nerf_bwd_fused_stash_floats": (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int]),
@@ -349,7 +353,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 40           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 41           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

@@ -614,7 +614,11 @@ def nerf_named_parameters(renderer):
 
 
 class NerfRenderFn(Function):
-    """VolumeFeatureRenderer.render with gradients w.r.t. the camera pose and the FiLM table.  Forward = the fused kernel;
+    """VolumeFeatureRenderer.render with gradients w.r.t. the camera pose and the FiLM table, from the upstreams of ALL its maps:
+    features, thumb, and -- as autograd reaches them through the reference's volume_integration (nerf_utils.py:329-336) -- xyz
+    [B,3,S,S] and mask [2,B,S,S] (mask[0] = the last sample's weight, mask[1] = depth = -|xyz|).  The last two enter the
+    compositing backward and the camera chain of either route and add no launch; absent ones (None) cost nothing.  Forward = the
+    fused kernel;
     backward = the fused recompute + backward kernels of csrc/nerf_bwd_fused.hip (the materialised sequence of
     csrc/nerf_bwd.hip for shapes they do not cover, or with CIPS3D_FUSED_NERF_BACKWARD=0).  The renderer's own weights are treated as constants
     (`optim_render_params: false` in the released inversion recipes, train_cips3d_compcars_v10.yaml:585)."""
@@ -639,14 +643,16 @@ class NerfRenderFn(Function):
         ctx.renderer = renderer
         ctx.fwd = fwd
         ctx.cfg = (img_size, n_samples, static_viewdirs)
-        ctx.save_for_backward(cam_poses.detach(), focals, near, far, film.detach(), perturb_u)
-        ctx.mark_non_differentiable(mask, xyz)
-        ctx.set_materialize_grads(False)        # (else the engine fills zero gradients for xyz and mask; None is handled below)
+        # (xyz: the depth channel's backward needs the forward's map -- kept only when something can ask for a gradient)
+        ctx.save_for_backward(cam_poses.detach(), focals, near, far, film.detach(), perturb_u,
+                              xyz if any(ctx.needs_input_grad) else None)
+        ctx.set_materialize_grads(False)        # (else the engine fills zero gradients for xyz and mask; None = absent, see backward)
         return features, thumb, xyz, mask
 
     @staticmethod
     def backward(ctx, dfeat, dthumb, dxyz, dmask):
-        cam_poses, focals, near, far, film, perturb_u = ctx.saved_tensors
+        cam_poses, focals, near, far, film, perturb_u, xyz = ctx.saved_tensors
+        geo = dict(d_mask=dmask, d_xyz=dxyz, xyz=xyz if dmask is not None else None)
         img_size, n_samples, static = ctx.cfg
         r = ctx.renderer
         _, layer_bias = r._derived_buffers()
@@ -658,7 +664,7 @@ class NerfRenderFn(Function):
         if ctx.want_params:
             dfilm, dcam, pg = hip.nerf_backward(r.network, r.sigmoid_beta.detach() if r.with_sdf else None, cam_poses, focals, near, far, perturb_u, film,
                                                 layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(),
-                                                need_params=True)
+                                                need_params=True, **geo)
             names = [n for n, _ in nerf_named_parameters(r)]
             grads = tuple(pg[n].reshape(p.shape) if ctx.needs_input_grad[10 + i] else None
                           for i, (n, (_, p)) in enumerate(zip(names, nerf_named_parameters(r))))
@@ -667,9 +673,9 @@ class NerfRenderFn(Function):
             packed, _ = r._derived_buffers()
             dfilm, dcam = hip.nerf_backward_fused(r.network, r.sigmoid_beta.detach() if r.with_sdf else None, cam_poses, focals, near, far, perturb_u,
                                                   film, layer_bias, packed, r._packed_transposed(), img_size, n_samples,
-                                                  static, dfeat, dthumb, fwd=ctx.fwd)
+                                                  static, dfeat, dthumb, fwd=ctx.fwd, **geo)
             ctx.fwd = None
         else:
             dfilm, dcam = hip.nerf_backward(r.network, r.sigmoid_beta.detach() if r.with_sdf else None, cam_poses, focals, near, far, perturb_u, film,
-                                            layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float())
+                                            layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(), **geo)
         return (None, dcam, None, None, None, dfilm, None, None, None, None) + (None,) * ctx.n_params

@@ -13,6 +13,7 @@
 //   cips3d_nerf_bwd_heads      rows of a [nr,H] matrix applied over the channels (sigma / rgb heads; W0^T, Wd^T in backward)
 //   cips3d_nerf_bwd_dot        g[p] = <dF[:, ray], f[:, p]>
 //   cips3d_nerf_bwd_composite  volume integration forward + backward per ray -> w, d(sdf), d(rgb logits)
+//                              (_geo: also from the gradients of the mask, depth and xyz maps)
 //   cips3d_nerf_bwd_film_grad  d(pre) = upstream * cos(gamma pre + beta) * gamma, sums for d(gamma), d(beta)
 //   cips3d_nerf_bwd_camera     d(points), d(viewdirs) -> d(cam_poses)
 //   cips3d_camera_params_bwd   d(cam_poses) -> d(azim, elev)     (nerf_utils.py:344-436, forward-mode duals)
@@ -36,6 +37,31 @@ __device__ __forceinline__ RayGeom ray_geom(const cips3d_nerf_bwd_geom& G, int b
                        0.f, 0.f);
   nerf_linspace_consts(r.N, r.t_end, r.t_step);   // (computed here, on the device: these kernels take no such arguments)
   return r;
+}
+
+// Upstreams of the geometry maps of one ray (nerf_utils.py:329-336: xyz = sum_k w_k p_k, mask[0] = w_{N-1}, mask[1] = -|xyz|):
+// m = d loss / d mask[0], (x, y, z) = the effective adjoint of xyz = d_xyz - d_depth * xyz / |xyz| (0 from the depth where
+// |xyz| == 0: torch's subgradient of norm).  d_mask [2,B,R] (needs the forward's xyz [B,3,R]) and d_xyz [B,3,R] may each be NULL.
+struct GeoAdj { float x, y, z, m; };
+__device__ __forceinline__ GeoAdj geo_adjoint(const float* __restrict__ d_mask, const float* __restrict__ d_xyz,
+                                              const float* __restrict__ xyz, int B, int R, int b, int ray) {
+  GeoAdj a{0.f, 0.f, 0.f, 0.f};
+  if (d_xyz) {
+    const float* dx = d_xyz + (int64_t)b * 3 * R + ray;
+    a.x = dx[0]; a.y = dx[R]; a.z = dx[2 * R];
+  }
+  if (d_mask) {
+    a.m = d_mask[(int64_t)b * R + ray];
+    const float dd = d_mask[((int64_t)B + b) * R + ray];
+    const float* xp = xyz + (int64_t)b * 3 * R + ray;
+    const float X = xp[0], Y = xp[R], Z = xp[2 * R];
+    const float n = nerf_norm3(X, Y, Z);
+    if (n > 0.f) {
+      const float s = dd / n;
+      a.x -= s * X; a.y -= s * Y; a.z -= s * Z;
+    }
+  }
+  return a;
 }
 
 // ---------------------------------------------------------------------------------------------- points + layer 0
@@ -167,13 +193,17 @@ __global__ void __launch_bounds__(256) dot_kernel(const float* __restrict__ dF, 
 
 // ---------------------------------------------------------------------------------------------- compositing fwd + bwd
 // One thread per ray (nerf_utils.py:264-307).  Writes w, T (scratch), then d(sdf) [B,P] and d(rgb logits) [B,3,P].
+// d_mask / d_xyz (either set; wave-uniform): G_k gains <xbar, p_k> + [k == N-1] mbar, p_k the world point the forward composites,
+// and the ray's sum_k w_k, sum_k w_k z_k go to wsum / wzsum [B,R] (the direct path through the points: camera_chain_kernel).
 __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, const float* __restrict__ sdf,
                                                         const float* __restrict__ crgb, const float* __restrict__ g,
                                                         const float* __restrict__ dthumb,
                                                         const float* __restrict__ sigmoid_beta, float* __restrict__ w,
                                                         float* __restrict__ Tbuf, float* __restrict__ dsdf,
                                                         float* __restrict__ dcrgb, float* __restrict__ ddnorm,
-                                                        float* __restrict__ dbeta_ray) {
+                                                        float* __restrict__ dbeta_ray, const float* __restrict__ d_mask,
+                                                        const float* __restrict__ d_xyz, const float* __restrict__ xyz,
+                                                        float* __restrict__ wsum, float* __restrict__ wzsum) {
   const int b = blockIdx.y;
   const int R = G.img_size * G.img_size;
   const int ray = blockIdx.x * 256 + threadIdx.x;
@@ -205,6 +235,10 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
   float S = 0.f;      // sum_{j>k} w_j G_j
   float dn = 0.f;     // d loss / d |rays_d|  (delta_k = dz_k * |rays_d|)
   float dbt = 0.f;    // d loss / d sigmoid_beta of this ray: sigma = s / beta, s = sigmoid(-sdf / beta)
+  const bool geo = d_mask != nullptr || d_xyz != nullptr;
+  GeoAdj ga{0.f, 0.f, 0.f, 0.f};
+  if (geo) ga = geo_adjoint(d_mask, d_xyz, xyz, G.B, R, b, ray);
+  float ws = 0.f, wz = 0.f;   // sum_k w_k, sum_k w_k z_k
   for (int k = N - 1; k >= 0; --k) {
     const int64_t o = (int64_t)k * R;
     const float dz = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f);
@@ -215,7 +249,15 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
     const float alpha = 1.f - e;
     const float Tk = tp[o], wk = wp[o];
     const float s0 = nerf_sigmoid(cp[o]), s1 = nerf_sigmoid(cp[P + o]), s2 = nerf_sigmoid(cp[2 * P + o]);
-    const float Gk = g[(int64_t)b * P + ray + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
+    float Gk = g[(int64_t)b * P + ray + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
+    if (geo) {
+      const float z = r.z(k);
+      const float px = r.ox + r.dx * z, py = r.oy + r.dy * z, pz = r.oz + r.dz * z;
+      Gk += (ga.x * px + ga.y * py) + ga.z * pz;
+      if (k == N - 1) Gk += ga.m;
+      ws += wk;
+      wz = fmaf(wk, z, wz);
+    }
     const float dalpha = Tk * Gk - S / ((1.f - alpha) + 1e-10f);
     S = fmaf(wk, Gk, S);
     const float dsigma = dalpha * delta * e;
@@ -228,20 +270,27 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
   }
   ddnorm[(int64_t)b * R + ray] = dn;
   if (dbeta_ray) dbeta_ray[(int64_t)b * R + ray] = dbt;
+  if (geo) {
+    wsum[(int64_t)b * R + ray] = ws;
+    wzsum[(int64_t)b * R + ray] = wz;
+  }
 }
 
 // The same integration with one SAMPLE per thread: 32 rays x N samples per workgroup (N <= 32).  A thread per ray leaves the chip
 // to R*B / 64 waves (128 at 64^2, B = 2: 87 us for 0.4 M points); here the transcendental work and the loads of all samples run
 // side by side and only the products along the ray -- T_k, the suffix sum S_k, the per-ray sums -- are chained, each thread walking
 // the shared per-sample factors in the per-ray loop's own order (the results are the ones composite_kernel produces).
-// dynamic LDS: 7 * N * 32 floats.
+// dynamic LDS: 7 * N * 32 floats (the geometry upstreams need no eighth array: the thread that sums w_k z_k has the ray's
+// geometry and rebuilds z_k).
 __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geom G, const float* __restrict__ sdf,
                                                              const float* __restrict__ crgb, const float* __restrict__ g,
                                                              const float* __restrict__ dthumb,
                                                              const float* __restrict__ sigmoid_beta, float* __restrict__ w,
                                                              float* __restrict__ Tbuf, float* __restrict__ dsdf,
                                                              float* __restrict__ dcrgb, float* __restrict__ ddnorm,
-                                                             float* __restrict__ dbeta_ray) {
+                                                             float* __restrict__ dbeta_ray, const float* __restrict__ d_mask,
+                                                             const float* __restrict__ d_xyz, const float* __restrict__ xyz,
+                                                             float* __restrict__ wsum, float* __restrict__ wzsum) {
   extern __shared__ float comp_lds[];
   const int b = blockIdx.y;
   const int R = G.img_size * G.img_size;
@@ -276,7 +325,15 @@ __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geo
               d2 = dthumb[((int64_t)b * 3 + 2) * R + ray];
   const float* cp = crgb + (int64_t)b * 3 * P + o;
   const float s0 = nerf_sigmoid(cp[0]), s1 = nerf_sigmoid(cp[P]), s2 = nerf_sigmoid(cp[2 * P]);
-  const float Gk = g[(int64_t)b * P + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
+  float Gk = g[(int64_t)b * P + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
+  const bool geo = d_mask != nullptr || d_xyz != nullptr;
+  if (geo) {
+    const GeoAdj ga = geo_adjoint(d_mask, d_xyz, xyz, G.B, R, b, ray);
+    const float z = r.z(k);
+    const float px = r.ox + r.dx * z, py = r.oy + r.dy * z, pz = r.oz + r.dz * z;
+    Gk += (ga.x * px + ga.y * py) + ga.z * pz;
+    if (k == N - 1) Gk += ga.m;
+  }
   Gl[li] = Gk;
   __syncthreads();
   float T = 1.f;
@@ -316,6 +373,16 @@ __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geo
     if (!raw)
       for (int j = N - 1; j >= 0; --j) dbt = fmaf(Dl[j * 32 + lr], Cl[j * 32 + lr], dbt);
     dbeta_ray[(int64_t)b * R + ray] = dbt;
+  }
+  if (geo && k == N - 1) {   // (the per-ray loop's order)
+    float ws = 0.f, wz = 0.f;
+    for (int j = N - 1; j >= 0; --j) {
+      const float wj = Wl[j * 32 + lr];
+      ws += wj;
+      wz = fmaf(wj, r.z(j), wz);
+    }
+    wsum[(int64_t)b * R + ray] = ws;
+    wzsum[(int64_t)b * R + ray] = wz;
   }
 }
 
@@ -413,9 +480,14 @@ __global__ void __launch_bounds__(256) film_grad_kernel(float* __restrict__ buf,
 // pts_n = (o + d z) 2/span;  rays_d = Rm d_cam;  o = T;  viewdir = normalize(static ? d_cam : rays_d).
 // grid (ceil(R / 64), B), 1024 threads: wave w of a workgroup owns a slice of the samples of the group's 64 rays (every term is
 // linear in the per-sample sums) -- a thread per ray alone is R*B/64 waves on the whole chip; 12 atomics per workgroup.
+// d_mask / d_xyz (either set): xyz = sum_k w_k (o + z_k d) also reaches the pose directly, d o += wsum xbar, d d += wzsum xbar
+// (world units: not scaled by 2 / span), in slice 0 beside ddnorm.
 __global__ void __launch_bounds__(1024) camera_chain_kernel(cips3d_nerf_bwd_geom G, const float* __restrict__ dptsn,
                                                             const float* __restrict__ dvd_pt,
-                                                            const float* __restrict__ ddnorm, float* __restrict__ dcam) {
+                                                            const float* __restrict__ ddnorm, float* __restrict__ dcam,
+                                                            const float* __restrict__ d_mask, const float* __restrict__ d_xyz,
+                                                            const float* __restrict__ xyz, const float* __restrict__ wsum,
+                                                            const float* __restrict__ wzsum) {
   __shared__ float sh[12][16];
   const int b = blockIdx.y;
   const int R = G.img_size * G.img_size;
@@ -453,6 +525,12 @@ __global__ void __launch_bounds__(1024) camera_chain_kernel(cips3d_nerf_bwd_geom
     if (slice == 0) {   // |rays_d| enters the sample spacing of the compositing (nerf_utils.py:264-268)
       const float gn = ddnorm[(int64_t)b * R + ray] / r.dnorm;
       dD[0] = fmaf(gn, r.dx, dD[0]); dD[1] = fmaf(gn, r.dy, dD[1]); dD[2] = fmaf(gn, r.dz, dD[2]);
+      if (d_mask != nullptr || d_xyz != nullptr) {
+        const GeoAdj ga = geo_adjoint(d_mask, d_xyz, xyz, G.B, R, b, ray);
+        const float ws = wsum[(int64_t)b * R + ray], wz = wzsum[(int64_t)b * R + ray];
+        dO[0] = fmaf(ws, ga.x, dO[0]); dO[1] = fmaf(ws, ga.y, dO[1]); dO[2] = fmaf(ws, ga.z, dO[2]);
+        dD[0] = fmaf(wz, ga.x, dD[0]); dD[1] = fmaf(wz, ga.y, dD[1]); dD[2] = fmaf(wz, ga.z, dD[2]);
+      }
     }
     const float dc[3] = {r.dcx, r.dcy, r.dcz};
 #pragma unroll
@@ -573,21 +651,31 @@ extern "C" int cips3d_nerf_bwd_dot(const float* dF, const float* f, int B, int H
   return cips3d_launch_status();
 }
 
-extern "C" int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* G, const float* sdf, const float* crgb, const float* g,
-                                         const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch,
-                                         float* dsdf, float* dcrgb, float* ddnorm, float* dbeta_ray, void* stream) {
+// d_mask / d_xyz NULL: the compositing backward of the features and the thumbnail alone
+extern "C" int cips3d_nerf_bwd_composite_geo(const cips3d_nerf_bwd_geom* G, const float* sdf, const float* crgb, const float* g,
+                                             const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch,
+                                             float* dsdf, float* dcrgb, float* ddnorm, float* dbeta_ray, const float* d_mask,
+                                             const float* d_xyz, const float* xyz, float* wsum, float* wzsum, void* stream) {
   if (!geom_ok(G) || !sdf || !crgb || !g || !dthumb || !w || !T_scratch || !dsdf || !dcrgb || !ddnorm)
     return CIPS3D_E_BADARG;
+  if ((d_mask && !xyz) || ((d_mask || d_xyz) && (!wsum || !wzsum))) return CIPS3D_E_BADARG;
   if (G->B == 0) return 0;
   const int R = G->img_size * G->img_size;
   if (G->n_samples >= 2 && G->n_samples <= 32)
     hipLaunchKernelGGL(composite_par_kernel, dim3((unsigned)ceil_div(R, 32), (unsigned)G->B), dim3(32 * G->n_samples),
                        sizeof(float) * 7 * 32 * G->n_samples, as_stream(stream), *G, sdf, crgb, g, dthumb, sigmoid_beta, w,
-                       T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray);
+                       T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray, d_mask, d_xyz, xyz, wsum, wzsum);
   else
     hipLaunchKernelGGL(composite_kernel, dim3((unsigned)ceil_div(R, 256), (unsigned)G->B), dim3(256), 0, as_stream(stream), *G, sdf,
-                       crgb, g, dthumb, sigmoid_beta, w, T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray);
+                       crgb, g, dthumb, sigmoid_beta, w, T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray, d_mask, d_xyz, xyz, wsum, wzsum);
   return cips3d_launch_status();
+}
+
+extern "C" int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* G, const float* sdf, const float* crgb, const float* g,
+                                         const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch,
+                                         float* dsdf, float* dcrgb, float* ddnorm, float* dbeta_ray, void* stream) {
+  return cips3d_nerf_bwd_composite_geo(G, sdf, crgb, g, dthumb, sigmoid_beta, w, T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int cips3d_nerf_bwd_row_dots(const float* a, const float* x, int nx, int64_t Px, float* out, int B, int rows,
@@ -616,27 +704,32 @@ extern "C" int cips3d_nerf_bwd_film_grad(float* buf, const float* pre, const flo
   return cips3d_launch_status();
 }
 
-extern "C" int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
-                                      const float* ddnorm, float* dcam, void* stream) {
+// accumulate != 0: added to a dcam the caller has zeroed; d_mask / d_xyz NULL: no direct path from the geometry maps
+extern "C" int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
+                                          const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
+                                          const float* wsum, const float* wzsum, int accumulate, float* dcam, void* stream) {
   if (!geom_ok(G) || !dptsn || !dvd_pt || !ddnorm || !dcam) return CIPS3D_E_BADARG;
+  if ((d_mask && !xyz) || ((d_mask || d_xyz) && (!wsum || !wzsum))) return CIPS3D_E_BADARG;
   if (G->B == 0) return 0;
   hipStream_t st = as_stream(stream);
-  hipError_t e = hipMemsetAsync(dcam, 0, sizeof(float) * 12 * G->B, st);
-  if (e != hipSuccess) return (int)e;
+  if (!accumulate) {
+    hipError_t e = hipMemsetAsync(dcam, 0, sizeof(float) * 12 * G->B, st);
+    if (e != hipSuccess) return (int)e;
+  }
   const int R = G->img_size * G->img_size;
   hipLaunchKernelGGL(camera_chain_kernel, dim3((unsigned)ceil_div(R, 64), (unsigned)G->B), dim3(1024), 0, st, *G, dptsn, dvd_pt,
-                     ddnorm, dcam);
+                     ddnorm, dcam, d_mask, d_xyz, xyz, wsum, wzsum);
   return cips3d_launch_status();
+}
+
+extern "C" int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
+                                      const float* ddnorm, float* dcam, void* stream) {
+  return cips3d_nerf_bwd_camera_geo(G, dptsn, dvd_pt, ddnorm, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dcam, stream);
 }
 
 extern "C" int cips3d_nerf_bwd_camera_acc(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
                                           const float* ddnorm, float* dcam, void* stream) {
-  if (!geom_ok(G) || !dptsn || !dvd_pt || !ddnorm || !dcam) return CIPS3D_E_BADARG;
-  if (G->B == 0) return 0;
-  const int R = G->img_size * G->img_size;
-  hipLaunchKernelGGL(camera_chain_kernel, dim3((unsigned)ceil_div(R, 64), (unsigned)G->B), dim3(1024), 0, as_stream(stream), *G, dptsn,
-                     dvd_pt, ddnorm, dcam);
-  return cips3d_launch_status();
+  return cips3d_nerf_bwd_camera_geo(G, dptsn, dvd_pt, ddnorm, nullptr, nullptr, nullptr, nullptr, nullptr, 1, dcam, stream);
 }
 
 extern "C" int cips3d_camera_params_bwd(const float* locations, const float* up, const float* dextrinsics, int B,

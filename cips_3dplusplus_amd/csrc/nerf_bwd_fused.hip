@@ -1,6 +1,7 @@
 // Fused backward of the NeRF half on gfx950: d loss / d(FiLM table) and d loss / d(cam_poses) from the gradients of the
-// feature map and the thumbnail, with the point MLP held in the register file in BOTH directions (the reference obtains
-// these from autograd through SirenGenerator.forward and Render.volume_integration, cips3d/volume_renderer.py:39-160,
+// feature map and the thumbnail -- and, when given, of the mask / depth and xyz maps (d_mask, d_xyz: they enter at the compositing
+// backward and at the camera chain and nowhere else) -- with the point MLP held in the register file in BOTH directions (the
+// reference obtains these from autograd through SirenGenerator.forward and Render.volume_integration, cips3d/volume_renderer.py:39-160,
 // cips3d/nerf_utils.py:264-338; flip inversion drives it, models/projector_v10.py:211-277).
 //
 // The materialised sequence (nerf_bwd.hip + the decoder GEMM) rebuilds every layer as act[b][c][p] in HBM and walks it with
@@ -13,6 +14,7 @@
 //                       in the wave's own register order (1 KiB per wave store, fully coalesced); per point it emits sdf,
 //                       the rgb logits and g = <d_features[:, ray], feature> -- all the compositing backward needs.
 //   composite_kernel    (nerf_bwd.hip) volume integration forward + backward per ray -> w, d sdf, d rgb logits, d |rays_d|
+//                       (d_mask / d_xyz set: d loss / d w_k gains the geometry maps' share; per-ray sum w_k, sum w_k z_k)
 //   nerf_bwd_kernel     per 16-point tile, layers in reverse.  Epilogue of layer l (VALU):
 //                           u    = upstream (accumulator of the previous MFMA layer, or the compositing gradient)
 //                           uc   = u * cos(gamma' a + c)          a = stashed accumulator of layer l
@@ -26,7 +28,7 @@
 //                       The sums over the 16 points of a tile are a cross-lane reduce-scatter (DPP quad permutes + two
 //                       bpermute stages: 49 instructions per 16 values instead of 64 + 15 selects), accumulated in LDS and
 //                       flushed with one global atomic per workgroup and table entry.
-//   camera_chain_kernel (nerf_bwd.hip) d points, d viewdirs, d |rays_d| -> d cam_poses
+//   camera_chain_kernel (nerf_bwd.hip) d points, d viewdirs, d |rays_d| (and xyz's direct path through the points) -> d cam_poses
 //
 // HBM traffic: the stash is written once and read once (B * P * depth * H * 4 bytes each way); everything else is per-point
 // scalars.  Renderer weights are constants of this path (`optim_render_params: false`, train_cips3d_compcars_v10.yaml:585).
@@ -61,6 +63,8 @@ struct FusedArgs {
   float* dptsn;        // [B][3][P]
   float* dvd;          // [B][3][P]
   float* ddnorm;       // [B][R]
+  float* wsum;         // [B][R]  (d_mask / d_xyz)
+  float* wzsum;        // [B][R]
   float* sums;         // [B][L][2][H]: S1, S2
 };
 
@@ -862,8 +866,8 @@ int launch_fused(const FusedArgs& a, hipStream_t st) {
   if (P.fwd_sdf) hipLaunchKernelGGL((nerf_g_kernel<NT>), dim3(wgs), dim3(WAVES * 64), 0, st, a);
   else hipLaunchKernelGGL((nerf_stash_kernel<NT, TPS>), dim3(wgs), dim3(WAVES * 64), lds_a, st, a);
   if (int rc = cips3d_launch_status()) return rc;
-  if (int rc = cips3d_nerf_bwd_composite(&G, a.sdf, a.crgb, a.g, P.d_thumb, P.sigmoid_beta, a.wts, a.Tb, a.dsdf, a.dcrgb,
-                                         a.ddnorm, nullptr, st))
+  if (int rc = cips3d_nerf_bwd_composite_geo(&G, a.sdf, a.crgb, a.g, P.d_thumb, P.sigmoid_beta, a.wts, a.Tb, a.dsdf, a.dcrgb,
+                                             a.ddnorm, nullptr, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, st))
     return rc;
   hipLaunchKernelGGL((nerf_bwd_kernel<NT, TPS>), dim3(wgs), dim3(WAVES * 64), lds_b, st, a);
   return cips3d_launch_status();
@@ -895,7 +899,7 @@ extern "C" int64_t cips3d_nerf_bwd_fused_stash_floats(int B, int img_size, int n
 extern "C" int64_t cips3d_nerf_bwd_fused_scratch_floats(int B, int img_size, int n_samples, int hidden, int depth) {
   if (B <= 0 || img_size <= 0 || n_samples <= 0 || hidden <= 0 || depth <= 0) return 0;
   const int64_t R = (int64_t)img_size * img_size, P = R * n_samples, H = hidden, L = depth + 1;
-  return align4(10 * H) + align4(B * R * H) + 17 * align4(B * P) + align4(B * R) + align4(B * L * 2 * H);
+  return align4(10 * H) + align4(B * R * H) + 17 * align4(B * P) + 3 * align4(B * R) + align4(B * L * 2 * H);
 }
 
 extern "C" int cips3d_nerf_pack_weights_t(const float* w_hidden, const float* w_view, const float* packed, float* packed_t,
@@ -918,6 +922,7 @@ extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, voi
       !P.b_rgb || !P.d_features || !P.d_thumb || !P.stash || !P.scratch || !P.dfilm || !P.dcam)
     return CIPS3D_E_BADARG;
   if (P.n_chunks < 1 || P.n_chunks > G.n_samples) return CIPS3D_E_BADARG;
+  if (P.d_mask && !P.xyz) return CIPS3D_E_BADARG;
   if (!fused_shape_ok(P.hidden, P.depth, G.img_size, G.n_samples)) return CIPS3D_E_UNSUPP;
   if (G.B == 0) return 0;
   hipStream_t st = as_stream(stream);
@@ -948,6 +953,8 @@ extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, voi
   a.dptsn = take(3 * B * Pn);
   a.dvd = take(3 * B * Pn);
   a.ddnorm = take(B * R);
+  a.wsum = take(B * R);
+  a.wzsum = take(B * R);
   a.sums = take((int64_t)B * L * 2 * H);
 
   {
@@ -971,5 +978,6 @@ extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, voi
   hipLaunchKernelGGL(finalize_film_kernel, dim3(ceil_div(B * L * H, 256)), dim3(256), 0, st, a.sums, P.layer_bias, P.packed, B,
                      L, H, P.dfilm);
   if ((rc = cips3d_launch_status())) return rc;
-  return cips3d_nerf_bwd_camera_acc(&G, a.dptsn, a.dvd, a.ddnorm, P.dcam, st);      // (dcam: zeroed by the preparation launch)
+  return cips3d_nerf_bwd_camera_geo(&G, a.dptsn, a.dvd, a.ddnorm, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, 1, P.dcam,
+                                    st);                                            // (dcam: zeroed by the preparation launch)
 }

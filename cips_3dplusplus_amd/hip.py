@@ -1214,14 +1214,28 @@ def camera_params_bwd(locations, dextr, up=None):
     return dloc
 
 
+def _geo_upstreams(d_mask, d_xyz, xyz, B, R):
+    """The upstreams of the render's geometry maps as the kernels take them: d_mask [2,B,S,S] (planar: d mask[0], d depth), d_xyz
+    [B,3,S,S] and the forward's xyz [B,3,S,S] -> contiguous fp32 (d_mask [2,B,R] | None, d_xyz [B,3,R] | None, xyz | None)."""
+    if d_mask is not None and xyz is None:
+        raise ValueError("d_mask needs xyz, the forward's map: the depth channel is -|xyz|")
+    if d_mask is None and d_xyz is None:
+        return None, None, None
+    dm = None if d_mask is None else d_mask.float().reshape(2, B, R).contiguous()
+    dx = None if d_xyz is None else d_xyz.float().reshape(B, 3, R).contiguous()
+    return dm, dx, None if dm is None else xyz.detach().float().reshape(B, 3, R).contiguous()
+
+
 def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, film, layer_bias, img_size, n_samples,
-                  static_viewdirs, d_features, d_thumb, need_params=False):
+                  static_viewdirs, d_features, d_thumb, need_params=False, d_mask=None, d_xyz=None, xyz=None):
     """The materialised NeRF backward (see csrc/nerf_bwd.hip): returns (dfilm [B,L,2,H], dcam [B,3,4]) -- and, with
     need_params (`optim_render_params`, models/projector_v10.py:848-872), a dict of the gradients of the renderer's own
     weights: pts_linears.{l}.weight / .bias, views_linears.weight / .bias, rgb_linear.*, sigma_linear.*, sigmoid_beta
     (the gamma / beta heads get theirs from the FiLM table's backward).
 
-    net = SirenGenerator (weights), film [B,L,2,H], layer_bias [L,H]; d_features [B,H,S,S], d_thumb [B,3,S,S]."""
+    net = SirenGenerator (weights), film [B,L,2,H], layer_bias [L,H]; d_features [B,H,S,S], d_thumb [B,3,S,S].
+    d_mask [2,B,S,S] (d mask[0], d depth) and d_xyz [B,3,S,S]: the upstreams of the geometry maps, None = absent; d_mask needs
+    `xyz`, the forward's [B,3,S,S] map.  They enter the compositing backward and the camera chain -- no further launch."""
     lib = _lib.load()
     st = stream_ptr()
     dev = cam_poses.device
@@ -1285,10 +1299,15 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     # ---- compositing backward
     wts, Tb, dsdf, dcrgb, ddnorm = new(B, P), new(B, P), new(B, P), new(B, 3, P), new(B, R)
     dbeta_ray = new(B, R) if need_params else None
-    check(lib.cips3d_nerf_bwd_composite(gp, dev_ptr(sdf), dev_ptr(crgb), dev_ptr(g), dev_ptr(dth),
-                                        dev_ptr(sigmoid_beta, "sigmoid_beta", True),      # None: with_sdf = False
-                                        dev_ptr(wts), dev_ptr(Tb), dev_ptr(dsdf), dev_ptr(dcrgb), dev_ptr(ddnorm),
-                                        dev_ptr(dbeta_ray, "dbeta_ray", True), st), "cips3d_nerf_bwd_composite")
+    dm, dx, xm = _geo_upstreams(d_mask, d_xyz, xyz, B, R)
+    geo = dm is not None or dx is not None
+    wsum, wzsum = (new(B, R), new(B, R)) if geo else (None, None)
+    geo_ptrs = (dev_ptr(dm, "d_mask", True), dev_ptr(dx, "d_xyz", True), dev_ptr(xm, "xyz", True),
+                dev_ptr(wsum, "wsum", True), dev_ptr(wzsum, "wzsum", True))
+    check(lib.cips3d_nerf_bwd_composite_geo(gp, dev_ptr(sdf), dev_ptr(crgb), dev_ptr(g), dev_ptr(dth),
+                                            dev_ptr(sigmoid_beta, "sigmoid_beta", True),      # None: with_sdf = False
+                                            dev_ptr(wts), dev_ptr(Tb), dev_ptr(dsdf), dev_ptr(dcrgb), dev_ptr(ddnorm),
+                                            dev_ptr(dbeta_ray, "dbeta_ray", True), *geo_ptrs, st), "cips3d_nerf_bwd_composite_geo")
 
     # ---- gradients of the renderer's own weights (optional): the wide blocks W_l [H,H] on the split-fp16 weight-gradient
     # GEMM (contraction over the points), everything narrow -- biases, the first layer, the view-direction columns, the heads
@@ -1352,8 +1371,8 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     check(lib.cips3d_nerf_bwd_heads(dev_ptr(dpre), dev_ptr(w_first), 1, 3, None, 3, B, H, P, dev_ptr(dptsn), st),
           "cips3d_nerf_bwd_heads")
     dcam = new(B, 3, 4)
-    check(lib.cips3d_nerf_bwd_camera(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), dev_ptr(dcam), st),
-          "cips3d_nerf_bwd_camera")
+    check(lib.cips3d_nerf_bwd_camera_geo(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), *geo_ptrs, 0, dev_ptr(dcam), st),
+          "cips3d_nerf_bwd_camera_geo")
     if need_params:
         return dfilm, dcam, pg
     return dfilm, dcam
@@ -1389,10 +1408,10 @@ def nerf_forward_stash(B, img_size, n_samples, hidden, depth, device, n_chunks=N
 
 
 def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, film, layer_bias, packed, packed_t, img_size,
-                        n_samples, static_viewdirs, d_features, d_thumb, fwd=None):
+                        n_samples, static_viewdirs, d_features, d_thumb, fwd=None, d_mask=None, d_xyz=None, xyz=None):
     """The fused NeRF backward (csrc/nerf_bwd_fused.hip): returns (dfilm [B,L,2,H], dcam [B,3,4]); same contract as
-    nerf_backward.  `fwd` = the nerf_forward_stash buffers a differentiable forward filled: the forward is then not
-    recomputed."""
+    nerf_backward (d_mask / d_xyz / xyz included).  `fwd` = the nerf_forward_stash buffers a differentiable forward filled: the
+    forward is then not recomputed."""
     lib = _lib.load()
     dev = cam_poses.device
     B, H, D = cam_poses.shape[0], net.W, net.D
@@ -1422,6 +1441,8 @@ def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb
     p.d_features, p.d_thumb = dev_ptr(keep[6]), dev_ptr(keep[7])
     p.stash, p.scratch, p.dfilm, p.dcam = dev_ptr(stash), dev_ptr(scratch), dev_ptr(dfilm), dev_ptr(dcam)
     p.hidden, p.depth, p.n_chunks = H, D, n_chunks
+    geo = _geo_upstreams(d_mask, d_xyz, xyz, B, R)          # (held until the call is enqueued)
+    p.d_mask, p.d_xyz, p.xyz = (dev_ptr(t, "geometry upstream", True) for t in geo)
     check(lib.cips3d_nerf_bwd_fused(C.byref(p), stream_ptr()), "cips3d_nerf_bwd_fused")
     return dfilm, dcam
 

@@ -15,7 +15,9 @@ benchmarks.  The other terms of the step loss (:1164-1200) are knobs of `project
 defaults: `mask_background` (`mask_blend`, :1164-1167), `mse_weight` + `target_images` (:1176-1181) and `optim_noise_bufs` +
 `regularize_noise_weight` (`noise_regulariser`, :1183-1195); on the GPU the blend and the regulariser are one autograd node
 each (csrc/inversion_loss.hip).  `ssim_weight` + `target_images` is not the reference's: ssim_weight x mean (1 - SSIM), the
-Gaussian-window SSIM on continuous values as one more autograd node (`ssim_loss`, csrc/ssim_loss.hip).  `metrics_every` > 0 logs the PSNR and SSIM the reference charts (:1125-1139) and returns those of
+Gaussian-window SSIM on continuous values as one more autograd node (`ssim_loss`, csrc/ssim_loss.hip).  `silhouette_weight` +
+`target_masks` is not the reference's either: silhouette_weight x mean (mask - (1 - target_masks))^2 on the render's own mask map,
+whose gradient the NeRF backward takes in its compositing kernel (`silhouette_loss`; autograd.NerfRenderFn).  `metrics_every` > 0 logs the PSNR and SSIM the reference charts (:1125-1139) and returns those of
 the final re-render (:1229-1242, 1266-1279), computed on the device (metrics.MetricsLog, csrc/metrics.hip) and read once after the
 loop.  What is NOT here: `use_stat_loss` / `vgg16_relu`; LPIPS; Streamlit charts and videos.
 
@@ -168,6 +170,16 @@ def ssim_loss(rgb, target, weight, data_range=2.0):
     return weight * (1 - _ssim_gaussian_torch(rgb, target, data_range)[0]).mean()
 
 
+def silhouette_loss(mask, target_masks, weight):
+    """weight x mean (mask - (1 - target_masks))^2: fits the render's silhouette to a segmentation.  `mask` is the generator's
+    `ret["mask"]` [B,1,S,S] -- the weight of the last sample of every ray, i.e. the probability of the BACKGROUND
+    (nerf_utils.py:333-336) -- and `target_masks` the FOREGROUND segmentation in [0, 1] at the same resolution, a constant.
+    Differentiable with respect to `mask`, whose gradient the NeRF backward carries to the pose and the styles.  fp32 HIP tensors
+    go through the squared-difference node (autograd.SqDiffPairFn); a loop forms 1 - target_masks once and calls `_weighted_mse`
+    itself (project_wplus)."""
+    return _weighted_mse(mask, 1 - target_masks.detach(), weight)
+
+
 def perceptual_loss(net, target_images, rgb_weight=1.0, thumb_weight=1.0, img_size=1024):
     """rgb_weight sum (fea(rgb) - fea(target))^2 + thumb_weight sum (fea(thumb) - fea(target_thumb))^2 with `net` a
     perceptual.VGG16ConvLoss (projector_v10.py:1170-1174).  The target features -- of `target_images` [B,3,S,S] in [-1, 1] and of
@@ -247,13 +259,18 @@ class FlipProjector:
                       lr_decoder_params=0.005, lr_noise=0.001, truncation_psi=1.0, flip_w_decoder_every=10,
                       azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
                       mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0, lpips_metric=None,
-                      ssim_weight=0.0):
+                      ssim_weight=0.0, silhouette_weight=0.0, target_masks=None):
         """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
         `mask_background`: from the appearance phase on, the image's gradient only flows where the render's foreground mask says
         so (mask_blend; the thumbnail is not blended, as in the reference).  `mse_weight` > 0 adds mse_weight x
         F.mse_loss(image, target_images) (projector_v10.py:1176-1181).  `ssim_weight` > 0 (needs `target_images`) adds
         ssim_weight x mean (1 - SSIM) of the same image -- after the mask blending -- against target_images (`ssim_loss`:
         Gaussian window, continuous values), between the MSE term and the regulariser; 0: nothing new runs.
+        `silhouette_weight` > 0 (needs `target_masks`, the foreground segmentation [bs_cam, 1, S, S] in [0, 1] at the render's
+        resolution S = cam_cfg["img_size"]; resizing is the caller's preprocessing, as for target_images) adds
+        silhouette_weight x mean (mask - (1 - target_masks))^2 of the render's mask map (`silhouette_loss`) in both phases, after
+        the SSIM term and before the regulariser: the term that moves the pose where the perceptual loss is flat in azimuth.  Its
+        gradient enters the NeRF backward's compositing kernel (no further launch there).  0: nothing new runs.
         `metrics_every` > 0 (needs `target_images`): PSNR and SSIM (metrics.py: scikit-image's defaults on 8-bit images) of view 0
         of the generator's image, before the mask blending, against target_images[0], at the steps with step % metrics_every == 0
         and at the last one (the reference's logging condition, :1125-1139) -- two launches per logged step, no copy and no
@@ -268,6 +285,15 @@ class FlipProjector:
             raise ValueError("project_wplus: mse_weight > 0 needs target_images")
         if ssim_weight > 0 and target_images is None:
             raise ValueError("project_wplus: ssim_weight > 0 needs target_images")
+        bg_target = None
+        if silhouette_weight > 0:
+            if target_masks is None:
+                raise ValueError("project_wplus: silhouette_weight > 0 needs target_masks")
+            want = (bs_cam, 1, cam_cfg["img_size"], cam_cfg["img_size"])
+            if not torch.is_tensor(target_masks) or tuple(target_masks.shape) != want:
+                raise ValueError(f"project_wplus: target_masks must be a tensor of shape {list(want)} (the render's resolution), got "
+                                 f"{list(target_masks.shape) if torch.is_tensor(target_masks) else type(target_masks).__name__}")
+            bg_target = (1 - target_masks.detach().to(self.device, torch.float32)).contiguous()      # formed once
         metrics_log = None
         if metrics_every < 0 or int(metrics_every) != metrics_every:
             raise ValueError(f"project_wplus: metrics_every must be a non-negative integer, got {metrics_every}")
@@ -337,6 +363,8 @@ class FlipProjector:
                 loss = loss + _weighted_mse(rgb, target_images, mse_weight)
             if ssim_weight > 0:
                 loss = loss + ssim_loss(rgb, target_images, ssim_weight)
+            if silhouette_weight > 0:
+                loss = loss + _weighted_mse(mask, bg_target, silhouette_weight)
             if optim_noise_bufs and regularize_noise_weight > 0:
                 loss = loss + noise_regulariser(noise_bufs, regularize_noise_weight)
             for o in opts:

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 40  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 41  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1070,7 +1070,17 @@ int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* geom, const float* sdf
                               const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch, float* dsdf,
                               float* dcrgb, float* ddnorm, float* dbeta_ray, void* stream);
 /* (dbeta_ray [B,R] or NULL: per-ray d loss / d sigmoid_beta, for `optim_render_params`, models/projector_v10.py:848-872)
- * out[row][c] += sum_{b,p} a[b][row][p] * x[b][c][p mod Px] (c < nx <= 3), out[row][3] += sum_{b,p} a[b][row][p]; a [B,rows,P],
+ * The same with the upstreams of the geometry maps of Render.volume_integration (cips3d/nerf_utils.py:329-336: xyz = sum_k w_k p_k,
+ * mask[0] = w_{N-1}, mask[1] = depth = -|xyz|): d_mask [2,B,R] (planar: d mask[0], then d depth) and d_xyz [B,3,R], each may be
+ * NULL; xyz [B,3,R] is the forward's map (needed with d_mask: d depth acts as -d_depth * xyz / |xyz| on xyz, 0 where |xyz| == 0).
+ * With xbar the effective adjoint of xyz, d loss / d w_k gains <xbar, p_k> + [k == N-1] d mask[0], p_k = o + z_k d in world
+ * units; the per-ray sums wsum = sum_k w_k and wzsum = sum_k w_k z_k [B,R] (written when d_mask or d_xyz is set) carry the direct
+ * path through the points to cips3d_nerf_bwd_camera_geo.  Both NULL: exactly cips3d_nerf_bwd_composite. */
+int cips3d_nerf_bwd_composite_geo(const cips3d_nerf_bwd_geom* geom, const float* sdf, const float* crgb, const float* g,
+                                  const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch, float* dsdf,
+                                  float* dcrgb, float* ddnorm, float* dbeta_ray, const float* d_mask, const float* d_xyz,
+                                  const float* xyz, float* wsum, float* wzsum, void* stream);
+/* out[row][c] += sum_{b,p} a[b][row][p] * x[b][c][p mod Px] (c < nx <= 3), out[row][3] += sum_{b,p} a[b][row][p]; a [B,rows,P],
  * x [B,nx,Px], out [rows,4] zeroed by the caller: the narrow weight gradients and the biases of the point MLP. */
 int cips3d_nerf_bwd_row_dots(const float* a, const float* x, int nx, int64_t Px, float* out, int B, int rows, int64_t P,
                              void* stream);
@@ -1088,6 +1098,11 @@ int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* geom, const float* dptsn,
 /* the same, ADDED to a dcam the caller has zeroed (cips3d_nerf_bwd_fused clears it in its preparation launch) */
 int cips3d_nerf_bwd_camera_acc(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
                                float* dcam, void* stream);
+/* the two above with the direct path of the geometry maps: d o += wsum xbar, d d += wzsum xbar per ray (d_mask, d_xyz, xyz, wsum,
+ * wzsum as in cips3d_nerf_bwd_composite_geo; d_mask and d_xyz both NULL: none).  accumulate != 0: dcam is added to. */
+int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
+                               const float* d_mask, const float* d_xyz, const float* xyz, const float* wsum, const float* wzsum,
+                               int accumulate, float* dcam, void* stream);
 /* ---- NeRF half, fused backward (csrc/nerf_bwd_fused.hip): the same gradients as the sequence above -- d loss / d film
  * [B,L,2,H] and d loss / d cam_poses [B,3,4] from d_features [B,H,R] and d_thumb [B,3,R] -- with the point MLP kept in the
  * register file in both directions (the reference gets them from autograd through cips3d/volume_renderer.py:39-160 and
@@ -1129,6 +1144,10 @@ typedef struct cips3d_nerf_bwd_fused_params {
    * only g = <d_features, feature> is then rebuilt, from the view layer's stash. */
   const float* fwd_sdf;      /* [B,P] */
   const float* fwd_crgb;     /* [B,3,P] */
+  /* upstreams of the mask / depth and xyz maps (cips3d_nerf_bwd_composite_geo); each may be NULL, xyz is needed with d_mask */
+  const float* d_mask;       /* [2,B,R] */
+  const float* d_xyz;        /* [B,3,R] */
+  const float* xyz;          /* [B,3,R]: the forward's map */
 } cips3d_nerf_bwd_fused_params;
 
 /* 1 when the fused kernels cover the shape (hidden 32/64/128/256, R % 16 == 0, tables within the LDS) */

@@ -3,7 +3,7 @@
     python tools/bench_inversion.py [--depth 6] [--steps 200] [--res 256] [--loss surrogate|vgg16_conv_random]
                                      [--vgg-precision fp32_exact|split_fp16]
                                      [--optim-noise-bufs] [--mask-background] [--mse-weight W] [--metrics-every K]
-                                     [--lpips random] [--ssim-weight W]
+                                     [--lpips random] [--ssim-weight W] [--silhouette-weight W]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
@@ -20,7 +20,10 @@ expressions of the first two instead of the HIP nodes (A/B).  With none of the t
 --lpips random: LPIPS against the target is reported too (project_wplus's `lpips_metric`: a perceptual.LPIPS('vgg_random') of
 --vgg-precision; logged beside PSNR / SSIM with --metrics-every); the JSON line gains the final re-render's "lpips".
 --ssim-weight W: W x mean (1 - SSIM) against the target images is added (project_wplus's `ssim_weight`: the Gaussian-window
-SSIM node of csrc/ssim_loss.hip; CIPS3D_FUSED_SSIM=0 runs its torch expression instead, A/B).  0: the run is what it was."""
+SSIM node of csrc/ssim_loss.hip; CIPS3D_FUSED_SSIM=0 runs its torch expression instead, A/B).  0: the run is what it was.
+--silhouette-weight W: W x mean (mask - (1 - target_masks))^2 of the render's mask map is added (project_wplus's
+`silhouette_weight`); the target is the same generator's foreground (1 - mask) rendered once at another pose (azimuth +-0.35,
+mean latent).  Its gradient goes through the mask map into the NeRF backward.  0: the run is what it was."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -42,6 +45,7 @@ ap.add_argument("--mse-weight", type=float, default=0.0)
 ap.add_argument("--metrics-every", type=int, default=0)
 ap.add_argument("--lpips", choices=("random",), default=None)
 ap.add_argument("--ssim-weight", type=float, default=0.0)
+ap.add_argument("--silhouette-weight", type=float, default=0.0)
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -77,6 +81,18 @@ if a.ssim_weight > 0:
     from cips_3dplusplus_amd import projector as _P
     extra.update(ssim_weight=a.ssim_weight, target_images=t_rgb)
     knobs["ssim_weight"], knobs["fused_ssim"] = a.ssim_weight, _P.FUSED_SSIM
+if a.silhouette_weight > 0:
+    from cips_3dplusplus_amd.camera import Camera
+    with torch.no_grad():
+        mr, md = G.get_mean_latent(2000, dev)
+        e, f, n, fa, _ = Camera.generate_camera_params(64, dev, locations=torch.tensor([[0.35, 0.0], [-0.35, 0.0]], device=dev),
+                                                       fov_ang=cam_cfg["fov_ang"], dist_radius=cam_cfg["dist_radius"])
+        t = G(zs=[None, None], style_render=mr.reshape(1, 1, -1).repeat(2, G.N_layers_renderer + 1, 1),
+              style_decoder=md.reshape(1, 1, -1).repeat(2, G.decoder.n_latent, 1), cam_poses=e, focals=f, img_size=64, near=n,
+              far=fa, nerf_cfg=ncfg)
+        t_masks = (1 - t["mask"]).clone()
+    extra.update(silhouette_weight=a.silhouette_weight, target_masks=t_masks)
+    knobs["silhouette_weight"] = a.silhouette_weight
 if a.metrics_every > 0:
     extra.update(metrics_every=a.metrics_every, target_images=t_rgb)
     knobs["metrics_every"] = a.metrics_every
@@ -90,7 +106,7 @@ if a.mask_background:                   # the blend runs from the appearance pha
     extra.update(mask_background=True)
     knobs["mask_background"] = True
     n_pose, n_app = 0, a.steps + a.app_steps
-if set(knobs) - {"metrics_every", "lpips", "ssim_weight", "fused_ssim"}:
+if set(knobs) - {"metrics_every", "lpips", "ssim_weight", "fused_ssim", "silhouette_weight"}:
     from cips_3dplusplus_amd import projector as _P
     knobs["fused_noise_reg"], knobs["fused_mask_blend"] = _P.FUSED_NOISE_REG, _P.FUSED_MASK_BLEND
 out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=n_pose, N_steps_app=n_app,
