@@ -48,6 +48,9 @@ class LinearFn(Function):
 
 
 def linear(x, W, bias=None, w_scale=1.0, b_scale=1.0, lrelu=False, act_gain=1.0, out_scale=1.0, out_shift=0.0):
+    if lrelu and (out_shift != 0.0 or out_scale <= 0.0 or act_gain <= 0.0):
+        # cips3d_linear_bwd takes the slope from the sign of the forward's OUTPUT, which is the pre-activation's only then
+        raise ValueError("autograd.linear: lrelu with out_shift != 0, out_scale <= 0 or act_gain <= 0 has no backward here")
     return LinearFn.apply(x, W, bias, float(w_scale), float(b_scale), bool(lrelu), float(act_gain), float(out_scale),
                           float(out_shift))
 

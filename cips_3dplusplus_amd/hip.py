@@ -110,6 +110,8 @@ def linear(x, W, bias=None, out=None, w_scale=1.0, b_scale=1.0, pixelnorm=False,
     out_dim = W.shape[0]
     if out is None:
         out = torch.empty(B, out_dim, device=x.device, dtype=torch.float32)
+    if B == 0:           # (an empty tensor has no address to hand over; the entry point launches nothing for B = 0 either)
+        return out
     check(lib.cips3d_linear(dev_ptr(x, "x"), x.stride(0), dev_ptr(W, "W"), dev_ptr(bias, "bias", True), dev_ptr(out, "out"),
                             out.stride(0), B, in_dim, out_dim, w_scale, b_scale, int(pixelnorm), int(lrelu), act_gain,
                             out_scale, out_shift, dev_ptr(trunc_mean, "trunc_mean", True), trunc_psi, out_repeat, out_repeat_stride,
@@ -270,10 +272,20 @@ class LinearTable:
 
     def backward(self, B, out_base, dy_base, x_base, dx_base=None, need_dW=True, need_db=True):
         """Gradients of every head (cips3d_linear_table_bwd).  dy_base / dx_base mirror the forward's out / x buffers
-        (dx_base is accumulated into: zero it first).  Returns (dW_flat, w_offsets (python list), db_flat)."""
+        (dx_base is accumulated into: zero it first).  Returns (dW_flat, w_offsets (python list), db_flat).
+        The kernels read x and write dW in 16-byte pieces and find a row's head with one ballot: a table they cannot take
+        (a head whose in_dim or x_stride is no multiple of 4 or whose x is not 16-byte aligned, more than 64 heads) is
+        refused here, before any launch."""
+        if len(self._descs) > 64:
+            raise RuntimeError(f"LinearTable.backward: {len(self._descs)} heads, the table backward takes at most 64")
+        for i, d in enumerate(self._descs):
+            if d.in_dim % 4 != 0 or d.x_stride % 4 != 0 or (d.x or 0) % 16 != 0:
+                raise RuntimeError(f"LinearTable.backward: head {i} (in_dim {d.in_dim}, x_stride {d.x_stride}, x at byte "
+                                   f"{(d.x or 0) % 16} of a 16-byte line): in_dim and x_stride must be multiples of 4 and x 16-byte aligned")
         if self._dev is None:
             self._upload()
-        in_dim = self._descs[0].in_dim
+        # the widest head sizes the columns kernel's grid (cips3d_linear_table_bwd's in_dim); every head loops over its own
+        in_dim = max(d.in_dim for d in self._descs)
         offs, off = [], 0
         for d in self._descs:
             offs.append(off)

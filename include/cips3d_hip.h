@@ -115,7 +115,9 @@ int cips3d_linear_table(const cips3d_linear_desc* table_dev, int n_desc, int tot
  *                                            the caller zeroes dx; NULL = not wanted
  *   dW flat, head i at dW + w_offsets[i] ([out_dim, in_dim]; w_offsets = device array of int64 element offsets); NULL = not wanted
  *   db flat [total_rows] (rows of heads without bias receive their value all the same); NULL = not wanted
- * Every head must have the same in_dim (% 4 == 0). */
+ * in_dim: the LARGEST in_dim of the table (it sizes the grid over input columns; every head loops over its own).  The table lives
+ * on the device, so what the kernels need of every head is the caller's to check before the call (hip.LinearTable.backward
+ * does): in_dim % 4 == 0, x_stride % 4 == 0, x 16-byte aligned -- x is read and dW written in 16-byte pieces; n_desc <= 64. */
 int cips3d_linear_table_bwd(const cips3d_linear_desc* table_dev, int n_desc, int total_rows, int in_dim, int B,
                             const float* out_base, const float* dy_base, const float* x_base, float* dx_base,
                             const int64_t* w_offsets_dev, float* dW, float* db, void* stream);
