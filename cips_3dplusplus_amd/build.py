@@ -19,8 +19,8 @@ LIB = os.path.join(PKG, "libcips3d_hip.so")
 ARCH = "gfx950"
 SOURCES = ["bias_act.hip", "upfirdn2d.hip", "linear.hip", "camera.hip", "nerf.hip", "nerf_sdf_grad.hip", "nerf_normals.hip", "decoder.hip", "chain.hip", "conv3x3.hip", "forward.hip", "backward.hip", "decoder_grad.hip", "nerf_bwd.hip", "nerf_bwd_fused.hip", "render_ops.hip", "rng.hip", "optim.hip", "mesh.hip", "mesh_raster.hip", "vgg.hip", "vgg_split.hip", "inversion_loss.hip", "metrics.hip", "lpips.hip", "ssim_loss.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall",
-         "-Wno-unused-function", "-fno-gpu-rdc", "-fgpu-flush-denormals-to-zero" if False else ""]
-FLAGS = [f for f in FLAGS if f] + os.environ.get("CIPS3D_HIPCC_FLAGS", "").split()
+         "-Wno-unused-function", "-fno-gpu-rdc"]
+FLAGS = FLAGS + os.environ.get("CIPS3D_HIPCC_FLAGS", "").split()
 
 
 def hipcc():
@@ -39,8 +39,8 @@ def source_hash():
     import hashlib
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
     files += [os.path.join(os.path.dirname(PKG), "include", "cips3d_hip.h"), os.path.abspath(__file__)]
-    # (per-file flags included: a knob that only changes those -- CIPS3D_CHAIN_SLP -- must invalidate the library too; a probe of
-    # round 4 compared two "builds" that were the same file because it did not)
+    # (per-file flags included: a change that only touches those must invalidate the library too; a probe of round 4 compared two
+    # "builds" that were the same file because it did not)
     h = hashlib.sha256((" ".join(FLAGS) + " | " + repr(sorted(FILE_FLAGS.items()))).encode())
     for f in files:
         if os.path.exists(f):
@@ -63,8 +63,7 @@ def up_to_date():
 # asm as well, and tests/test_host.py checks the kernel's assembly for the form
 # metrics.hip: its fp32 window arithmetic is promised bit-identical run to run; SLP packed it into v_pk_mul_f32 / v_pk_add_f32 too, so
 # it is built without SLP vectorisation as well; lpips.hip promises the same of its per-pixel fp32 sums, ssim_loss.hip of its windows
-FILE_FLAGS = {"chain.hip": [] if os.environ.get("CIPS3D_CHAIN_SLP") == "1" else ["-fno-slp-vectorize"],
-              "metrics.hip": ["-fno-slp-vectorize"], "lpips.hip": ["-fno-slp-vectorize"],
+FILE_FLAGS = {"chain.hip": ["-fno-slp-vectorize"], "metrics.hip": ["-fno-slp-vectorize"], "lpips.hip": ["-fno-slp-vectorize"],
               "ssim_loss.hip": ["-fno-slp-vectorize"]}
 
 

@@ -55,15 +55,7 @@
 // out (asm v_fmac_f32 in the epilogue: 0 of 59 repeats differ, with or without SLP), so correctness does not hang on a
 // compiler flag; build.py still compiles this file with -fno-slp-vectorize (no other packed-fp32 arithmetic in the planes
 // kernels either; no measurable cost), and tests/test_gpu_bf16_storage.py repeats the folds bit for bit.
-#include <stdlib.h>
 #include "common.h"
-
-#ifndef CIPS3D_FOLD_PK
-#define CIPS3D_FOLD_PK 0
-#endif
-#ifndef CIPS3D_FOLD_NOP
-#define CIPS3D_FOLD_NOP 0
-#endif
 
 namespace {
 
@@ -238,19 +230,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   float lc0 = 0.f, lc1 = 0.f;                // the layer's bound constants (planes output)
   float pin = 0.f;                           // this lane's entries of the input's patch maxima (planes output)
   // a planes output under range tracking: the exponent follows from max|in| of this pixel block and the layer's constants
-#ifndef CIPS3D_CHAIN_AB
-#define CIPS3D_CHAIN_AB 0        // timing-only ablations: 1 no range work at all, 2 no patch-maxima store, 3 no patch-maxima load
-#endif
-  const bool track = CIPS3D_CHAIN_AB != 1 && NP == 2 && a.out_fmt == 1 && a.lconst;
+  const bool track = NP == 2 && a.out_fmt == 1 && a.lconst;
   // The epilogue's operands are REQUESTED here (pure loads into registers, right behind the first stage's LDS-DMA) and only
   // turned into what the epilogue needs after the main loop (finish_ops).  Round 5: in the old form -- loads and their arithmetic
   // interleaved -- `a.x_exp ? a.x_exp[..] : a.x_exp_const` became ONE flat load of a selected address (array or kernarg word), a
   // flat load's result needs vmcnt(0), and that wait sat in front of every other operand load: the whole first stage had to land
   // before the remaining ~5 dependent round trips (bound constants, patch maxima, noise, bias, ToRGB rows) even started --
   // 1-2 us per launch in front of the main loop.
-#ifndef CIPS3D_CHAIN_LATE_OPS
-#define CIPS3D_CHAIN_LATE_OPS 1     // 0: finish_ops right behind issue_ops, as before round 5 (A/B)
-#endif
   int e_raw = 0;
   f32x4 lc_raw = {0.f, 0.f, 0.f, 0.f};
   auto issue_ops = [&]() {
@@ -264,7 +250,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
       if (track) {
         const float* lc = a.lconst + b * 4;
         lc_raw = f32x4{lc[0], lc[1], lc[2], 0.f};
-        if (a.x_pmax && CIPS3D_CHAIN_AB != 3) {      // the 2 x Cin/16 patch maxima of this pixel block are contiguous: one load per wave (Cin <= 512)
+        if (a.x_pmax) {      // the 2 x Cin/16 patch maxima of this pixel block are contiguous: one load per wave (Cin <= 512)
           const int n_half = (HW + 63) / 64, per = K >> 4;
           const int n_ent = (2 * (int)blockIdx.x + 1 < n_half ? 2 : 1) * per;
           const float* pp = a.x_pmax + ((int64_t)b * n_half + 2 * blockIdx.x) * per;
@@ -299,7 +285,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
       if (track) {
         lc0 = lc_raw[0];
         lc1 = fmaxf(lc_raw[1], 1.41421356237309515f * lc_raw[2]);
-        if (a.x_pmax && CIPS3D_CHAIN_AB != 3) {
+        if (a.x_pmax) {
           const int n_half = (HW + 63) / 64, per = K >> 4;
           const int n_ent = (2 * (int)blockIdx.x + 1 < n_half ? 2 : 1) * per;
           const float* pp = a.x_pmax + ((int64_t)b * n_half + 2 * blockIdx.x) * per;
@@ -313,10 +299,6 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
         }
       }
     }
-  };
-  auto load_ops = [&]() {
-    issue_ops();
-    if (!CIPS3D_CHAIN_LATE_OPS) finish_ops();
   };
   f32x4 acc[WM][4];
 #pragma unroll
@@ -341,11 +323,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   static_assert(NS >= 2 && (NS - 2) * PW <= 63, "counted vmcnt");
   // (NS = 2: the operand loads ride BEHIND the first stage's DMA -- the loop's first wait is vmcnt(0) anyway, and in front
   // of it they delayed the first stage: 0.367 -> 0.384 ms per forward; deeper rings: in front, older than every counted stage)
-  if (NS > 2) load_ops();
+  if (NS > 2) issue_ops();
 #pragma unroll
   for (int s0 = 0; s0 < NS - 1; ++s0)
     if (s0 < nstage) stage_load(s0);
-  if (NS == 2) load_ops();
+  if (NS == 2) issue_ops();
 
 #ifdef CIPS3D_CHAIN_STAMPS
   unsigned long long ph_[4] = {0, 0, 0, 0}, tp_ = __builtin_amdgcn_s_memtime();
@@ -424,7 +406,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   }
 
   CSTAMP(2);                         // main loop
-  if (CIPS3D_CHAIN_LATE_OPS) finish_ops();
+  finish_ops();
   if (track) {
     // max|in| of the pixel block from the lanes' entries (wave-uniform, no LDS), the bound, the exponent, its powers of two
     const float m_in = cips3d_wave_max_uniform(pin);
@@ -433,9 +415,6 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
     kback = cips3d_uniform(cips3d_pow2(e));
     if (blockIdx.y == 0 && tid == 0) a.out_exp[b * ((HW + BN - 1) / BN) + blockIdx.x] = e;
   }
-#if CIPS3D_FOLD_PK && (CIPS3D_FOLD_NOP & 4)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // probe: every load of this wave -- the epilogue's operands -- has returned
-#endif
   // ---- epilogue.  D layout: acc[i][c][r] = out[o = obase + 4 q + r][pixel npx[c]]
   // (one accumulator set per 16-row tile: the ToRGB slots are sums of FOUR tiles in a fixed order whatever the workgroup's height --
   // a 128-row workgroup writes two 64-row slots that hold the same bits two 64-row workgroups would have written)
@@ -464,76 +443,15 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
       }
       // (columns past HW repeat the last pixel without its noise: a value the patch maximum may include -- it only has to bound)
       mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fmaxf(fabsf(v[2]), fabsf(v[3])), mx));
-#if CIPS3D_FOLD_PK == 3
-      // probe (tools/pk_fold_probe.sh, round 5): EXACTLY the four instruction forms hipcc's SLP build emits for one column (read
-      // off its assembly: profiles/r05_slp_fold_isa.md) -- r = 0: v_pk_fma_f32 D, W, V01, 0 op_sel_hi:[1,0,0] (fresh accumulator,
-      // inline constant 0, broadcast of the pair's low register); r = 1: ... V01 ... op_sel:[0,1,0] (broadcast of the pair's HIGH
-      // register); r = 2, 3: op_sel_hi:[1,0,1] -- round 4's hand-written probe covered only the last form.  CIPS3D_FOLD_FORMS
-      // masks which of the first two are used (bit 0: r = 0, bit 1: r = 1); a cleared bit falls back to the last form.
-#ifndef CIPS3D_FOLD_FORMS
-#define CIPS3D_FOLD_FORMS 3
-#endif
       if (a.rgb_part) {
-        typedef float f32x2_t __attribute__((ext_vector_type(2)));
-        f32x2_t p12 = {prgb[i][1][c], prgb[i][2][c]};
-        const f32x2_t v01 = {v[0], v[1]}, v23 = {v[2], v[3]}, v1x = {v[1], 0.f}, v3x = {v[3], 0.f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(prgb[i][0][c]) : "v"(wrgb[i][0][r]), "v"(v[r]));
-        const f32x2_t w0 = {wrgb[i][1][0], wrgb[i][2][0]}, w1 = {wrgb[i][1][1], wrgb[i][2][1]}, w2 = {wrgb[i][1][2], wrgb[i][2][2]},
-                      w3 = {wrgb[i][1][3], wrgb[i][2][3]};
-        if ((CIPS3D_FOLD_FORMS & 1) && i == 0) {
-          // (the compiler's first instruction starts the accumulator: prgb is zero before the first row tile)
-          asm volatile("v_pk_fma_f32 %0, %1, %2, 0 op_sel_hi:[1,0,0]" : "=v"(p12) : "v"(w0), "v"(v01));
-        } else {
-          asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(p12) : "v"(w0), "v"(v01));
-        }
-        if (CIPS3D_FOLD_FORMS & 2) asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0]" : "+v"(p12) : "v"(w1), "v"(v01));
-        else asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(p12) : "v"(w1), "v"(v1x));
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(p12) : "v"(w2), "v"(v23));
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(p12) : "v"(w3), "v"(v3x));
-        prgb[i][1][c] = p12[0];
-        prgb[i][2][c] = p12[1];
-      }
-#elif CIPS3D_FOLD_PK == 2
-      // probe (tools/pk_fold_probe.sh): the SLP build's instruction pattern written by hand -- channel 0 as v_fmac_f32, channels
-      // 1 / 2 as ONE register pair per product assembled by two v_mov_b32 into fixed registers and consumed by v_pk_fma_f32 with
-      // an op_sel_hi broadcast of v[r] -- with CIPS3D_FOLD_NOP wait states between the v_movs and the packed instruction
-      if (a.rgb_part) {
-        typedef float f32x2_t __attribute__((ext_vector_type(2)));
-        f32x2_t p12 = {prgb[i][1][c], prgb[i][2][c]};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(prgb[i][0][c]) : "v"(wrgb[i][0][r]), "v"(v[r]));
-          const f32x2_t vb = {v[r], 0.f};
-          asm volatile("v_mov_b32 v126, %1\n\tv_mov_b32 v127, %2\n\t"
-                       ".if %4 > 0\n\ts_nop %4 - 1\n\t.endif\n\t"
-                       "v_pk_fma_f32 %0, v[126:127], %3, %0 op_sel_hi:[1,0,1]"
-                       : "+v"(p12) : "v"(wrgb[i][1][r]), "v"(wrgb[i][2][r]), "v"(vb), "n"(CIPS3D_FOLD_NOP) : "v126", "v127");
-        }
-        prgb[i][1][c] = p12[0];
-        prgb[i][2][c] = p12[1];
-      }
-#else
-      if (a.rgb_part) {
-#if CIPS3D_FOLD_PK && (CIPS3D_FOLD_NOP & 2)
-        asm volatile("s_nop 7\n\ts_nop 7");          // probe: distance between the producers of v[] and the packed chain
-#endif
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             // one v_fmac_f32 per product, written out: nothing can pair the channel-1 / channel-2 accumulations into
             // v_pk_fma_f32 (see the build note in the header of this file; VALU results feed VALU here: no hazard state to keep)
-#if CIPS3D_FOLD_PK        /* reproducer builds only (tools/pk_fold_probe.sh): the C form SLP packs */
-            prgb[i][ch][c] = fmaf(wrgb[i][ch][r], v[r], prgb[i][ch][c]);
-#else
             asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(prgb[i][ch][c]) : "v"(wrgb[i][ch][r]), "v"(v[r]));
-#endif
-#if CIPS3D_FOLD_PK && (CIPS3D_FOLD_NOP & 1)
-        asm volatile("s_nop 7\n\ts_nop 7");          // probe: distance between the packed chain and whatever follows it
-#endif
       }
-#endif
       if (npx[c] < HW) {
         if (a.out_fmt == 1) {
           // planes: channels obase + 4 q + r live in channel block (obase >> 3) + (q >> 1), elements 4 (q & 1) + r
@@ -588,7 +506,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
     atomicAdd(&g_chain_stamps[6], ph_[2]);
   }
 #endif
-  if (CIPS3D_CHAIN_AB != 1 && CIPS3D_CHAIN_AB != 2 && a.out_pmax && n0 + wn_i * 64 < HW) {
+  if (a.out_pmax && n0 + wn_i * 64 < HW) {
     // this wave's patch (16 WM channels x 64 pixels): its largest |out|, one plain store per 16 channels
     static_assert(BN == 64 * WGN, "a wave column = one 64-pixel half block");
     const float m = cips3d_wave_max_uniform(mx * kback);
@@ -600,10 +518,6 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
     if (tid == 0) cips3d_amax_raise_if(a.out_amax + b * CIPS3D_AMAX_FLOATS, m, blockIdx.y * gridDim.x + blockIdx.x);
   }
   if (!a.rgb_part) return;
-#if CIPS3D_FOLD_PK && (CIPS3D_FOLD_NOP & 8)
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // probe: nothing of this wave in flight, then everybody here
-  __syncthreads();
-#endif
   // ---- folded ToRGB partial of this workgroup's BM rows: over the 4 lane quarters by shuffles, over the WGM wave rows
   // through LDS (every wave passed the last stage's lgkmcnt(0) and meets at the barrier below)
 #pragma unroll
@@ -794,7 +708,6 @@ extern "C" int cips3d_modconv1x1_planes16(const void* x_planes16, const float* w
                                           const float* noise_w, const float* bias, const float* rgb_w, float* rgb_part,
                                           int* n_row_blocks, const cips3d_range* rg, void* stream) {
   if ((rgb_w == nullptr) != (rgb_part == nullptr)) return CIPS3D_E_BADARG;
-  static const int cfg = getenv("CIPS3D_CHAIN16_CFG") ? atoi(getenv("CIPS3D_CHAIN16_CFG")) : 0;   // A/B knob
   if (n_row_blocks) *n_row_blocks = Cout > 0 ? Cout / 64 : 0;
   if (!x_planes16 || !wm || !out || B < 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return CIPS3D_E_BADARG;
   if ((out_format != 0 && out_format != 2 && out_format != 3) || (epilogue != 0 && epilogue != 1) || (epilogue == 1 && !bias))
@@ -809,9 +722,7 @@ extern "C" int cips3d_modconv1x1_planes16(const void* x_planes16, const float* w
   // at 64^2): batch 1 7.45 us / batch 4 17.4 us; a 2-slot ring 8.0 / 17.5; 128-deep stages 7.4 / 24.2 (one workgroup per CU);
   // 128 x 128 tiles (2/3 of the operand bytes per flop) 9.6 / 19.8; 64 x 64 tiles 7.5 / 19.9.
   dim3 grid((unsigned)ceil_div<int64_t>(HW, 128), (unsigned)(Cout / 64), (unsigned)B);
-  if (cfg == 1) hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 2, 1>), grid, dim3(512), 0, as_stream(stream), a);
-  else if (cfg == 2) hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 128, 2, 1>), grid, dim3(512), 0, as_stream(stream), a);
-  else hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 3, 1>), grid, dim3(512), 0, as_stream(stream), a);
+  hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 3, 1>), grid, dim3(512), 0, as_stream(stream), a);
   return cips3d_launch_status();
 }
 
@@ -854,13 +765,10 @@ extern "C" int cips3d_modconv1x1_planes(const void* x_planes, const float* wm, v
     return cips3d_launch_status();
   }
   dim3 grid((unsigned)ceil_div<int64_t>(HW, 128), (unsigned)(Cout / 64) + (a.ride.part ? 1u : 0u), (unsigned)B);
-  static const int cfg = getenv("CIPS3D_CHAIN_CFG") ? atoi(getenv("CIPS3D_CHAIN_CFG")) : 0;     // A/B knob (ring depth / stage size)
   // (Round 3, measured and not kept: 128 x 128 tiles -- 2/3 of the operand bytes per flop through the L2 -> LDS path, 256
   // workgroups -- 16.3 us per 512 -> 512 layer against 12.2: twice the MFMAs and fragment reads per wave at the same one
   // workgroup per CU; 32 x 128 tiles / four waves for the 512 -> 256 exit, whose 64 x 128 grid covers half the CUs: 10.4 against
   // 10.0 us.)
-  if (cfg == 1) hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 3>), grid, dim3(512), 0, as_stream(stream), a);
-  else if (cfg == 2) hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 32, 4>), grid, dim3(512), 0, as_stream(stream), a);
-  else hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 2>), grid, dim3(512), 0, as_stream(stream), a);
+  hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 2>), grid, dim3(512), 0, as_stream(stream), a);
   return cips3d_launch_status();
 }

@@ -42,10 +42,6 @@ int cips3d_linear_table_zero(const cips3d_linear_desc* table_dev, int n_desc, in
 // to the compiler: its loads and stores become flat_ instructions, which count on lgkmcnt as well as vmcnt and may return
 // out of order with respect to both -- every wait behind one is a wait for everything.  (Kernel-argument pointers are
 // known to be global already.)
-#ifdef CIPS3D_NO_GLOBAL_CAST      /* A/B knob: leave them generic */
-template <typename T> __device__ static inline const T* cips3d_g(const T* p) { return p; }
-template <typename T> __device__ static inline T* cips3d_g(T* p) { return p; }
-#else
 template <typename T>
 __device__ static inline const __attribute__((address_space(1))) T* cips3d_g(const T* p) {
   return (const __attribute__((address_space(1))) T*)p;
@@ -54,7 +50,6 @@ template <typename T>
 __device__ static inline __attribute__((address_space(1))) T* cips3d_g(T* p) {
   return (__attribute__((address_space(1))) T*)p;
 }
-#endif
 
 // floor division for possibly negative numerators (b > 0)
 __host__ __device__ static inline int floor_div_i(int a, int b) {
@@ -104,34 +99,10 @@ __device__ static inline float sin_accurate(float x) {
   return __int_as_float(__float_as_int(y) ^ (ki << 31));
 }
 
-// sin(x) on the hardware sine: exact two-constant Cody-Waite reduction by 2 pi (k * 2PI_HI is absorbed by the FMA, 2PI_LO
-// restores the bits it lacks), then v_sin_f32 on r / (2 pi) in [-0.5, 0.5].  6 VALU slots instead of ~15; max error 3.9e-7,
-// mean 5.5e-8 over |x| <= 1e3 (tools/sin_probe.py; sin_accurate: 1.2e-7 / 1.6e-8).  In the FiLM-SIREN network the error of a
-// layer's output is dominated by gamma (~30) times the fp32 rounding of its pre-activation (~1e-6), so the renderer's
-// distance to an fp64 evaluation does not move (tests/test_gpu_split_fp16.py).
-__device__ static inline float sin_hw(float x) {
-  const float INV_2PI = 0.159154943091895336f;
-  const float TWO_PI_HI = 6.28318548202514648f;        // float(2 pi)
-  const float TWO_PI_LO = -1.74845553146951715e-7f;    // 2 pi - TWO_PI_HI
-  const float k = rintf(x * INV_2PI);
-  float r = fmaf(k, -TWO_PI_HI, x);
-  r = fmaf(k, -TWO_PI_LO, r);
-  return __builtin_amdgcn_sinf(r * INV_2PI);
-}
-// cos(x), same reduction, v_cos_f32 (the FiLM-sine derivative of the fused NeRF backward)
-__device__ static inline float cos_hw(float x) {
-  const float INV_2PI = 0.159154943091895336f;
-  const float TWO_PI_HI = 6.28318548202514648f;
-  const float TWO_PI_LO = -1.74845553146951715e-7f;
-  const float k = rintf(x * INV_2PI);
-  float r = fmaf(k, -TWO_PI_HI, x);
-  r = fmaf(k, -TWO_PI_LO, r);
-  return __builtin_amdgcn_cosf(r * INV_2PI);
-}
-// sin(x) / cos(x) without a reduction of our own (the default since round 2): t = x / (2 pi) in revolutions, v_fract_f32
-// (exact) takes it into [0, 1), v_sin_f32 / v_cos_f32 evaluate there -- 3 VALU slots + the quarter-rate instruction instead
-// of 6 + it (render kernel 87.1 -> 81.9 us with sin_hw_direct's two, same box).  What it adds to the argument is the
-// rounding of the product t (half an ulp of t: 3e-6 rad for |x| in [50, 100], 1.5e-6 in [25, 50]) -- the size of the
+// sin(x) / cos(x) without a reduction of our own: t = x / (2 pi) in revolutions, v_fract_f32 (exact) takes it into [0, 1),
+// v_sin_f32 / v_cos_f32 evaluate there -- 3 VALU slots + the quarter-rate instruction instead of the 6 + it of an exact
+// Cody-Waite reduction by 2 pi in front of the hardware sine (render kernel 87.1 -> 81.9 us, same box).
+// What it adds to the argument is the rounding of the product t (half an ulp of t: 3e-6 rad for |x| in [50, 100], 1.5e-6 in [25, 50]) -- the size of the
 // rounding the reference's own fp32 evaluation of gamma * pre + beta makes twice.  Measured on the D = 8 renderer against
 // fp64: features 5.93e-5 with it, 5.80e-5 with the exact reduction, 5.84e-5 for the fp32 oracle itself
 // (tests/test_gpu_split_fp16.py::test_split_nerf_is_as_accurate_as_fp32).  The fract keeps every magnitude inside the
@@ -142,19 +113,10 @@ __device__ static inline float sin_hw_direct(float x) {
 __device__ static inline float cos_hw_direct(float x) {
   return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(x * 0.159154943091895336f));
 }
-// sin(2 pi t): the argument already in revolutions (render kernel with CIPS3D_FILM_REVOLUTIONS: 1 / 2 pi folded into the
-// staged FiLM table)
+// sin(2 pi t): the argument already in revolutions (render kernel: 1 / 2 pi folded into the staged FiLM table, nerf_mlp.h)
 __device__ static inline float sin_revolutions(float t) { return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(t)); }
-#ifdef CIPS3D_EXACT_SINE
-#define cips3d_sin sin_accurate
-#define cips3d_cos cosf
-#elif defined(CIPS3D_REDUCED_SINE)
-#define cips3d_sin sin_hw
-#define cips3d_cos cos_hw
-#else
 #define cips3d_sin sin_hw_direct
 #define cips3d_cos cos_hw_direct
-#endif
 
 // Split-fp16: x = hi + lo with hi = fp16(x), lo = fp16(x - hi) (22 significant bits; see nerf.hip / decoder.hip / chain.hip).
 // `x` is made opaque first: hipcc otherwise folds a multiplication that produced x into the conversion (v_fma_mixlo_f16:
@@ -228,9 +190,6 @@ __device__ static inline float wave_max(float v) {
 // sixteen loads are then scalar loads (no vector register, no vmcnt slot -- the counted waits of the GEMM rings do not see
 // them) and the scale factors derived from the result live in SGPRs through the kernel.
 __device__ static inline float cips3d_amax_load(const float* __restrict__ slots) {
-#ifdef CIPS3D_RANGE_NO_LOAD      // timing-only ablation
-  return 1.f;
-#endif
   float m = slots[0];
 #pragma unroll
   for (int s_ = 1; s_ < CIPS3D_AMAX_SLOTS; ++s_) m = fmaxf(m, slots[s_ * CIPS3D_AMAX_STRIDE]);
@@ -240,40 +199,25 @@ __device__ static inline float cips3d_amax_load(const float* __restrict__ slots)
 // next launch; a tensor that the NEXT launch reads (on all eight XCDs) can go to memory while the kernel still runs instead: an
 // agent-scope relaxed atomic store is a plain store with the sc1 bit (LLVM's gfx942+ memory model), the line stays valid in this
 // L2.  Measured on the 64^2 chain (9 planes outputs of 8.4 MB per view): -5.6 us per view, same-box, three interleaved rounds
-// (DESIGN.md 5.2); non-temporal stores: no change.  CIPS3D_WT_STORES=0 compiles every helper to the plain store (A/B).
-#ifndef CIPS3D_WT_STORES
-#define CIPS3D_WT_STORES 1
-#endif
+// (DESIGN.md 5.2); non-temporal stores: no change.
 __device__ static inline void cips3d_store_wt(float* p, float v) {
-#if CIPS3D_WT_STORES
   typedef __attribute__((address_space(1))) float gf32_t;
   __hip_atomic_store(reinterpret_cast<gf32_t*>(reinterpret_cast<uintptr_t>(p)), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *p = v;
-#endif
 }
 template <class T8>
 __device__ static inline void cips3d_store_wt8(void* p, T8 v) {        // any 8-byte value (four halfs, two words)
   static_assert(sizeof(T8) == 8, "8-byte payload");
-#if CIPS3D_WT_STORES
   typedef __attribute__((address_space(1))) unsigned long long gu64_t;
   __hip_atomic_store(reinterpret_cast<gu64_t*>(reinterpret_cast<uintptr_t>(p)), __builtin_bit_cast(unsigned long long, v),
                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *reinterpret_cast<T8*>(p) = v;
-#endif
 }
 template <class T16>
 __device__ static inline void cips3d_store_wt16(void* p, T16 v) {      // any 16-byte value; p 16-byte aligned
   static_assert(sizeof(T16) == 16, "16-byte payload");
-#if CIPS3D_WT_STORES
   typedef float f32x4_t_ __attribute__((ext_vector_type(4)));
   // (no 16-byte atomic store exists: the instruction written out.  The trailing s_nop 1 covers the store-data hazard the compiler
   // pads for its own stores -- a VALU write of the data registers right behind a > 64-bit store)
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(__builtin_bit_cast(f32x4_t_, v)) : "memory");
-#else
-  *reinterpret_cast<T16*>(p) = v;
-#endif
 }
 
 __device__ static inline float cips3d_uniform(float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); }
@@ -320,17 +264,11 @@ __device__ static inline float cips3d_wave_max_uniform(float v) { return cips3d_
 // `seen`: what cips3d_amax_peek returned for this slot some time ago (0: always raise).  The slot only ever grows, so a
 // workgroup whose maximum does not exceed a value the slot already held has nothing to tell it.
 __device__ static inline void cips3d_amax_raise_if(float* __restrict__ slots, float m, int slot, float seen = 0.f) {
-#ifdef CIPS3D_RANGE_NO_RECORD    // timing-only ablation
-  return;
-#endif
   if (!(m <= seen)) cips3d_amax_raise(slots, m, slot);          // (a NaN maximum is recorded too)
 }
 // the slot's value as the device sees it now (an agent-scope load: served past this XCD's L2 copy); a stale answer only costs
 // an atomic that was not needed
 __device__ static inline float cips3d_amax_peek(const float* __restrict__ slots, int slot) {
-#ifdef CIPS3D_RANGE_NO_PEEK
-  return 0.f;
-#endif
   return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(slots) + (slot & (CIPS3D_AMAX_SLOTS - 1)) * CIPS3D_AMAX_STRIDE,
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }

@@ -13,7 +13,6 @@
 // Rooflines: 64^2 / 128^2 stages are MFMA-bound (2*Cin*Cout flop per pixel against (Cin+Cout)*4 B);
 // >= 256^2 stages, the FIR up-sampler and ToRGB are HBM-bound: every kernel reads its input once and
 // writes its output once with >= 128-byte row segments.
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -62,11 +61,7 @@ __device__ __forceinline__ f32x4 split_mfma16(f32x4 afrag, h4 bh, h4 bl, f32x4 c
   return __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bh, c, 0, 0, 0);
 }
 
-#ifdef CIPS3D_FUSED_NO_MFMA     // timing-only ablation (tools/): what the fused stages would cost with free matrix work
-__device__ __forceinline__ f32x4 fused_mfma(float a, float b, f32x4 c) { c[0] += a * b; return c; }
-#else
 __device__ __forceinline__ f32x4 fused_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-#endif
 
 // Split-fp16 GEMM mode (CIPS3D_GEMM_SPLIT): fp32-equivalent products at the fp16 matrix rate.  Every operand is the
 // unevaluated sum of two fp16 numbers, x = hi + lo (hi = fp16(x), lo = fp16(x - hi): 22 significant bits in the 4 bytes
@@ -1166,15 +1161,6 @@ struct FusedArgs {
 
 // MINW = waves per SIMD the register allocation must leave room for (the per-workgroup chain load -> FIR -> LDS -> MFMA ->
 // store is serial, so throughput comes from co-resident workgroups).
-#ifndef CIPS3D_C128_LATE
-#define CIPS3D_C128_LATE true
-#endif
-#ifndef CIPS3D_C64_MINW
-#define CIPS3D_C64_MINW 4
-#endif
-#ifndef CIPS3D_C32_MINW
-#define CIPS3D_C32_MINW 8      // A/B knob: waves per SIMD the C = 32 stage is compiled for
-#endif
 #ifndef CIPS3D_FUSED_AB
 // timing-only ablations of the fused stages (results garbage; tools/README.md): 1 no scale loads, 2 no y_next record, 4 no ToRGB
 // sums (at C = 32, where nothing else reads conv2's output, the compiler then drops conv2 altogether: read that one as "no
@@ -1249,14 +1235,10 @@ __global__ void __launch_bounds__(64 * WGM * WGN, MINW) fused_up_conv_kernel(Fus
   // scale factors of the split operands (cips3d_range); set right before the first patch_store below
   float kact1 = 1.41421356237309515f, k2in = kSplitInv, kact2 = 1.41421356237309515f, kback2 = 1.f, kyn = kSplitInv;
 
-#ifndef CIPS3D_FUSED_TILE_DMA
-#define CIPS3D_FUSED_TILE_DMA 1      // 0: the noise tile and the ToRGB rows go through registers behind the range block, as before round 5 (A/B)
-#endif
-  constexpr bool TILE_DMA = CIPS3D_FUSED_TILE_DMA != 0;
-  float nw1_u = 0.f;                        // NoiseInjection.weight of conv1 (TILE_DMA: applied where the tile is read)
+  float nw1_u = 0.f;                        // NoiseInjection.weight of conv1 (applied where the tile is read)
   // the layer's range constants (uniform addresses: scalar loads -- as long as they are read in FRONT of the LDS-DMA below)
   float c10_u = 0.f, c11_u = 0.f, c20_u = 0.f, c21a_u = 0.f, c21b_u = 0.f;
-  if constexpr (SPLIT && TILE_DMA) {
+  if constexpr (SPLIT) {
     if (a.x_amax && !(CIPS3D_FUSED_AB & 1)) {
       const float* l1 = a.lconst1 + b * 4;
       c10_u = l1[0]; c11_u = l1[1];
@@ -1317,13 +1299,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, MINW) fused_up_conv_kernel(Fus
   // st + 2 are requested at the START of stage st and filtered at the END of stage st + 1 -- two stages of lead.  With one
   // stage of lead (the form C = 64 keeps) a stage lasted as long as a patch round trip: in-kernel stamps (tools/
   // fused_stamps.py) showed 5.6k cycles per stage at C = 256 for 1.5k cycles of matrix work.
-#ifndef CIPS3D_FUSED_DEEP
-#define CIPS3D_FUSED_DEEP 1      // A/B knob
-#endif
-#ifndef CIPS3D_DEEP_MIN_C
-#define CIPS3D_DEEP_MIN_C 256
-#endif
-  constexpr bool DEEP = CIPS3D_FUSED_DEEP && NSTAGE >= 3 && C >= CIPS3D_DEEP_MIN_C && (C != 128);   // same-box A/B: C = 256 24.4 -> 22.9 us; C = 128 (252 VGPRs with it) 25.2 -> 25.5: off there
+  constexpr bool DEEP = NSTAGE >= 3 && C >= 256;   // same-box A/B: C = 256 24.4 -> 22.9 us; C = 128 (252 VGPRs with it) 25.2 -> 25.5: off there
   float pv[BPT][3][4], pw[BPT][3][4];
   auto patch_load_into = [&](int st, float (&pset)[BPT][3][4]) {
 #pragma unroll
@@ -1399,42 +1375,30 @@ __global__ void __launch_bounds__(64 * WGM * WGN, MINW) fused_up_conv_kernel(Fus
   // today every row's load is waited for before its middle pair is copied to an even register pair -- 39.1 / 32.9 / 25.1 / 23.1 us
   // for C = 32 / 64 / 128 / 256 against 37.3 / 32.3 / 23.3 / 21.5: the co-resident workgroups cover those waits, the quads cost
   // registers and copies in the K loop.)
-#ifndef CIPS3D_FUSED_PATCH_FIRST
-#define CIPS3D_FUSED_PATCH_FIRST 1
-#endif
-  constexpr bool PATCH_FIRST = CIPS3D_FUSED_PATCH_FIRST && TILE_DMA;
-  if constexpr (PATCH_FIRST) {
-    patch_load(0);
-    if (DEEP) patch_load_into(1, pw);          // stage s's patches live in set s & 1 (pv: even, pw: odd)
-  }
-  if constexpr (TILE_DMA) {
-    const bool have_nz = a.noise1 && a.nw1 && !(CIPS3D_FUSED_AB & 128);
-    if (have_nz) nw1_u = a.nw1[0];
-    if (wave == 0) {                        // BN / 4 <= 64 lanes (BN = 128 in every instantiation): one wave's worth of 16-byte pieces
-      static_assert(BN / 4 <= 64 && (3 * C) % 4 == 0, "one LDS-DMA instruction per tile");
-      if (lane < BN / 4) {
-        if (have_nz) {
-          const int r = lane / (TW / 4), x4 = lane % (TW / 4);
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.noise1 + (int64_t)b * a.nbs1 + ((oy0 + r) * OW + ox0 + x4 * 4)),
-                                           (__attribute__((address_space(3))) void*)s_nz1, 16, 0, 0);
-        } else {
-          *reinterpret_cast<f32x4*>(s_nz1 + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+  patch_load(0);
+  if (DEEP) patch_load_into(1, pw);          // stage s's patches live in set s & 1 (pv: even, pw: odd)
+  const bool have_nz = a.noise1 && a.nw1 && !(CIPS3D_FUSED_AB & 128);
+  if (have_nz) nw1_u = a.nw1[0];
+  if (wave == 0) {                        // BN / 4 <= 64 lanes (BN = 128 in every instantiation): one wave's worth of 16-byte pieces
+    static_assert(BN / 4 <= 64 && (3 * C) % 4 == 0, "one LDS-DMA instruction per tile");
+    if (lane < BN / 4) {
+      if (have_nz) {
+        const int r = lane / (TW / 4), x4 = lane % (TW / 4);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.noise1 + (int64_t)b * a.nbs1 + ((oy0 + r) * OW + ox0 + x4 * 4)),
+                                         (__attribute__((address_space(3))) void*)s_nz1, 16, 0, 0);
+      } else {
+        *reinterpret_cast<f32x4*>(s_nz1 + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
-    if (a.wm_rgb) {                         // 3 C floats = 3 C / 4 pieces of 16 bytes, 64 per wave-instruction
+  }
+  if (a.wm_rgb) {                         // 3 C floats = 3 C / 4 pieces of 16 bytes, 64 per wave-instruction
 #pragma unroll
-      for (int p0 = 0; p0 < 3 * C / 4; p0 += 64 * WGM * WGN) {
-        const int pbase = p0 + wave * 64;   // (wave-uniform LDS base: the hardware adds lane * 16)
-        if (pbase < 3 * C / 4 && pbase + lane < 3 * C / 4)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.wm_rgb + (int64_t)b * 3 * C + (pbase + lane) * 4),
-                                           (__attribute__((address_space(3))) void*)(s_wrgb + pbase * 4), 16, 0, 0);
-      }
+    for (int p0 = 0; p0 < 3 * C / 4; p0 += 64 * WGM * WGN) {
+      const int pbase = p0 + wave * 64;   // (wave-uniform LDS base: the hardware adds lane * 16)
+      if (pbase < 3 * C / 4 && pbase + lane < 3 * C / 4)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.wm_rgb + (int64_t)b * 3 * C + (pbase + lane) * 4),
+                                         (__attribute__((address_space(3))) void*)(s_wrgb + pbase * 4), 16, 0, 0);
     }
-  }
-  if constexpr (!PATCH_FIRST) {
-    patch_load(0);
-    if (DEEP) patch_load_into(1, pw);          // stage s's patches live in set s & 1 (pv: even, pw: odd)
   }
 
   // Range of the split operands (cips3d_range, common.h).  act1 is split as act1 2^-e1, e1 from the bound
@@ -1448,19 +1412,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, MINW) fused_up_conv_kernel(Fus
   if constexpr (SPLIT) {
     if (a.x_amax && wave == 0 && !(CIPS3D_FUSED_AB & 1)) {
       const float t = lane < CIPS3D_AMAX_SLOTS ? a.x_amax[b * CIPS3D_AMAX_FLOATS + lane * CIPS3D_AMAX_STRIDE] : 0.f;
-      float c10, c11, c20 = 0.f, c21 = 0.f;
-      if constexpr (TILE_DMA) {
-        c10 = c10_u; c11 = c11_u;
-        if (NEXT) { c20 = c20_u; c21 = fmaxf(c21a_u, 1.41421356237309515f * c21b_u); }
-      } else {
-        const float* l1 = a.lconst1 + b * 4;            // (uniform addresses: scalar loads)
-        c10 = l1[0]; c11 = l1[1];
-        if (NEXT) {
-          const float* l2 = a.lconst2 + b * 4;
-          c20 = l2[0];
-          c21 = fmaxf(l2[1], 1.41421356237309515f * l2[2]);
-        }
-      }
+      float c10 = c10_u, c11 = c11_u, c20 = 0.f, c21 = 0.f;
+      if (NEXT) { c20 = c20_u; c21 = fmaxf(c21a_u, 1.41421356237309515f * c21b_u); }
       // (FLAT: x_amax is the maximum of conv1's GEMM RESULT -- what the FIR's gain multiplies in the up-sampling form; the row
       // gain of a plain StyledConv's constants is relative to that conv's INPUT)
       if (FLAT) c11 = 1.41421356237309515f;
@@ -1479,22 +1432,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, MINW) fused_up_conv_kernel(Fus
       if (lane == 0) *reinterpret_cast<f32x4*>(s_nz1 + BN) = sc;
     }
   }
-  // noise of the first conv for this tile, ToRGB weights (TILE_DMA: on their way since the top of the kernel)
-  if constexpr (TILE_DMA) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): this wave's LDS-DMA pieces (and, needed right behind the barrier anyway, its patches)
-  } else {
-  if (a.noise1 && a.nw1 && !(CIPS3D_FUSED_AB & 128)) nw1_u = a.nw1[0];
-  if (tid < BN / 4) {
-    const int r = tid / (TW / 4), x4 = tid % (TW / 4);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (a.noise1 && a.nw1 && !(CIPS3D_FUSED_AB & 128)) {
-      v = *reinterpret_cast<const f32x4*>(a.noise1 + (int64_t)b * a.nbs1 + ((oy0 + r) * OW + ox0 + x4 * 4));
-    }
-    *reinterpret_cast<f32x4*>(s_nz1 + r * TW + x4 * 4) = v;
-  }
-  if (a.wm_rgb)
-    for (int i = tid; i < 3 * C; i += NT) s_wrgb[i] = a.wm_rgb[(int64_t)b * 3 * C + i];
-  }
+  // noise of the first conv for this tile, ToRGB weights: on their way since the top of the kernel
+  __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): this wave's LDS-DMA pieces (and, needed right behind the barrier anyway, its patches)
   __syncthreads();
 
   f32x4 acc[WM][4];
@@ -2013,12 +1952,53 @@ extern "C" int cips3d_modconv1x1(const float* x, const float* wm, float* out, in
                                  nullptr, nullptr, rg, stream);
 }
 
-// rows per workgroup of the tile configuration cips3d_modconv1x1 picks for this Cout (= row blocks of the ToRGB partials)
-static int gemm_block_rows(int Cout) {
-  if (Cout >= 256 && Cout % 64 == 0) return 64;
-  if (Cout == 128) return 128;
-  if (Cout == 64) return 64;
-  return 32;
+// The tile of a 1x1 GEMM launch, forward (cips3d_modconv1x1_torgb) or activation-backward (cips3d_modconv1x1_actbwd):
+// BM = 16 WM WGM rows (= one row block of the ToRGB partials) x BN = 64 WGN pixels, K stages of BK in a ring of NS slots.
+struct GemmTile { int WM, WGM, WGN, BK, NS; };
+
+// small_grid_allowed: the forward GEMM without a ToRGB fold only (the fold's slots are 64 rows or more at these widths)
+static GemmTile gemm_tile(int B, int Cin, int Cout, int64_t HW, bool small_grid_allowed) {
+  if (Cout >= 256 && Cout % 64 == 0) {
+    // 64 x 128 tiles, 8 waves.  A grid that covers at most half of the 256 CUs (the 512 -> 256 low-res GEMM at 64^2: 128 tiles)
+    // runs on 32 x 128 tiles of 4 waves instead
+    const int64_t tiles = B > 0 && HW > 0 ? (int64_t)B * (Cout / 64) * ceil_div<int64_t>(HW, 128) : 0;
+    if (small_grid_allowed && tiles <= 128) return {1, 2, 2, 32, 4};
+    // 64-deep stages (half as many stage barriers: 705.9 -> 703.4 us per 1024^2 view, A/B on one box) when K allows
+    // ... for a grid of at most ONE workgroup per CU (the 64^2 layers of a single view: 256 tiles).  A larger grid (batch 2 and
+    // up: the inversion step) whose shape does not admit the 128-row tile below runs 32-deep stages in a 48 KB ring instead: two
+    // workgroups share a CU and one's prologue / epilogue -- a third of a launch, with the L2 port idle -- runs under the other's
+    // K loop (inversion step +3.4 %, same box)
+    if (tiles <= 256 && Cin % 64 == 0) return {1, 4, 2, 64, 2};
+    // a grid of more than one 64 x 128 tile per CU (batch 2 and up: the inversion step): 128 x 128 tiles, 64-deep stages -- half
+    // the operand bytes per flop through the L2 port and one workgroup per CU again; the ToRGB partials then come in 128-row
+    // blocks.  Inversion step, same box x3: 341.6-343.2 -> 348.8-349.4 steps/s with this form in the forward and the data-gradient
+    // GEMM (32-deep in 3 / 4 slots: 347.1-348.7 / 346.9-347.7)
+    if (tiles > 256 && Cout % 128 == 0 && Cin % 64 == 0) return {2, 4, 2, 64, 2};
+    return {1, 4, 2, 32, 2};
+  }
+  // Short contractions (K <= 128: the decoder's 128 / 64 / 32-channel layers at 256^2 and above) are HBM-bound streams with
+  // two to four K stages: a 2-slot ring (half the LDS) lets a second workgroup share the CU and cover the first one's
+  // epilogue loads and stores
+  const int ns = Cin <= 128 && Cout < 256 ? 2 : 4;
+  if (Cout == 128) return {1, 8, 1, 32, ns};      // all 128 rows: x read once
+  if (Cout == 64) return {1, 4, 2, 32, ns};       // 64 x 128
+  return {1, 2, 2, 32, ns};                       // 32 x 128 (any Cout % 32 == 0)
+}
+
+static int launch_gemm_tile(const GemmTile& t, bool actbwd, const GemmArgs& a, hipStream_t st) {
+#define GEMM_TILE_CASE(wm, wgm, wgn, bk, ns)                                                    \
+  if (t.WM == wm && t.WGM == wgm && t.WGN == wgn && t.BK == bk && t.NS == ns)                   \
+    return actbwd ? launch_gemm_actbwd<wm, wgm, wgn, bk, ns>(a, st) : launch_gemm<wm, wgm, wgn, bk, ns>(a, st);
+  GEMM_TILE_CASE(1, 2, 2, 32, 4)
+  GEMM_TILE_CASE(1, 4, 2, 64, 2)
+  GEMM_TILE_CASE(2, 4, 2, 64, 2)
+  GEMM_TILE_CASE(1, 4, 2, 32, 2)
+  GEMM_TILE_CASE(1, 8, 1, 32, 2)
+  GEMM_TILE_CASE(1, 2, 2, 32, 2)
+  GEMM_TILE_CASE(1, 8, 1, 32, 4)
+  GEMM_TILE_CASE(1, 4, 2, 32, 4)
+#undef GEMM_TILE_CASE
+  return CIPS3D_E_UNSUPP;      // (not reached: gemm_tile names only the tiles above)
 }
 
 extern "C" int cips3d_modconv1x1_torgb(const float* x, const float* wm, float* out, int B, int Cin, int Cout, int64_t HW,
@@ -2026,11 +2006,8 @@ extern "C" int cips3d_modconv1x1_torgb(const float* x, const float* wm, float* o
                                        const float* bias, const float* rgb_w, float* rgb_part, int* n_row_blocks,
                                        const cips3d_range* rg, void* stream) {
   if ((rgb_w == nullptr) != (rgb_part == nullptr)) return CIPS3D_E_BADARG;
-  // 128-row tiles for a grid of more than one 64 x 128 tile per CU (see below); the ToRGB partials then come in 128-row blocks
-  static const int big_tiles = getenv("CIPS3D_GEMM_BIG") ? atoi(getenv("CIPS3D_GEMM_BIG")) : 1;
-  const bool big = big_tiles && Cout >= 256 && Cout % 128 == 0 && Cin % 64 == 0 && HW > 0 && B > 0 &&
-                   (int64_t)B * (Cout / 64) * ceil_div<int64_t>(HW, 128) > 256;
-  if (n_row_blocks) *n_row_blocks = Cout > 0 ? Cout / (big ? 128 : gemm_block_rows(Cout)) : 0;
+  const GemmTile tile = gemm_tile(B, Cin, Cout, HW, !rgb_part);
+  if (n_row_blocks) *n_row_blocks = Cout > 0 ? Cout / (16 * tile.WM * tile.WGM) : 0;
   if (!x || !wm || !out || B < 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return CIPS3D_E_BADARG;
   if ((epilogue & CIPS3D_GEMM_BF16) && (epilogue & CIPS3D_GEMM_SPLIT)) return CIPS3D_E_BADARG;
   const int bf16 = (epilogue & CIPS3D_GEMM_BF16) ? 1 : (epilogue & CIPS3D_GEMM_SPLIT) ? 2 : 0;
@@ -2043,52 +2020,7 @@ extern "C" int cips3d_modconv1x1_torgb(const float* x, const float* wm, float* o
   if (B == 0) return 0;
   GemmArgs a{x, wm, out, B, Cin, Cout, HW, epilogue, noise, noise_bstride, noise_w, bias, bf16, out_bf16, rgb_w, rgb_part,
              rg ? rg->x_amax : nullptr, rg ? rg->out_amax : nullptr, cips3d_actbwd{}};
-  hipStream_t st = as_stream(stream);
-  static const int dbg_cfg = getenv("CIPS3D_GEMM_CFG") ? atoi(getenv("CIPS3D_GEMM_CFG")) : 0;   // tuning knob (tools/)
-  if (dbg_cfg && !rgb_part && Cout % 128 == 0) {      // (the ToRGB fold needs the default tiling: gemm_block_rows)
-    switch (dbg_cfg) {
-      case 1: return launch_gemm<2, 2, 2, 32, 4>(a, st);    // 64 x 128, 4 waves
-      case 2: return launch_gemm<1, 4, 2, 32, 4>(a, st);    // 64 x 128, 8 waves
-      case 3: return launch_gemm<2, 4, 2, 32, 3>(a, st);    // 128 x 128, 8 waves
-      case 4: return launch_gemm<1, 4, 2, 32, 2>(a, st);    // 64 x 128, 8 waves, 1 stage in flight
-      case 5: return launch_gemm<2, 2, 4, 32, 3>(a, st);    // 64 x 256, 8 waves
-      case 6: return launch_gemm<1, 8, 1, 32, 4>(a, st);    // 128 x 64, 8 waves
-      case 7: return launch_gemm<1, 2, 2, 32, 4>(a, st);    // 32 x 128, 4 waves
-      case 8: return launch_gemm<2, 4, 1, 32, 2>(a, st);    // 128 x 64, 8 waves, 8 accumulator chains per wave
-      case 9: return launch_gemm<2, 4, 1, 32, 3>(a, st);
-      case 10: return launch_gemm<2, 2, 2, 32, 2>(a, st);   // 64 x 128, 4 waves, 8 chains
-    }
-  }
-  if (Cout >= 256 && Cout % 64 == 0) {
-    // 64 x 128 tiles.  A grid that covers at most half of the 256 CUs (the 512 -> 256 low-res GEMM at 64^2: 128 tiles)
-    // runs on smaller tiles instead; not for the ToRGB fold, whose slot count follows gemm_block_rows()
-    static const int small_cfg = getenv("CIPS3D_GEMM_SMALL") ? atoi(getenv("CIPS3D_GEMM_SMALL")) : 1;
-    if (!rgb_part && small_cfg && (int64_t)B * (Cout / 64) * ceil_div<int64_t>(HW, 128) <= 128) {
-      if (small_cfg == 1) return launch_gemm<1, 2, 2, 32, 4>(a, st);    // 32 x 128, 4 waves
-      if (small_cfg == 2) return launch_gemm<1, 4, 1, 32, 4>(a, st);    // 64 x 64, 4 waves
-    }
-    // 8 waves; 64-deep stages (half as many stage barriers: 705.9 -> 703.4 us per 1024^2 view, A/B on one box) when K allows
-    // ... for a grid of at most ONE workgroup per CU (the 64^2 layers of a single view: 256 tiles).  A larger grid (batch 2 and
-    // up: the inversion step) runs 32-deep stages in a 48 KB ring instead: two workgroups share a CU and one's prologue /
-    // epilogue -- a third of a launch, with the L2 port idle -- runs under the other's K loop (inversion step +3.4 %, same box)
-    static const int bk = getenv("CIPS3D_GEMM_BK") ? atoi(getenv("CIPS3D_GEMM_BK")) : 0;       // tuning knob (tools/): 32 | 64
-    const bool one_round = (int64_t)B * (Cout / 64) * ceil_div<int64_t>(HW, 128) <= 256;
-    if (!big && (bk ? bk == 64 : one_round) && Cin % 64 == 0) return launch_gemm<1, 4, 2, 64, 2>(a, st);
-    // a grid of more than one 64 x 128 tile per CU (batch 2 and up: the inversion step): 128 x 128 tiles, 64-deep stages -- half
-    // the operand bytes per flop through the L2 port and one workgroup per CU again.  Inversion step, same box x3: 341.6-343.2 ->
-    // 348.8-349.4 steps/s with this form in the forward and the data-gradient GEMM (32-deep in 3 / 4 slots: 347.1-348.7 / 346.9-347.7)
-    if (big) return launch_gemm<2, 4, 2, 64, 2>(a, st);
-    return launch_gemm<1, 4, 2, 32, 2>(a, st);
-  }
-  static const int ns2 = getenv("CIPS3D_GEMM_NS2") ? atoi(getenv("CIPS3D_GEMM_NS2")) : 1;     // (see cips3d_modconv1x1_actbwd)
-  if (ns2 && Cin <= 128) {      // (same rows per workgroup as the 4-slot forms: the ToRGB fold's slot count does not change)
-    if (Cout == 128) return launch_gemm<1, 8, 1, 32, 2>(a, st);
-    if (Cout == 64) return launch_gemm<1, 4, 2, 32, 2>(a, st);
-    if (Cout < 256) return launch_gemm<1, 2, 2, 32, 2>(a, st);
-  }
-  if (Cout == 128) return launch_gemm<1, 8, 1, 32, 4>(a, st);                     // all 128 rows: x read once
-  if (Cout == 64) return launch_gemm<1, 4, 2, 32, 4>(a, st);                      // 64 x 128
-  return launch_gemm<1, 2, 2, 32, 4>(a, st);                                      // 32 x 128 (any Cout % 32 == 0)
+  return launch_gemm_tile(tile, false, a, as_stream(stream));
 }
 
 extern "C" int cips3d_modconv1x1_actbwd(const float* g, const float* wm_t, float* dpre, int B, int Cin, int Cout, int64_t HW,
@@ -2104,28 +2036,7 @@ extern "C" int cips3d_modconv1x1_actbwd(const float* g, const float* wm_t, float
   if (B == 0) return 0;
   GemmArgs a{g, wm_t, dpre, B, Cin, Cout, HW, 0, noise, noise_bstride, nullptr, nullptr, (flags & CIPS3D_GEMM_SPLIT) ? 2 : 0, 0,
              nullptr, nullptr, rg ? rg->x_amax : nullptr, rg ? rg->out_amax : nullptr, *ab};
-  hipStream_t st = as_stream(stream);
-  if (Cout >= 256 && Cout % 64 == 0) {
-    // (as cips3d_modconv1x1: 64-deep stages for a grid of at most one workgroup per CU, else the 48 KB ring and two per CU)
-    static const int bk = getenv("CIPS3D_GEMM_BK") ? atoi(getenv("CIPS3D_GEMM_BK")) : 0;       // tuning knob (tools/): 32 | 64
-    const bool one_round = (int64_t)B * (Cout / 64) * ceil_div<int64_t>(HW, 128) <= 256;
-    if ((bk ? bk == 64 : one_round) && Cin % 64 == 0) return launch_gemm_actbwd<1, 4, 2, 64, 2>(a, st);
-    static const int big_tiles = getenv("CIPS3D_GEMM_BIG") ? atoi(getenv("CIPS3D_GEMM_BIG")) : 1;      // (see cips3d_modconv1x1_torgb)
-    if (big_tiles && Cout % 128 == 0 && Cin % 64 == 0) return launch_gemm_actbwd<2, 4, 2, 64, 2>(a, st);
-    return launch_gemm_actbwd<1, 4, 2, 32, 2>(a, st);
-  }
-  // Short contractions (K <= 128: the decoder's 128 / 64 / 32-channel layers at 256^2 and above) are HBM-bound streams with
-  // two to four K stages: a 2-slot ring (half the LDS) lets a second workgroup share the CU and cover the first one's
-  // epilogue loads and stores
-  static const int ns2 = getenv("CIPS3D_GEMM_NS2") ? atoi(getenv("CIPS3D_GEMM_NS2")) : 1;
-  if (ns2 && Cin <= 128) {
-    if (Cout == 128) return launch_gemm_actbwd<1, 8, 1, 32, 2>(a, st);
-    if (Cout == 64) return launch_gemm_actbwd<1, 4, 2, 32, 2>(a, st);
-    if (Cout < 256) return launch_gemm_actbwd<1, 2, 2, 32, 2>(a, st);
-  }
-  if (Cout == 128) return launch_gemm_actbwd<1, 8, 1, 32, 4>(a, st);
-  if (Cout == 64) return launch_gemm_actbwd<1, 4, 2, 32, 4>(a, st);
-  return launch_gemm_actbwd<1, 2, 2, 32, 4>(a, st);
+  return launch_gemm_tile(gemm_tile(B, Cin, Cout, HW, false), true, a, as_stream(stream));
 }
 
 extern "C" int cips3d_up2_fir_act(const float* y_lo, const float* fir, float* out, int B, int C, int H, int W,
@@ -2209,8 +2120,8 @@ extern "C" int cips3d_fused_up_conv_next(const float* y_lo, const float* fir, co
     // with the partials added through LDS (C = 128: a tie, kept)
     // (last template flag: epilogue operands requested after the MFMAs -- at C = 64 / 128 that removes the spills of the
     // chained form, -2 us / neutral; at C = 256 it measured +1 us and stays off)
-    return C == 64    ? launch_fused<64, 2, 2, 2, 1, 16, CIPS3D_C64_MINW, true, true, true>(a, st)
-           : C == 128 ? launch_fused<128, 4, 2, 2, 1, 32, 2, true, false, CIPS3D_C128_LATE>(a, st)
+    return C == 64    ? launch_fused<64, 2, 2, 2, 1, 16, 4, true, true, true>(a, st)
+           : C == 128 ? launch_fused<128, 4, 2, 2, 1, 32, 2, true, false, true>(a, st)
                       : launch_fused<256, 2, 8, 1, 2, 64, 2, true, true>(a, st);
   switch (C) {
     // tile shapes / register budgets picked by sweep on MI355X (profiles/r01_i_*): time per stage in the comment
@@ -2221,7 +2132,7 @@ extern "C" int cips3d_fused_up_conv_next(const float* y_lo, const float* fir, co
     // (252) 136.8 VALU / 16.7 us.  Not the wave launch rate: a wave that owns all 32 channels of its 64 pixels (<32, 2, 1, 4, 1, 32,
     // 4>: half the waves, no cross-wave ToRGB exchange) takes 39.6 against 39.4 us on one box, eight waves per workgroup 41.0.  The
     // conv2 epilogue written as channel-pair v_pk_*_f32 by hand: 37.4 against 37.5 -- hipcc's SLP pass had packed it already.)
-    case 32: return launch_fused<32, 1, 2, 2, 1, 32, CIPS3D_C32_MINW, false, false, true>(a, st);   // 2 rows x 64, 4 waves     46 us @1024^2
+    case 32: return launch_fused<32, 1, 2, 2, 1, 32, 8, false, false, true>(a, st);   // 2 rows x 64, 4 waves     46 us @1024^2
     case 64: return launch_fused<64, 2, 2, 2, 1, 16, 4>(a, st);      // 2 rows x 64, 4 waves, BK 16     42 us @512^2
     case 128: return launch_fused<128, 4, 2, 4, 1, 32, 2>(a, st);    // 4 rows x 64                     33 us @256^2
     case 256: return launch_fused<256, 2, 8, 1, 2, 64, 2>(a, st);    // 2 rows x 32: 256 workgroups at 128^2

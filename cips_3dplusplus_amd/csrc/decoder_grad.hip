@@ -14,7 +14,6 @@
 //                                 then ONE launch for the modulation backward of all layers, the style-table backward, and a
 //                                 tail launch for the scalar noise weights.
 // Gradient operands of the split-fp16 GEMMs are scaled by their measured maxima (amax slots, cips3d_range).
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -408,8 +407,7 @@ extern "C" int cips3d_decoder_grad_forward(const cips3d_decoder_grad_plan* plan,
   // conv's registers (partial sums per row block, cips3d_modconv1x1_torgb), and the slots of consecutive such layers are
   // folded by ONE cips3d_torgb_reduce when their sum is first needed -- eight cips3d_torgb launches that re-read the
   // activations become two reductions at CompCars 256^2.  The slots live in g[0] (a gradient buffer: idle in the forward;
-  // one layer's slots are < 3/32 of its activation).  CIPS3D_GRAD_TORGB_FOLD=0: one cips3d_torgb per layer (A/B knob).
-  static const bool fold_on = [] { const char* e = getenv("CIPS3D_GRAD_TORGB_FOLD"); return !(e && e[0] == '0'); }();
+  // one layer's slots are < 3/32 of its activation).
   int64_t g_floats = 0;        // what g[0] certainly holds: the largest StyledConv output
   for (int li = 0; li < P.n_layers; ++li)
     if (P.layers[li].kind == 0) {
@@ -441,7 +439,7 @@ extern "C" int cips3d_decoder_grad_forward(const cips3d_decoder_grad_plan* plan,
         rgb_i ^= 1;
       }
       const cips3d_grad_layer* T = li + 1 < P.n_layers ? &P.layers[li + 1] : nullptr;
-      const bool fold = fold_on && L.kind == 0 && T && T->kind == 2 && T->Cin == L.Cout && T->H == L.H && T->W == L.W && hw % 4 == 0 &&
+      const bool fold = L.kind == 0 && T && T->kind == 2 && T->Cin == L.Cout && T->H == L.H && T->W == L.W && hw % 4 == 0 &&
                         fold_nb < CIPS3D_TORGB_FOLD_MAX && (fold_slots == 0 || (fold_H == L.H && fold_W == L.W)) &&
                         ((int64_t)fold_slots + L.Cout / 16) * B * 3 * hw <= g_floats;
       if (fold) {

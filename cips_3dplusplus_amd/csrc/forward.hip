@@ -286,12 +286,11 @@ extern "C" int cips3d_generator_forward(const cips3d_generator_plan* plan, const
       cips3d_reduce_job ride_job{};
       bool ride = false;
       if (L.kind == 1 && fold_slots) {
-        static const int ride_on = getenv("CIPS3D_TORGB_RIDE") ? atoi(getenv("CIPS3D_TORGB_RIDE")) : 1;      // A/B knob
         const bool fused_next = li + 2 < P.n_dec_layers && P.layers[li + 1].kind == 0 && P.layers[li + 2].kind == 3 &&
                                 P.layers[li + 1].Cin == L.Cout && P.layers[li + 1].Cout == L.Cout && P.layers[li + 2].Cin == L.Cout &&
                                 cips3d_fused_up_conv_supported(L.Cout, L.H, L.W);
         const int64_t fhw = (int64_t)fold_H * fold_W;
-        if (ride_on && ranged && fused_next && !ylo_ready && (L.flags & 4) && !(L.flags & 32) && fold_slots <= 48 && fhw % 4 == 0 &&
+        if (ranged && fused_next && !ylo_ready && (L.flags & 4) && !(L.flags & 32) && fold_slots <= 48 && fhw % 4 == 0 &&
             (int64_t)B * 3 * fhw / 4 <= ((int64_t)L.H * L.W + 127) / 128 * B * 128) {
           ride_job.part = P.rgb_part;
           for (int k = 0; k < fold_nb; ++k) ride_job.bias[k] = fold_bias[k];

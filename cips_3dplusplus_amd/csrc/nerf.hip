@@ -46,7 +46,6 @@
 // Roofline: MFMA-bound on paper (flops/point = 2*3*H + (D-1)*2*H^2 + 2*(H+3)*H + 2*H*4, executed as 3 fp16 products per
 // fp32 product); with the split form the sine epilogues (VALU) and the LDS fragment reads are of the same order as the
 // matrix time.  HBM traffic is the partials only (n_chunks * (H+8) * 4 B per ray).
-#include <stdlib.h>
 
 #include <atomic>
 #include <type_traits>
@@ -1040,14 +1039,13 @@ extern "C" int64_t cips3d_nerf_part_floats(int B, int img_size, int hidden, int 
 }
 
 // fused finish: needs the chunk waves of a ray group in one workgroup (n_chunks divides 8), the tables large enough for the scalar exchange
-// and the partial exchange + tables within the 160 KB of LDS.  CIPS3D_NERF_FUSE_FINISH=0: the stand-alone nerf_finish launch (A/B knob).
+// and the partial exchange + tables within the 160 KB of LDS; otherwise the stand-alone nerf_finish launch.
 static int nerf_fuse_plan(const cips3d_nerf_params* p) {
   const int H = p->hidden, L = p->depth + 1;
   if (H != 32 && H != 64 && H != 128 && H != 256) return 0;
   const int TPS = H == 256 ? 4 : 2;
   if (!(p->o_features && p->o_thumb && p->o_xyz && p->o_mask)) return 0;
-  static const int off = getenv("CIPS3D_NERF_FUSE_FINISH") ? atoi(getenv("CIPS3D_NERF_FUSE_FINISH")) == 0 : 0;   // A/B knob
-  if (off || p->n_chunks < 1 || WAVES % p->n_chunks != 0 || nerf_table_floats(H, L) < WAVES * 8 * RAYS) return 0;
+  if (p->n_chunks < 1 || WAVES % p->n_chunks != 0 || nerf_table_floats(H, L) < WAVES * 8 * RAYS) return 0;
   return sizeof(float) * ((size_t)nerf_ring_floats(H, TPS, true) + nerf_table_floats(H, L)) <= 160 * 1024 ? 1 : 0;
 }
 

@@ -172,7 +172,7 @@ __device__ __forceinline__ RayGeom make_ray(const cips3d_nerf_bwd_geom& G, int b
 
 // stage the FiLM table of view b: s_film[l][0][o] = gamma' (gamma 2^-s for the MFMA layers), s_film[l][1][o] = gamma bias + beta
 // `unit`: 1 for radians (the backward kernel: its y = uc gamma' needs gamma' itself), 1 / 2 pi for the forward recompute, which
-// evaluates the sines exactly as the render kernel does (nerf.hip, CIPS3D_FILM_REVOLUTIONS) so that both fill the same stash
+// evaluates the sines exactly as the render kernel does (nerf.hip; FILM_UNIT / FILM_SIN of nerf_mlp.h) so that both fill the same stash
 __device__ __forceinline__ void stage_film(const cips3d_nerf_bwd_fused_params& P, int b, int H, int D, float* s_film, int tid,
                                            float unit = 1.f) {
   const int L = D + 1;

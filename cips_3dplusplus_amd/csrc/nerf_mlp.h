@@ -5,19 +5,11 @@
 #include "common.h"
 #include "nerf_geom.h"
 
-// CIPS3D_FILM_REVOLUTIONS: the staged FiLM table carries gamma' / 2 pi and c / 2 pi, so that the epilogue's FMA yields the
+// The staged FiLM table carries gamma' / 2 pi and c / 2 pi, so that the epilogue's FMA yields the
 // sine argument in revolutions and v_sin_f32(fract(.)) takes it as it is -- one multiplication less per activation.  The extra
 // rounding (of gamma' / 2 pi, once per table entry) perturbs the argument by |x| 2^-24 relative, the size of an ulp of gamma.
-#ifndef CIPS3D_FILM_REVOLUTIONS
-#define CIPS3D_FILM_REVOLUTIONS 1
-#endif
-#if CIPS3D_FILM_REVOLUTIONS && !defined(CIPS3D_EXACT_SINE) && !defined(CIPS3D_REDUCED_SINE)
 #define FILM_UNIT 0.159154943091895336f
 #define FILM_SIN sin_revolutions
-#else
-#define FILM_UNIT 1.f
-#define FILM_SIN cips3d_sin
-#endif
 
 namespace {
 

@@ -735,7 +735,7 @@ def test_full_size_forward_repeats_bit_for_bit_at_batch_4(precision):
     """Sixty one-call forwards at 1024^2, batch 4 (fixed noise, no jitter) must produce the same bits: every kernel of the
     decoder runs with several workgroups per CU there, and the four fused up-sampling stages are compiled WITH hipcc's SLP
     vectoriser (v_pk_*_f32 in their FIR / epilogue arithmetic).  The planes kernels (csrc/chain.hip) once differed from run to
-    run in exactly that situation when SLP had packed their ToRGB fold (tools/pk_fold_probe.sh, profiles/r04_pk_fold_probe.txt:
+    run in exactly that situation when SLP had packed their ToRGB fold (profiles/r04_pk_fold_probe.txt, profiles/r05_slp_fold_cause.md:
     a property of that build's code, not of v_pk_fma_f32 -- the same pattern written by hand repeats); this is the tripwire for
     the rest of the decoder."""
     from cips_3dplusplus_amd.camera import Camera

@@ -208,7 +208,7 @@ def test_chain_kernels_carry_no_high_register_broadcast_of_packed_fp32(tmp_path)
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     text = out.read_text()
-    assert "-fno-slp-vectorize" in build.FILE_FLAGS.get("chain.hip", []) or os.environ.get("CIPS3D_CHAIN_SLP") == "1"
+    assert "-fno-slp-vectorize" in build.FILE_FLAGS.get("chain.hip", [])
     cur, bad, n_kernels = None, [], 0
     for line in text.splitlines():
         m = re.match(r"^(_Z\S*chain_gemm_kernel\S*):", line)
@@ -221,3 +221,34 @@ def test_chain_kernels_carry_no_high_register_broadcast_of_packed_fp32(tmp_path)
             bad.append((cur, line.strip()))
     assert n_kernels >= 3, "chain_gemm_kernel instantiations not found in the assembly"
     assert not bad, bad[:3]
+
+
+def test_every_build_macro_and_c_side_environment_variable_is_documented():
+    """A `CIPS3D_*` macro that a preprocessor conditional under csrc/ tests is a build of its own, a C-side `getenv("CIPS3D_...")` a
+    path of its own: each is an instrument or a product switch that tools/README.md (macros, variables) or INTEGRATION.md (variables)
+    names -- or it is an A/B knob whose measurement is over, which is folded to its shipped value, not kept.  Include
+    guards and the constants the public header defines are not knobs."""
+    import re
+    from cips_3dplusplus_amd import build
+    root = os.path.dirname(build.PKG)
+    read = lambda *parts: open(os.path.join(root, *parts), encoding="utf-8").read()
+    header = read("include", "cips3d_hip.h")
+    public = set(re.findall(r"^\s*#\s*define\s+(CIPS3D_\w+)", header, re.M))
+    readme, integration = read("tools", "README.md"), read("INTEGRATION.md")
+    named = lambda name, text: re.search(name + r"(?!\w)", text) is not None      # (`-DCIPS3D_X` names CIPS3D_X, `CIPS3D_X_Y` does not)
+    macros, variables, n_files = {}, {}, 0
+    for f in sorted(os.listdir(build.CSRC)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        n_files += 1
+        text = read("cips_3dplusplus_amd", "csrc", f)
+        for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", text, re.M):
+            for name in re.findall(r"\bCIPS3D_\w+", line):
+                macros.setdefault(name, f)
+        for name in re.findall(r"getenv\(\s*\"(CIPS3D_\w+)\"", text):
+            variables.setdefault(name, f)
+    assert n_files > 20 and "CIPS3D_CHAIN_STAMPS" in macros and "CIPS3D_STYLE_PHASE" in variables      # the scan sees the sources
+    undocumented = {n: f for n, f in macros.items() if n not in public and not named(n, readme)}
+    assert not undocumented, f"build macros that tools/README.md does not name: {undocumented}"
+    undocumented = {n: f for n, f in variables.items() if not named(n, readme) and not named(n, integration)}
+    assert not undocumented, f"C-side environment variables that neither tools/README.md nor INTEGRATION.md names: {undocumented}"

@@ -2,7 +2,7 @@
 independent half-width chains (a 1x1 conv couples a pixel only to itself, so the left and right halves of the image
 never meet) on two streams, so that one chain's launch boundary / DMA ramp / store tail runs under the other's MFMAs.
 
-    [CIPS3D_GEMM_CFG=7] python tools/gemm_two_chains.py
+    python tools/gemm_two_chains.py
 """
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
