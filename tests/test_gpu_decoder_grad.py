@@ -8,6 +8,8 @@ import torch
 import cips_3dplusplus_amd as pkg
 from cips_3dplusplus_amd import hip
 
+import _decoder_bwd_cases as BC
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -22,13 +24,17 @@ def _rel(a, ref):
 @pytest.mark.parametrize("sa,sb", [(1.0, 1.0), (2.0 ** -30, 2.0 ** 17), (2.0 ** 20, 2.0 ** -24)])
 def test_split_wgrad_is_as_accurate_as_fp32_at_any_magnitude(B, M, K, P, sa, sb):
     """dwm[b] = dy[b] x[b]^T over the pixels on split-fp16 products: gradients of any magnitude (the scale comes from the
-    measured maxima) within 1.5x of what the fp32-MFMA kernel misses against fp64, no inf / nan; accumulate mode adds."""
+    measured maxima) within 1.5x of what the fp32-MFMA kernel misses against fp64, no inf / nan; accumulate mode adds.  The
+    fp32-MFMA kernel, the yardstick, is itself held to its per-element bound (tests/_decoder_bwd_cases.py)."""
     g = torch.Generator(device=DEV).manual_seed(M + K + B)
     dy = torch.randn(B, M, P, device=DEV, generator=g) * sa
     x = torch.randn(B, K, P, device=DEV, generator=g) * sb
     x[:, :, ::7] *= 1e-3                                   # a wide spread inside one tensor
     ref = torch.einsum("bmp,bkp->bmk", dy.double().cpu(), x.double().cpu())
     f32 = hip.gemm_wgrad(dy, x)
+    e_f32 = (f32.double().cpu() - ref).abs()
+    bound = BC.wgrad_bound(dy, x).cpu()                      # (fp64 on the device: the contraction of the absolute values)
+    assert bool((e_f32 <= bound).all()), f"gemm_wgrad is {BC.worst(e_f32, bound)[0]:.3g} x its bound"
     sp = hip.gemm_wgrad_split(dy, x, hip.absmax(dy), hip.absmax(x))
     assert bool(torch.isfinite(sp).all())
     e32, esp = _rel(f32, ref), _rel(sp, ref)
