@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(1024) modulate_bwd_ds_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ packing
-// out = A-fragment order (see decoder.hip: modulate_row) of wm[b] (M x K) or of its transpose (K x M).
+// out = A-fragment order (see modulate.hip: modulate_row) of wm[b] (M x K) or of its transpose (K x M).
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ wm, float* __restrict__ out, int B, int M,
                                                    int K, int transpose) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ wm,
   const int o = tr ? c : r, i = tr ? r : c;   // (row, column) of the packed matrix
   const int OM = tr ? K : M, OK = tr ? M : K;
   if (transpose & 2) {
-    // split-fp16 fragments for CIPS3D_GEMM_SPLIT (decoder.hip): 2^8 w = fp16 hi + fp16 lo, natural k order
+    // split-fp16 fragments for CIPS3D_GEMM_SPLIT (gemm1x1.hip): 2^8 w = fp16 hi + fp16 lo, natural k order
     const int ot = o >> 4, kb = i >> 5, j = i & 7, q = (i >> 3) & 3;
     const float sv = wm[e] * 256.f;
     _Float16 hi, lo;
@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(256) gemm_wgrad_kernel(const float* __restrict
         unsafeAtomicAdd(dwm + ((int64_t)b * M + m0 + 16 * i + 4 * q + t) * K + k0 + 16 * j + r, acc[i][j][t]);
 }
 
-// The same contraction on split-fp16 products (v_mfma_f32_16x16x32_f16, three per fp32 product; decoder.hip explains the
+// The same contraction on split-fp16 products (v_mfma_f32_16x16x32_f16, three per fp32 product; mfma_frag.h explains the
 // arithmetic).  Gradients have no natural scale, so both operands are split as v * 2^-e with the power of two that puts the
 // tensor's MEASURED maximum (amax slots of the producing kernel, cips3d_range) into [2^14, 2^15); the accumulators go back
 // through 2^(e_dy + e_x), exactly.

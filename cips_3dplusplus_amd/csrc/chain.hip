@@ -1,7 +1,7 @@
 // The run of 1x1 StyledConvs at the NeRF resolution (conv1 + convs.0-7 of the release decoder: nine 512-channel GEMMs at
 // 64^2, models/model_v3.py:602-632) on SPLIT-fp16 activations that STAY split between layers.
 //
-// Split-fp16 arithmetic (decoder.hip, nerf.hip): x = hi + lo with hi = fp16(x), lo = fp16(x - hi) -- 22 significant bits in
+// Split-fp16 arithmetic (mfma_frag.h, nerf.hip): x = hi + lo with hi = fp16(x), lo = fp16(x - hi) -- 22 significant bits in
 // the 4 bytes of an fp32 -- and a product is three exact fp16 products accumulated in fp32 on v_mfma_f32_16x16x32_f16.
 // cips3d_modconv1x1 in CIPS3D_GEMM_SPLIT mode splits the fp32 activations in registers after every LDS read (3 VALU per
 // value, repeated by every wave row): VALU-bound at ~15.5 us per layer.  Here the PRODUCER's epilogue splits each output
@@ -55,19 +55,9 @@
 // out (asm v_fmac_f32 in the epilogue: 0 of 59 repeats differ, with or without SLP), so correctness does not hang on a
 // compiler flag; build.py still compiles this file with -fno-slp-vectorize (no other packed-fp32 arithmetic in the planes
 // kernels either; no measurable cost), and tests/test_gpu_bf16_storage.py repeats the folds bit for bit.
-#include "common.h"
+#include "mfma_frag.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
-constexpr float kSplitInv = 1.f / 256.f;       // the modulate kernel scaled the weights by 2^8
-
-__device__ __forceinline__ constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
 #ifdef CIPS3D_CHAIN_STAMPS
 // Diagnostic build only: per-phase cycle sums over all workgroups (wave 0), one batch of atomics per workgroup at its end.
@@ -455,11 +445,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
       if (npx[c] < HW) {
         if (a.out_fmt == 1) {
           // planes: channels obase + 4 q + r live in channel block (obase >> 3) + (q >> 1), elements 4 (q & 1) + r
-          typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-          unsigned h0, l0, h1, l1;
-          cips3d_split_pair(v[0], v[1], h0, l0);
-          cips3d_split_pair(v[2], v[3], h1, l1);
-          const h4 hi = __builtin_bit_cast(h4, u32x2_t{h0, h1}), lo = __builtin_bit_cast(h4, u32x2_t{l0, l1});
+          h4 hi, lo;
+          split_frag(v[0], v[1], v[2], v[3], hi, lo);
           _Float16* dst = reinterpret_cast<_Float16*>(a.out) +
                           ((((int64_t)b * (a.Cout >> 3) + (obase >> 3) + (q >> 1)) * 2) * HW + npx[c]) * 8 + 4 * (q & 1);
           cips3d_store_wt8(dst, hi);                      // (write-through: common.h)
@@ -469,12 +456,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
           // of the bf16 mode)
           unsigned short* dst = reinterpret_cast<unsigned short*>(a.out) +
                                 (((int64_t)b * (a.Cout >> 3) + (obase >> 3) + (q >> 1)) * HW + npx[c]) * 8 + 4 * (q & 1);
-          typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-          typedef float f32x2_t __attribute__((ext_vector_type(2)));
-          typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-          const bf16x2_t p0 = __builtin_convertvector(f32x2_t{v[0], v[1]}, bf16x2_t);
-          const bf16x2_t p1 = __builtin_convertvector(f32x2_t{v[2], v[3]}, bf16x2_t);
-          cips3d_store_wt8(dst, u32x2_t{__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1)});
+          cips3d_store_wt8(dst, pack_bf16(v[0], v[1], v[2], v[3]));
         } else if (a.out_fmt == 2) {
           unsigned short* dst = reinterpret_cast<unsigned short*>(a.out) + ((int64_t)b * a.Cout + obase + 4 * q) * HW + npx[c];
           typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));

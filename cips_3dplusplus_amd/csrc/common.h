@@ -118,7 +118,7 @@ __device__ static inline float sin_revolutions(float t) { return __builtin_amdgc
 #define cips3d_sin sin_hw_direct
 #define cips3d_cos cos_hw_direct
 
-// Split-fp16: x = hi + lo with hi = fp16(x), lo = fp16(x - hi) (22 significant bits; see nerf.hip / decoder.hip / chain.hip).
+// Split-fp16: x = hi + lo with hi = fp16(x), lo = fp16(x - hi) (22 significant bits; see nerf.hip / mfma_frag.h / chain.hip).
 // `x` is made opaque first: hipcc otherwise folds a multiplication that produced x into the conversion (v_fma_mixlo_f16:
 // fp16 of the exactly-rounded-once product) while the residual is taken against the fp32-rounded x -- when the two roundings
 // of hi disagree (rare) the halves miss x by a whole fp16 ulp (2^-11 relative; measured 2.5e-4 on the fused stage's output).

@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(256) modconv3x3_kernel(Conv3Args a) {
 
 // ------------------------------------------------------------------------------------------------
 // The same convolution on split-fp16 products (the decoder's default arithmetic: three exact fp16 x fp16 products per fp32 product
-// on v_mfma_f32_16x16x32_f16, fp32 accumulation -- decoder.hip / chain.hip; 5.3 x the fp32 matrix instruction's rate).
+// on v_mfma_f32_16x16x32_f16, fp32 accumulation -- mfma_frag.h / chain.hip; 5.3 x the fp32 matrix instruction's rate).
 //   contraction index   a 32-deep MFMA step holds the 16 channels of a K stage for TWO taps: k = 16 h + ch, tap = 2 p + h for the
 //                       tap pairs p = 0 .. 4 (taps in row-major order, the tenth tap is zero weights).  Lane quarter q supplies
 //                       k = 8 q .. 8 q + 7: channels 8 (q & 1) .. + 7 of tap 2 p + (q >> 1).

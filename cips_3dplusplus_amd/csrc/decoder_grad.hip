@@ -10,7 +10,7 @@
 //   cips3d_decoder_grad_backward  one memset of every accumulator, then per StyledConv, last to first:
 //                                   [FIR transpose of an up-sampling layer]  -> weight-gradient GEMM (split-fp16,
 //                                   backward.hip) -> data-gradient GEMM whose epilogue IS the previous layer's activation
-//                                   backward, ToRGB backward and parameter reductions (decoder.hip, ACTBWD);
+//                                   backward, ToRGB backward and parameter reductions (gemm1x1.hip, ACTBWD);
 //                                 then ONE launch for the modulation backward of all layers, the style-table backward, and a
 //                                 tail launch for the scalar noise weights.
 // Gradient operands of the split-fp16 GEMMs are scaled by their measured maxima (amax slots, cips3d_range).
@@ -33,7 +33,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
 // ------------------------------------------------------------------------------------------------
 // Activation backward without a GEMM in front of it: the LAST StyledConv's output is read by the last ToRGB only, so the
 // gradient w.r.t. it is the rank-3 product rgb_w^T drgb (+ g_in when the caller has another contribution).  Same
-// arithmetic and reductions as the ACTBWD epilogue of decoder.hip.  grid (ceil(HW / 1024), C, B).
+// arithmetic and reductions as the ACTBWD epilogue of gemm1x1.hip.  grid (ceil(HW / 1024), C, B).
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) act_tail_kernel(const float* __restrict__ g_in, const float* __restrict__ y,
                                                        const float* __restrict__ rgb_w, const float* __restrict__ drgb,
@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(256) act_tail_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // Transpose of the 2x FIR up-sampler (upfirdn2d up = 2, pad = (2, 1), 4 x 4 taps; the forward is up2_fir_act_kernel of
-// decoder.hip):  out[oy] = sum_iy in[iy] k[oy - 2 iy + 1]  =>  g_in[iy][ix] = sum_{t,u} g_out[2iy - 1 + t][2ix - 1 + u] k[t][u].
+// gemm1x1.hip):  out[oy] = sum_iy in[iy] k[oy - 2 iy + 1]  =>  g_in[iy][ix] = sum_{t,u} g_out[2iy - 1 + t][2ix - 1 + u] k[t][u].
 // One thread = 4 consecutive ix of one row; grid (blocks, B) so that a workgroup's maximum belongs to one sample.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) up2_fir_bwd_kernel(const float* __restrict__ g_hi, const float* __restrict__ fir,

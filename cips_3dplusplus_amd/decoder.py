@@ -2,7 +2,7 @@
 
 Same class names, constructor arguments, parameter / buffer names and shapes as the reference so
 `decoder.*`, `style.*`, `style_decoder.*` keys of a reference checkpoint load unchanged
-(SURVEY.md Appendix B).  Forward passes launch the HIP kernels of csrc/decoder.hip:
+(SURVEY.md Appendix B).  Forward passes launch the HIP kernels of csrc/modulate.hip, gemm1x1.hip, decoder_ops.hip and fused_stage.hip:
 
     ModulatedConv2d (k=1)   modulation GEMV -> modulate_weights (MFMA-packed) -> modconv1x1 GEMM
         up-sampling variant modconv1x1 at low resolution, then the 2x polyphase FIR

@@ -3,7 +3,7 @@
 `forward(...)` keyword arguments, same `ret_maps` keys, same `state_dict` key names.
 
 forward = mapping networks (cips3d_linear chain) -> fused NeRF render (csrc/nerf.hip) -> decoder
-(csrc/decoder.hip).  Inference path only: no autograd graph is built (the reference's training-only
+(csrc/modulate.hip, gemm1x1.hip, fused_stage.hip, decoder_ops.hip).  Inference path only: no autograd graph is built (the reference's training-only
 switches raise, see `forward`).  RNG sites of the reference stay RNG sites here (per-ray jitter when
 `perturb`, fresh decoder noise when `noise_bufs` is None, 10 000 z's in `get_mean_latent`) and are
 injectable for parity runs (`perturb_u=`, `noise_bufs=`, preset `style_render_mean` /

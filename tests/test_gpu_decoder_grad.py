@@ -48,7 +48,7 @@ def test_split_wgrad_is_as_accurate_as_fp32_at_any_magnitude(B, M, K, P, sa, sb)
     (2, 512, 512, 64, True, True, False), (2, 512, 512, 64, False, False, False), (1, 256, 512, 32, True, True, True),
     (2, 128, 256, 32, True, False, True), (2, 64, 128, 64, True, True, False), (3, 32, 64, 16, True, True, True),
     (2, 32, 32, 48, False, True, False),
-    # the arms of the tile choice (gemm_tile in csrc/decoder.hip) the cases above do not reach: a contraction that is no multiple of
+    # the arms of the tile choice (gemm_tile in csrc/gemm1x1.hip) the cases above do not reach: a contraction that is no multiple of
     # 64, 280 tiles under a height that is no multiple of 128, and 128 / 64 / 32 rows behind a contraction longer than 128
     (1, 96, 256, 16, True, True, False), (1, 64, 320, 84, True, False, False), (1, 256, 128, 16, True, True, False),
     (1, 256, 64, 16, False, True, False), (1, 256, 32, 16, True, False, True)])

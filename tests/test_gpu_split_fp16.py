@@ -23,7 +23,7 @@ def cu(t):
     return t.to(DEV).contiguous()
 
 
-# (one case per arm of the tile choice, gemm_tile in csrc/decoder.hip: 256 tiles of 64 x 128 / more / at most 128; K <= 128, 32 rows;
+# (one case per arm of the tile choice, gemm_tile in csrc/gemm1x1.hip: 256 tiles of 64 x 128 / more / at most 128; K <= 128, 32 rows;
 # then 132 tiles with Cin % 64 != 0, 260 tiles with Cout % 128 != 0, and Cout = 128 / 64 / 32 under K <= 128 and K > 128)
 @pytest.mark.parametrize("cin,cout,hw,B", [(512, 512, 4096, 1), (256, 512, 4096, 2), (512, 256, 1024, 1), (64, 32, 256, 2),
                                            (96, 256, 4224, 1), (64, 320, 6656, 1), (64, 128, 512, 1), (128, 64, 512, 1),

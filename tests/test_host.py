@@ -223,6 +223,16 @@ def test_chain_kernels_carry_no_high_register_broadcast_of_packed_fp32(tmp_path)
     assert not bad, bad[:3]
 
 
+def test_build_sources_are_exactly_the_hip_files_of_csrc():
+    """A csrc/*.hip that build.SOURCES leaves out shows up only as a link error or a missing symbol at load time; a name in the list
+    without a file is skipped silently by the build.  (No .hip is deliberately left unbuilt.)"""
+    from cips_3dplusplus_amd import build
+    on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip"))
+    assert len(build.SOURCES) == len(set(build.SOURCES)), "a file is listed twice"
+    assert sorted(build.SOURCES) == on_disk
+    assert set(build.FILE_FLAGS) <= set(build.SOURCES), "per-file flags for a file that is not built"
+
+
 def test_every_build_macro_and_c_side_environment_variable_is_documented():
     """A `CIPS3D_*` macro that a preprocessor conditional under csrc/ tests is a build of its own, a C-side `getenv("CIPS3D_...")` a
     path of its own: each is an instrument or a product switch that tools/README.md (macros, variables) or INTEGRATION.md (variables)

@@ -2,10 +2,12 @@
 
     python tools/isa_same.py [--base REV] [--flags="-DCIPS3D_STAMPS ..."] [--jobs N] [file.hip ...]
 
-Compiles every csrc/*.hip (or the named ones) of REV (default HEAD) and of the working tree to gfx950 assembly with the
-library's flags (build.FLAGS, build.FILE_FLAGS, --flags on top) and compares the kernels by mangled name.  One line per
-translation unit, then the kernels that differ and those only one side has.  Exit status 1 if a kernel both sides have
-differs or the working tree has one that REV has not.
+Compiles every csrc/*.hip (or the named ones, where a side has them) of REV (default HEAD) and of the working tree to gfx950
+assembly with the library's flags (build.FLAGS, build.FILE_FLAGS, --flags on top), pools the kernels of all translation units
+of each side by mangled name and compares the two pools: a kernel that moved to another file with its body unchanged is the
+same.  One line per translation unit, one for the pools, then the kernels that differ and those only one side has.  Exit status 1
+if a kernel both sides have differs, the working tree has one that REV has not, or the working tree defines a name in more
+files than REV does (a copy).
 """
 import argparse
 import concurrent.futures as cf
@@ -41,6 +43,16 @@ def kernels(csrc, name, extra, out):
     return found
 
 
+def pool(units):
+    """{mangled name: [(file, text), ...]} over the translation units of one side.  A kernel with internal linkage that a shared
+    header defines may be compiled into more than one of them (vgg_shared.h): the copies are kept, sorted by text."""
+    pooled = {}
+    for name, found in sorted(units.items()):
+        for k, text in found.items():
+            pooled.setdefault(k, []).append((name, text))
+    return {k: sorted(v, key=lambda ft: ft[1]) for k, v in pooled.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", default="HEAD")
@@ -48,26 +60,38 @@ def main():
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("files", nargs="*")
     a = ap.parse_args()
-    bad = False
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "-C", ROOT, "archive", a.base, "cips_3dplusplus_amd/csrc", "include"], check=True,
                              capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
-        old_csrc = os.path.join(tmp, "cips_3dplusplus_amd", "csrc")
-        names = a.files or sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip"))
-        one = lambda n: (n, kernels(old_csrc, n, a.flags.split(), os.path.join(tmp, n + ".old.s")),      # noqa: E731
-                         kernels(build.CSRC, n, a.flags.split(), os.path.join(tmp, n + ".new.s")))
+        dirs = {"old": os.path.join(tmp, "cips_3dplusplus_amd", "csrc"), "new": build.CSRC}
+        jobs = [(side, f) for side, d in dirs.items() for f in sorted(os.listdir(d))
+                if f.endswith(".hip") and (not a.files or f in a.files)]
+        one = lambda j: (j, kernels(dirs[j[0]], j[1], a.flags.split(), os.path.join(tmp, f"{j[1]}.{j[0]}.s")))   # noqa: E731
+        units = {"old": {}, "new": {}}
         with cf.ThreadPoolExecutor(max_workers=a.jobs) as ex:
-            for name, old, new in ex.map(one, names):
-                lists = {"differs": sorted(k for k in new if k in old and new[k] != old[k]), "new": sorted(set(new) - set(old)),
-                         "gone": sorted(set(old) - set(new))}
-                bad = bad or bool(lists["differs"] or lists["new"])
-                verdict = "same" if not any(lists.values()) else ", ".join(f"{len(v)} {k}" for k, v in lists.items())
-                print(f"{name:22s} {len(old):4d} -> {len(new):4d} kernels  {verdict}")
-                for tag, ks in lists.items():
-                    for k in ks:
-                        print(f"    {tag}: {k}")
-    return 1 if bad else 0
+            for (side, name), found in ex.map(one, jobs):
+                units[side][name] = found
+    old, new = pool(units["old"]), pool(units["new"])
+    texts = lambda copies: [t for _, t in copies]                                                                # noqa: E731
+    files = lambda k: {f for side in (old, new) for f, _ in side.get(k, [])}                                     # noqa: E731
+    # a copy that REV does not have as well is an error whether or not the bodies agree: two files would have to change together
+    twice = sorted(k for k in new if len(new[k]) > 1 and len(new[k]) != len(old.get(k, [])))
+    lists = {"differs": sorted(k for k in new if k in old and k not in twice and texts(new[k]) != texts(old[k])),
+             "new": sorted(set(new) - set(old)), "gone": sorted(set(old) - set(new)), "defined twice": twice}
+    for name in sorted(set(units["old"]) | set(units["new"])):
+        mine = {tag: [k for k in ks if name in files(k)] for tag, ks in lists.items()}
+        moved = sum(1 for k in units["new"].get(name, {}) if k in old and name not in {f for f, _ in old[k]})
+        verdict = "same" if not any(mine.values()) else ", ".join(f"{len(v)} {k}" for k, v in mine.items() if v)
+        verdict += f" ({moved} from other files)" if moved else ""
+        print(f"{name:22s} {len(units['old'].get(name, {})):4d} -> {len(units['new'].get(name, {})):4d} kernels  {verdict}")
+    count = lambda side: sum(len(v) for v in side.values())                                                     # noqa: E731
+    print(f"{'all files':22s} {count(old):4d} -> {count(new):4d} kernels  " +
+          ("same" if not any(lists.values()) else ", ".join(f"{len(v)} {k}" for k, v in lists.items() if v)))
+    for tag, ks in lists.items():
+        for k in ks:
+            print(f"    {tag}: {k}  [{', '.join(sorted(f for f, _ in new.get(k, old.get(k))))}]")
+    return 1 if lists["differs"] or lists["new"] or lists["defined twice"] else 0
 
 
 if __name__ == "__main__":
