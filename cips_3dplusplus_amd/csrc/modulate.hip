@@ -249,7 +249,10 @@ extern "C" int cips3d_modulate_weights(const float* W, const float* s, int64_t s
   const int packed = (demodulate & 2) ? (((demodulate & 4) ? 2 : 1) | (demodulate & 248)) : 0;   // bit 3: flipped taps, bit 4: split-fp16, bit 5: split16, bit 6: transposed, bit 7: bf16
   if ((packed & 32) && (ksq != 1 || (packed & 24))) return CIPS3D_E_UNSUPP;
   if ((packed & 64) && (ksq != 1 || (packed & 63) != 1)) return CIPS3D_E_UNSUPP;
-  if (packed && ksq == 1 && (Cout % 32 != 0 || Cin % 8 != 0)) return CIPS3D_E_UNSUPP;
+  // every ksq == 1 fragment layout indexes 16-channel k-groups (Cin >> 4: plain, chained, split16, transposed); the 32-channel
+  // blocks of the split and bf16 forms are checked below.  (Cin % 16 == 8 used to pass: channels 16 kq + 8 .. landed in the next
+  // o-tile's block -- in bounds, scrambled)
+  if (packed && ksq == 1 && (Cout % 32 != 0 || Cin % 16 != 0)) return CIPS3D_E_UNSUPP;
   if ((packed & 16) && ksq == 1 && ((packed & 7) != 1 || Cin % 32 != 0)) return CIPS3D_E_UNSUPP;
   if ((packed & 16) && ksq != 1 && (ksq != 9 || (packed & ~8) != 17)) return CIPS3D_E_UNSUPP;      // 3x3: PACKED | SPLIT [| FLIP] only
   if ((packed & 128) && (ksq != 1 || (packed & 127) != 1 || Cin % 32 != 0)) return CIPS3D_E_UNSUPP;
