@@ -50,7 +50,6 @@
 #include <atomic>
 #include <type_traits>
 #include "common.h"
-#include "nerf_mlp.h"
 
 #ifdef CIPS3D_STAMPS
 #ifndef CIPS3D_STAMP_WAVE
@@ -81,11 +80,6 @@ extern "C" int cips3d_debug_read_stamps(unsigned long long* out16) {
   hipMemcpyToSymbol(HIP_SYMBOL(g_nerf_stamps), z, 128);
   return 0;
 }
-#else
-#define STAMP(i)
-#define STAMP_FLUSH()
-#define STAMP_PARAM
-#define STAMP_ARG
 #endif
 
 #ifdef CIPS3D_CLOCK
@@ -126,6 +120,8 @@ extern "C" int cips3d_debug_read_clock_wg(unsigned long long* out, int n_wg) {
   return 0;
 }
 #endif
+
+#include "nerf_mlp.h"       // (behind the stamp macros: its forward layer carries the stamps of a diagnostic build)
 
 namespace {
 
@@ -218,204 +214,6 @@ __global__ void __launch_bounds__(256) nerf_pack32_kernel(const float* __restric
     const int m = (int)(rem / 512), half = (int)((rem % 512) / 256), lane = (int)((rem % 256) / 4), r = (int)(rem % 4);
     const int o = t * 16 + (lane & 15), k = 32 * m + 16 * half + 4 * (lane >> 4) + r;
     packed[i] = l < D - 1 ? w_hidden[(int64_t)l * per_layer + (int64_t)o * H + k] : w_view[(int64_t)o * (H + 3) + k];
-  }
-}
-
-// One MFMA layer for the wave's 16 points (split-fp16 products, fp32 accumulation; see the file header).
-//   VIEW = false: Y = sin(gamma' * (W' X) + c)            gamma' = gamma 2^-s, W' = 2^s W (s_film holds gamma')
-//   VIEW = true : f = sin(gamma' * (W' X + Wd' v) + c);  FA += w * f;  rgb head partial sums += Wc f
-//   last (hidden layers): Y is h_D, the sigma head's partial sum  sdf_acc += Ws . Y  is taken from the epilogue's fp32 values
-// The caller guarantees slab `seq` is resident in slot (seq & 1); every slab step prefetches seq+1
-// while multiplying and ends with wait + barrier.
-// F32: the exact-fp32 instantiation (Generator.set_precision("fp32_exact"); cips3d_nerf_params.packed32): the same slabs, ring
-// and register images hold fp32 -- a 1 KiB piece is a 16 x 16 block of W where the split stream has one plane of a 16 x 32
-// block, (Xh[m], Xl[m]) are the bits of the fp32 activations of o-tiles 2m, 2m + 1 (the MFMA D layout IS the B operand of
-// v_mfma_f32_16x16x4_f32: k-step r of k-quarter q <-> unit 16 T + 4 q + r), eight 32-cycle MFMAs per (tile, k-block) where the
-// split kernel issues three 16-cycle ones.  Two waves per SIMD as in the split kernel: one wave's sine epilogue runs under
-// the other's matrix block (a one-wave-per-SIMD form of the same arithmetic measured 252 us; this one: see DESIGN).
-__host__ __device__ constexpr int nerf_table_floats(int H, int L) { return L * 2 * H + 10 * H; }
-
-template <bool F32>
-__device__ __forceinline__ void put8(const float (&v)[8], h8& hi, h8& lo) {
-  if constexpr (F32) {
-    hi = __builtin_bit_cast(h8, f32x4{v[0], v[1], v[2], v[3]});
-    lo = __builtin_bit_cast(h8, f32x4{v[4], v[5], v[6], v[7]});
-  } else {
-    split8(v, hi, lo);
-  }
-}
-
-template <int NT, int TPS, bool VIEW, bool STASH, bool F32 = false>
-__device__ __forceinline__ void mfma_layer(const h8 (&Xh)[NT / 2], const h8 (&Xl)[NT / 2], h8 (&Yh)[NT / 2], h8 (&Yl)[NT / 2],
-                                           float (&FA)[NT * 4], float wgt, float (&chead)[3], float& sdf_acc, bool last,
-                                           Ring& ring, const float* film_l, const float* s_wd, const float* s_wc,
-                                           const float* s_ws, float vx, float vy, float vz, float* stash_l, int wave, int lane, int q4o STAMP_PARAM) {
-  constexpr int H = NT * 16;
-  constexpr int TILE = 16 * H;          // floats (= 4-byte hi/lo pairs) of one o-tile's A fragments
-  constexpr int SLAB = TILE * TPS;
-  constexpr int STEPS = NT / TPS;
-  constexpr int R = TPS * 4;            // output values produced per step
-  constexpr int MB = NT / 2;            // 32-unit k-blocks of the layer input
-  constexpr int BPS = TPS / 2;          // k-blocks of the NEXT layer's input a step completes
-  static_assert(TPS % 2 == 0 && NT % TPS == 0, "a slab step must complete whole 32-unit blocks");
-  // The slab steps of a layer are fully unrolled (with 96 fp16 MFMAs per step instead of 256 fp32 ones the whole kernel is
-  // ~40 KB of code): the step index is a constant, results go straight to their final registers (the rolled loop of the
-  // fp32 kernel had to rotate Yh / Yl / FA by 48 moves per step; unrolling measured 107.6 -> 101.0 us).
-  // Epilogue stagger.  Waves w and w + WAVES/2 share a SIMD and meet at every slab barrier; with the barrier after the
-  // FiLM/sine epilogue both would run its VALU instructions together while the matrix pipe idles.  The upper half of the
-  // waves takes the step barrier BEFORE its epilogue instead, which then overlaps the partner wave's next-step MFMAs.  Either
-  // position is after this wave's last read of slot (seq&1) and before its next stage_slab into it.
-  // In-kernel stamps of this scheme (tools/run_kernel.py nerf on a -DCIPS3D_STAMPS build): the two matrix blocks of a SIMD
-  // run together (~2.9k cycles for 192 MFMAs = the pipe is full), then the lower wave's epilogue (~1.3k) with the pipe idle;
-  // a step is ~6.4k cycles.  Tried: a true half-period offset (two barriers per step, the upper half one barrier behind, so
-  // that one wave's matrix block always faces the other's epilogue): correct, but 127 us instead of 97 -- a matrix block
-  // that has the SIMD to itself is bound by its own A-fragment reads (8 x [8 ds_read_b128 -> wait -> 12 MFMAs]; the second
-  // wave is what hides that latency today), and double-buffering the fragments needs 32 registers the kernel does not have.
-  const bool late_epilogue = __builtin_amdgcn_readfirstlane(wave) >= WAVES / 2;
-#pragma unroll
-  for (int sl = 0; sl < STEPS; ++sl) {
-    if (ring.seq + 1 < ring.seq_end) {
-      const int nxt = (ring.seq + 1) % ring.per_sample;
-      stage_slab<SLAB>(ring.packed + (int64_t)nxt * SLAB, ring.lds + ((ring.seq + 1) & 1) * SLAB, wave, lane);
-    }
-    STAMP(8);    // (in-layer stamps: the phase before the first one of a layer is charged to slot 12 / 11 of the previous step)
-    const float* slab = ring.lds + (ring.seq & 1) * SLAB;
-    const int o_base = sl * (TPS * 16) + q4o;          // this lane's first output unit of the step
-    f32x4 acc[TPS];
-    // (opaque per step: as loop invariants the operand copies of vx, vy, vz were hoisted out of the sample loop and spilled)
-    float vxo = vx, vyo = vy, vzo = vz;
-    if (VIEW) asm volatile("" : "+v"(vxo), "+v"(vyo), "+v"(vzo));
-#pragma unroll
-    for (int tt = 0; tt < TPS; ++tt) {
-      const int o4 = o_base + tt * 16;
-      if (VIEW) {       // view-direction columns (pre-scaled by 2^s at staging) straight into the accumulator
-        const f32x4 wx = *reinterpret_cast<const f32x4*>(s_wd + o4);
-        const f32x4 wy = *reinterpret_cast<const f32x4*>(s_wd + H + o4);
-        const f32x4 wz = *reinterpret_cast<const f32x4*>(s_wd + 2 * H + o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[tt][i] = fmaf(wz[i], vzo, fmaf(wy[i], vyo, wx[i] * vxo));
-      } else {
-        acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-    // Matrix block, software-pipelined over half k-blocks.  History, all measured: 8 reads -> wait -> 12 MFMAs per k-block
-    // (the form of the fp32 kernel) left each wave bound by 8 LDS round trips per step -- ~3.2k cycles for 1.5k of its own
-    // matrix work (in-kernel stamps) -- 92.0 us; the next half's 4 reads requested before the current half's 6 MFMAs, through
-    // the compiler (which drains lgkmcnt to 0 at every wait, the fresh prefetch included) 89.2 us; the wait provoked in FRONT
-    // of the next reads (below) 87.3 us, matrix block ~2.0k cycles per step.
-    {
-      constexpr int HT = TPS / 2;
-      h8 fh[2][HT], fl[2][HT];
-      auto load_half = [&](int buf, int m, int half) {
-#pragma unroll
-        for (int t = 0; t < HT; ++t) {
-          const int tt = half * HT + t;
-          fh[buf][t] = *reinterpret_cast<const h8*>(slab + tt * TILE + ((2 * m) * 64 + lane) * 4);
-          fl[buf][t] = *reinterpret_cast<const h8*>(slab + tt * TILE + ((2 * m + 1) * 64 + lane) * 4);
-        }
-      };
-      load_half(0, 0, 0);
-#pragma unroll
-      for (int g = 0; g < 2 * MB; ++g) {
-        const int m = g >> 1, half = g & 1, cur = g & 1;
-#pragma unroll
-        for (int t = 0; t < HT; ++t) asm volatile("" : "+v"(fh[cur][t]), "+v"(fl[cur][t]));
-        if (g + 1 < 2 * MB) load_half(cur ^ 1, (g + 1) >> 1, (g + 1) & 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (F32) {      // fh / fl: the fp32 fragments of the k-block's two 16-unit halves; k ascending, the bit-exact chain
-          const f32x4 x0 = __builtin_bit_cast(f32x4, Xh[m]), x1 = __builtin_bit_cast(f32x4, Xl[m]);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int t = 0; t < HT; ++t)
-              acc[half * HT + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(f32x4, fh[cur][t])[r], x0[r],
-                                                                        acc[half * HT + t], 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int t = 0; t < HT; ++t)
-              acc[half * HT + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(f32x4, fl[cur][t])[r], x1[r],
-                                                                        acc[half * HT + t], 0, 0, 0);
-        } else {
-#pragma unroll
-        for (int t = 0; t < HT; ++t)
-          acc[half * HT + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[cur][t], Xh[m], acc[half * HT + t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < HT; ++t)
-          acc[half * HT + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[cur][t], Xl[m], acc[half * HT + t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < HT; ++t)
-          acc[half * HT + t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[cur][t], Xh[m], acc[half * HT + t], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    STAMP(9);    // matrix block
-    if (late_epilogue) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's piece of slab seq+1 has landed
-      __syncthreads();
-    }
-    STAMP(10);   // late waves: step barrier
-    float res[R];
-#pragma unroll
-    for (int tt = 0; tt < TPS; ++tt) {
-      const int o4 = o_base + tt * 16;
-      const f32x4 g4 = *reinterpret_cast<const f32x4*>(film_l + o4);
-      const f32x4 c4 = *reinterpret_cast<const f32x4*>(film_l + H + o4);
-      if (VIEW) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(s_wc + o4);
-        const f32x4 w1 = *reinterpret_cast<const f32x4*>(s_wc + H + o4);
-        const f32x4 w2 = *reinterpret_cast<const f32x4*>(s_wc + 2 * H + o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float f = FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
-          res[tt * 4 + i] = fmaf(wgt, f, FA[sl * R + tt * 4 + i]);
-          chead[0] = fmaf(w0[i], f, chead[0]);
-          chead[1] = fmaf(w1[i], f, chead[1]);
-          chead[2] = fmaf(w2[i], f, chead[2]);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) res[tt * 4 + i] = FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
-        if (last) {     // h_D: sigma head partial (volume_renderer.py:148) from the fp32 values, before they are split
-          const f32x4 ws4 = *reinterpret_cast<const f32x4*>(s_ws + o4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sdf_acc = fmaf(ws4[i], res[tt * 4 + i], sdf_acc);
-        }
-      }
-    }
-    // The sink pass would otherwise move the sines below the barrier that follows (undoing the stagger): make
-    // the results opaque here.
-#pragma unroll
-    for (int k = 0; k < R; ++k) asm volatile("" : "+v"(res[k]));
-    if (VIEW) asm volatile("" : "+v"(chead[0]), "+v"(chead[1]), "+v"(chead[2]));
-    // fully unrolled steps: the step index is a constant, results go to their final places
-    if (VIEW) {
-#pragma unroll
-      for (int k = 0; k < R; ++k) FA[sl * R + k] = res[k];
-    } else {
-#pragma unroll
-      for (int bb = 0; bb < BPS; ++bb) {
-        float v8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v8[j] = res[(2 * bb) * 4 + j];
-        put8<F32>(v8, Yh[sl * BPS + bb], Yl[sl * BPS + bb]);
-      }
-    }
-    STAMP(11);   // epilogue
-    // slab seq+1 has landed for every wave before anyone reads it / before slot (seq&1) is reused
-    if (!late_epilogue) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)  (expcnt/lgkmcnt untouched)
-      __syncthreads();
-    }
-    STAMP(12);   // early waves: step barrier
-    if constexpr (STASH) {
-      // differentiable forward: the step's accumulators in register order [sl * TPS + tt][lane][4], for cips3d_nerf_bwd_fused.
-      // Issued after the step barrier, so that no store acknowledgement is waited for at it.
-#pragma unroll
-      for (int tt = 0; tt < TPS; ++tt) *reinterpret_cast<f32x4*>(stash_l + ((sl * TPS + tt) * 64 + lane) * 4) = acc[tt];
-    }
-    ++ring.seq;
   }
 }
 
@@ -618,31 +416,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     constexpr bool PP = !F32;
     const bool odd_hidden = PP && ((D - 1) & 1);
     float chead[3] = {0.f, 0.f, 0.f};
-    auto layer0 = [&](auto& Oh, auto& Ol) {
-#pragma unroll
-    for (int m = 0; m < NT / 2; ++m) {
-      float v8[8];
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int o4 = (2 * m + hf) * 16 + q4o;
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(s_film + o4);
-        const f32x4 c4 = *reinterpret_cast<const f32x4*>(s_film + H + o4);
-        const f32x4 wx = *reinterpret_cast<const f32x4*>(s_w0 + o4);
-        const f32x4 wy = *reinterpret_cast<const f32x4*>(s_w0 + H + o4);
-        const f32x4 wz = *reinterpret_cast<const f32x4*>(s_w0 + 2 * H + o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float pre = fmaf(wz[i], nz, fmaf(wy[i], ny, wx[i] * nx));
-          v8[hf * 4 + i] = FILM_SIN(fmaf(g4[i], pre, c4[i]));
-        }
-        if (D == 1) {           // no hidden MFMA layer: this is h_D
-          const f32x4 ws4 = *reinterpret_cast<const f32x4*>(s_ws + o4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sdf = fmaf(ws4[i], v8[hf * 4 + i], sdf);
-        }
-      }
-      put8<F32>(v8, Oh[m], Ol[m]);
-    }
+    auto layer0 = [&](auto& Oh, auto& Ol) {      // (D == 1: no hidden MFMA layer, layer 0 is h_D)
+      first_layer<NT, F32>(Oh, Ol, sdf, D == 1, s_film, s_w0, s_ws, nx, ny, nz, q4o);
     };
     // ---- hidden layers 1 .. D-1
     if constexpr (PP) {
@@ -650,7 +425,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
       if (odd_hidden) {          // layer 0 -> Y, the odd hidden layer Y -> X; then pairs
         layer0(Yh, Yl);
         STAMP(1);   // sample setup + layer 0
-        mfma_layer<NT, TPS, false, STASH, F32>(Yh, Yl, Xh, Xl, FA, 0.f, chead, sdf, D == 2, ring, s_film + 2 * H, s_wd, s_wc,
+        mfma_layer<NT, TPS, STASH, F32>(Yh, Yl, Xh, Xl, ViewNone{}, chead, sdf, D == 2, ring, s_film + 2 * H, s_wd, s_wc,
                                           s_ws, vx, vy, vz, STASH ? stash_s : nullptr, wave, lane,
                                           q4o STAMP_ARG);
         l = 2;
@@ -659,10 +434,10 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
         STAMP(1);   // sample setup + layer 0
       }
       for (; l < D; l += 2) {
-        mfma_layer<NT, TPS, false, STASH, F32>(Xh, Xl, Yh, Yl, FA, 0.f, chead, sdf, false, ring, s_film + l * 2 * H, s_wd, s_wc,
+        mfma_layer<NT, TPS, STASH, F32>(Xh, Xl, Yh, Yl, ViewNone{}, chead, sdf, false, ring, s_film + l * 2 * H, s_wd, s_wc,
                                           s_ws, vx, vy, vz, STASH ? stash_s + (int64_t)(l - 1) * 16 * H : nullptr, wave, lane,
                                           q4o STAMP_ARG);
-        mfma_layer<NT, TPS, false, STASH, F32>(Yh, Yl, Xh, Xl, FA, 0.f, chead, sdf, l + 1 == D - 1, ring, s_film + (l + 1) * 2 * H, s_wd, s_wc,
+        mfma_layer<NT, TPS, STASH, F32>(Yh, Yl, Xh, Xl, ViewNone{}, chead, sdf, l + 1 == D - 1, ring, s_film + (l + 1) * 2 * H, s_wd, s_wc,
                                           s_ws, vx, vy, vz, STASH ? stash_s + (int64_t)l * 16 * H : nullptr, wave, lane,
                                           q4o STAMP_ARG);
       }
@@ -670,7 +445,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     layer0(Xh, Xl);
     STAMP(1);   // sample setup + layer 0
     for (int l = 1; l < D; ++l) {
-      mfma_layer<NT, TPS, false, STASH, F32>(Xh, Xl, Yh, Yl, FA, 0.f, chead, sdf, l == D - 1, ring, s_film + l * 2 * H, s_wd, s_wc,
+      mfma_layer<NT, TPS, STASH, F32>(Xh, Xl, Yh, Yl, ViewNone{}, chead, sdf, l == D - 1, ring, s_film + l * 2 * H, s_wd, s_wc,
                                         s_ws, vx, vy, vz, STASH ? stash_s + (int64_t)(l - 1) * 16 * H : nullptr, wave, lane,
                                         q4o STAMP_ARG);
 #pragma unroll
@@ -699,7 +474,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     STAMP(3);   // sigma head + weight
     // ---- view layer -> features, folded into FA; rgb head partial sums
     float sdf_unused = 0.f;
-    mfma_layer<NT, TPS, true, STASH, F32>(Xh, Xl, Yh, Yl, FA, w, chead, sdf_unused, false, ring, s_film + D * 2 * H, s_wd, s_wc, s_ws,
+    mfma_layer<NT, TPS, STASH, F32>(Xh, Xl, Yh, Yl, ViewComposite<NT>{FA, w}, chead, sdf_unused, false, ring, s_film + D * 2 * H, s_wd, s_wc, s_ws,
                                      vx, vy, vz, STASH ? stash_s + (int64_t)(D - 1) * 16 * H : nullptr, wave, lane,
                                      q4o STAMP_ARG);
     float c0 = chead[0], c1 = chead[1], c2 = chead[2];
@@ -1089,9 +864,7 @@ extern "C" int cips3d_nerf_render(const cips3d_nerf_params* p, void* stream) {
   NerfArgs a;
   a.p = P;
   if (zero_in_front) { a.p.zero_words = nullptr; a.p.n_zero_words = 0; }
-  a.groups = ceil_div(P.n_rays > 0 ? P.n_rays : P.img_size * P.img_size, RAYS);
-  a.tasks_per_view = ceil_div(a.groups * P.n_chunks, WAVES) * WAVES;
-  a.chunk = ceil_div(P.n_samples, P.n_chunks);
+  nerf_task_shape(P.n_rays > 0 ? P.n_rays : P.img_size * P.img_size, P.n_samples, P.n_chunks).to(a);
   a.fuse_finish = fuse;
   nerf_linspace_consts(P.n_samples, a.t_end, a.t_step);
   hipStream_t st = as_stream(stream);

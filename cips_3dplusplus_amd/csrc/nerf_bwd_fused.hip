@@ -10,9 +10,12 @@
 // next layer's B operand, weights streamed L2 -> LDS ring by LDS-DMA, split-fp16 products) and runs as two kernels around
 // the per-ray compositing backward:
 //
-//   nerf_stash_kernel   forward recompute.  Per MFMA layer the fp32 accumulators (W' x, before FiLM) are written to `stash`
-//                       in the wave's own register order (1 KiB per wave store, fully coalesced); per point it emits sdf,
-//                       the rgb logits and g = <d_features[:, ray], feature> -- all the compositing backward needs.
+//   nerf_stash_kernel   forward recompute: the render kernel's own layers (first_layer and mfma_layer<.., STASH = true> of
+//                       nerf_mlp.h, the instantiation the differentiable forward runs), so both fill the same stash.  Per MFMA
+//                       layer the fp32 accumulators (W' x, before FiLM) are written to `stash` in the wave's own register
+//                       order (1 KiB per wave store, fully coalesced); per point it emits sdf, the rgb logits and, where the
+//                       render composites the view layer's features, g = <d_features[:, ray], feature> (ViewGdot) -- all the
+//                       compositing backward needs.
 //   composite_kernel    (nerf_bwd.hip) volume integration forward + backward per ray -> w, d sdf, d rgb logits, d |rays_d|
 //                       (d_mask / d_xyz set: d loss / d w_k gains the geometry maps' share; per-ray sum w_k, sum w_k z_k)
 //   nerf_bwd_kernel     per 16-point tile, layers in reverse.  Epilogue of layer l (VALU):
@@ -186,16 +189,16 @@ __device__ __forceinline__ void stage_film(const cips3d_nerf_bwd_fused_params& P
   }
 }
 
-// the MFMA block of one slab step: acc[tt] += A(slab, tile tt) * (Xh + Xl), three fp16 products per fp32 product
+// the MFMA block of one slab step of the backward kernel: acc[tt] += A(slab, tile tt) * (Xh + Xl), three fp16 products per fp32 product
 template <int NT, int TPS>
 __device__ __forceinline__ void mfma_step(const float* slab, const h8 (&Xh)[NT / 2], const h8 (&Xl)[NT / 2], f32x4 (&acc)[TPS],
                                           int lane) {
-#ifdef CIPS3D_BWD_NO_MFMA       // timing-only ablation
+#ifdef CIPS3D_BWD_NO_MFMA       // timing-only ablation (the backward kernel only: the recompute runs nerf_mlp.h's layer)
   acc[0][0] += (float)Xh[0][0] + (float)Xl[NT / 2 - 1][1] + slab[lane];
   return;
 #endif
   constexpr int TILE = 16 * NT * 16;
-  // software-pipelined over half k-blocks (see nerf.hip:mfma_layer): the next half's fragments are requested before the current
+  // software-pipelined over half k-blocks (see nerf_mlp.h:mfma_layer): the next half's fragments are requested before the current
   // half's MFMAs, into the other of two fragment buffers
   constexpr int HT = TPS / 2 > 0 ? TPS / 2 : 1;
   constexpr int NH = TPS / HT;                    // halves per k-block
@@ -215,7 +218,7 @@ __device__ __forceinline__ void mfma_step(const float* slab, const h8 (&Xh)[NT /
   for (int g = 0; g < NG; ++g) {
     const int m = g / NH, half = g % NH, cur = g & 1;
 #pragma unroll
-    for (int t = 0; t < HT; ++t) asm volatile("" : "+v"(fh[cur][t]), "+v"(fl[cur][t]));   // the wait sits here (nerf.hip)
+    for (int t = 0; t < HT; ++t) asm volatile("" : "+v"(fh[cur][t]), "+v"(fl[cur][t]));   // the wait sits here (nerf_mlp.h)
     if (g + 1 < NG) load_half(cur ^ 1, g + 1);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -237,96 +240,6 @@ __device__ __forceinline__ void step_wait_barrier() {
 }
 
 // ------------------------------------------------------------------------------------------------ forward recompute + stash
-// One MFMA layer (forward), see nerf.hip:mfma_layer.  Differences: the accumulators go to `stash_l` (after the step barrier,
-// so that no store acknowledgement is waited for at it), the view layer accumulates gdot = <dF, f> instead of compositing.
-template <int NT, int TPS, bool VIEW>
-__device__ __forceinline__ void stash_layer(const h8 (&Xh)[NT / 2], const h8 (&Xl)[NT / 2], h8 (&Yh)[NT / 2], h8 (&Yl)[NT / 2],
-                                            float& gdot, float (&chead)[3], float& sdf_acc, bool last, Ring& ring,
-                                            const float* film_l, const float* s_wd, const float* s_wc, const float* s_ws,
-                                            const float* dF_ray, float* stash_l, float vx, float vy, float vz, int wave,
-                                            int lane, int q4o) {
-  constexpr int H = NT * 16;
-  constexpr int SLAB = 16 * H * TPS;
-  constexpr int STEPS = NT / TPS;
-  constexpr int R = TPS * 4;
-  constexpr int BPS = TPS / 2;
-  const bool late = __builtin_amdgcn_readfirstlane(wave) >= WAVES / 2;
-#pragma unroll
-  for (int sl = 0; sl < STEPS; ++sl) {
-    if (ring.seq + 1 < ring.seq_end) {
-      const int nxt = (ring.seq + 1) % ring.per_sample;
-      stage_slab<SLAB>(ring.packed + (int64_t)nxt * SLAB, ring.lds + ((ring.seq + 1) & 1) * SLAB, wave, lane);
-    }
-    const float* slab = ring.lds + (ring.seq & 1) * SLAB;
-    const int o_base = sl * (TPS * 16) + q4o;
-    f32x4 acc[TPS];
-    float vxo = vx, vyo = vy, vzo = vz;
-    if (VIEW) asm volatile("" : "+v"(vxo), "+v"(vyo), "+v"(vzo));
-#pragma unroll
-    for (int tt = 0; tt < TPS; ++tt) {
-      const int o4 = o_base + tt * 16;
-      if (VIEW) {
-        const f32x4 wx = *reinterpret_cast<const f32x4*>(s_wd + o4);
-        const f32x4 wy = *reinterpret_cast<const f32x4*>(s_wd + H + o4);
-        const f32x4 wz = *reinterpret_cast<const f32x4*>(s_wd + 2 * H + o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[tt][i] = fmaf(wz[i], vzo, fmaf(wy[i], vyo, wx[i] * vxo));
-      } else {
-        acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-    mfma_step<NT, TPS>(slab, Xh, Xl, acc, lane);
-    if (late) step_wait_barrier();
-    float res[R];
-#pragma unroll
-    for (int tt = 0; tt < TPS; ++tt) {
-      const int o4 = o_base + tt * 16;
-      const f32x4 g4 = *reinterpret_cast<const f32x4*>(film_l + o4);
-      const f32x4 c4 = *reinterpret_cast<const f32x4*>(film_l + H + o4);
-      if (VIEW) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(s_wc + o4);
-        const f32x4 w1 = *reinterpret_cast<const f32x4*>(s_wc + H + o4);
-        const f32x4 w2 = *reinterpret_cast<const f32x4*>(s_wc + 2 * H + o4);
-        const f32x4 d4 = *reinterpret_cast<const f32x4*>(dF_ray + o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float f = FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
-          gdot = fmaf(d4[i], f, gdot);
-          chead[0] = fmaf(w0[i], f, chead[0]);
-          chead[1] = fmaf(w1[i], f, chead[1]);
-          chead[2] = fmaf(w2[i], f, chead[2]);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) res[tt * 4 + i] = FILM_SIN(fmaf(g4[i], acc[tt][i], c4[i]));
-        if (last) {
-          const f32x4 ws4 = *reinterpret_cast<const f32x4*>(s_ws + o4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sdf_acc = fmaf(ws4[i], res[tt * 4 + i], sdf_acc);
-        }
-      }
-    }
-    if (VIEW) {
-      asm volatile("" : "+v"(chead[0]), "+v"(chead[1]), "+v"(chead[2]), "+v"(gdot));
-    } else {
-#pragma unroll
-      for (int k = 0; k < R; ++k) asm volatile("" : "+v"(res[k]));
-#pragma unroll
-      for (int bb = 0; bb < BPS; ++bb) {
-        float v8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v8[j] = res[(2 * bb) * 4 + j];
-        split8(v8, Yh[sl * BPS + bb], Yl[sl * BPS + bb]);
-      }
-    }
-    if (!late) step_wait_barrier();
-    // the step's accumulators, in register order: [sl * TPS + tt][lane][4]
-#pragma unroll
-    for (int tt = 0; tt < TPS; ++tt) *reinterpret_cast<f32x4*>(stash_l + ((sl * TPS + tt) * 64 + lane) * 4) = acc[tt];
-    ++ring.seq;
-  }
-}
-
 template <int NT, int TPS>
 __global__ void __launch_bounds__(WAVES * 64, 2) nerf_stash_kernel(FusedArgs a) {
   constexpr int H = NT * 16;
@@ -395,35 +308,12 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_stash_kernel(FusedArgs a) 
 
     h8 Xh[NT / 2], Xl[NT / 2], Yh[NT / 2], Yl[NT / 2];
     float sdf = 0.f;
-#pragma unroll
-    for (int m = 0; m < NT / 2; ++m) {
-      float v8[8];
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int o4 = (2 * m + hf) * 16 + q4o;
-        const f32x4 wx = *reinterpret_cast<const f32x4*>(s_w0 + o4);
-        const f32x4 wy = *reinterpret_cast<const f32x4*>(s_w0 + H + o4);
-        const f32x4 wz = *reinterpret_cast<const f32x4*>(s_w0 + 2 * H + o4);
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(s_film + o4);
-        const f32x4 c4 = *reinterpret_cast<const f32x4*>(s_film + H + o4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float pre = fmaf(wz[i], nz, fmaf(wy[i], ny, wx[i] * nx));
-          v8[hf * 4 + i] = FILM_SIN(fmaf(g4[i], pre, c4[i]));
-        }
-        if (D == 1) {
-          const f32x4 ws4 = *reinterpret_cast<const f32x4*>(s_ws + o4);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sdf = fmaf(ws4[i], v8[hf * 4 + i], sdf);
-        }
-      }
-      split8(v8, Xh[m], Xl[m]);
-    }
+    first_layer<NT, false>(Xh, Xl, sdf, D == 1, s_film, s_w0, s_ws, nx, ny, nz, q4o);
     float chead[3] = {0.f, 0.f, 0.f};
     float gdot = 0.f;
     for (int l = 1; l < D; ++l) {
-      stash_layer<NT, TPS, false>(Xh, Xl, Yh, Yl, gdot, chead, sdf, l == D - 1, ring, s_film + l * 2 * H, s_wd, s_wc, s_ws,
-                                  dF_ray, stash_s + (int64_t)(l - 1) * 16 * H, ry.vx, ry.vy, ry.vz, wave, lane, q4o);
+      mfma_layer<NT, TPS, true>(Xh, Xl, Yh, Yl, ViewNone{}, chead, sdf, l == D - 1, ring, s_film + l * 2 * H, s_wd, s_wc, s_ws,
+                                       ry.vx, ry.vy, ry.vz, stash_s + (int64_t)(l - 1) * 16 * H, wave, lane, q4o);
 #pragma unroll
       for (int i = 0; i < NT / 2; ++i) { Xh[i] = Yh[i]; Xl[i] = Yl[i]; }
     }
@@ -431,8 +321,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_stash_kernel(FusedArgs a) 
     sdf += __shfl_xor(sdf, 32, 64);
     sdf += b_sigma;
     float sdf_unused = 0.f;
-    stash_layer<NT, TPS, true>(Xh, Xl, Yh, Yl, gdot, chead, sdf_unused, false, ring, s_film + D * 2 * H, s_wd, s_wc, s_ws,
-                               dF_ray, stash_s + (int64_t)(D - 1) * 16 * H, ry.vx, ry.vy, ry.vz, wave, lane, q4o);
+    mfma_layer<NT, TPS, true>(Xh, Xl, Yh, Yl, ViewGdot{dF_ray, gdot}, chead, sdf_unused, false, ring, s_film + D * 2 * H, s_wd,
+                                    s_wc, s_ws, ry.vx, ry.vy, ry.vz, stash_s + (int64_t)(D - 1) * 16 * H, wave, lane, q4o);
     float c0 = chead[0], c1 = chead[1], c2 = chead[2];
     c0 += __shfl_xor(c0, 16, 64); c1 += __shfl_xor(c1, 16, 64); c2 += __shfl_xor(c2, 16, 64); gdot += __shfl_xor(gdot, 16, 64);
     c0 += __shfl_xor(c0, 32, 64); c1 += __shfl_xor(c1, 32, 64); c2 += __shfl_xor(c2, 32, 64); gdot += __shfl_xor(gdot, 32, 64);
@@ -890,10 +780,8 @@ extern "C" int cips3d_nerf_bwd_fused_supported(int hidden, int depth, int img_si
 
 extern "C" int64_t cips3d_nerf_bwd_fused_stash_floats(int B, int img_size, int n_samples, int hidden, int depth, int n_chunks) {
   if (B <= 0 || img_size <= 0 || n_samples <= 0 || hidden <= 0 || depth <= 0 || n_chunks <= 0) return 0;
-  const int64_t groups = ceil_div<int64_t>((int64_t)img_size * img_size, RAYS);
-  const int64_t tasks_per_view = ceil_div<int64_t>(groups * n_chunks, WAVES) * WAVES;
-  const int64_t chunk = ceil_div(n_samples, n_chunks);
-  return (int64_t)B * tasks_per_view * chunk * depth * 16 * hidden;
+  const NerfTaskShape ts = nerf_task_shape((int64_t)img_size * img_size, n_samples, n_chunks);
+  return (int64_t)B * ts.tasks_per_view * ts.chunk * depth * 16 * hidden;
 }
 
 extern "C" int64_t cips3d_nerf_bwd_fused_scratch_floats(int B, int img_size, int n_samples, int hidden, int depth) {
@@ -930,9 +818,7 @@ extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, voi
   const int64_t R = (int64_t)G.img_size * G.img_size, Pn = R * G.n_samples;
   FusedArgs a;
   a.p = P;
-  a.groups = (int)(R / RAYS);
-  a.tasks_per_view = ceil_div(a.groups * P.n_chunks, WAVES) * WAVES;
-  a.chunk = ceil_div(G.n_samples, P.n_chunks);
+  nerf_task_shape(R, G.n_samples, P.n_chunks).to(a);        // (R % 16 == 0: whole groups)
   nerf_linspace_consts(G.n_samples, a.t_end, a.t_step);
   float* s = P.scratch;
   auto take = [&](int64_t n) { float* r = s; s += align4(n); return r; };

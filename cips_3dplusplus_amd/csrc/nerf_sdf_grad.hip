@@ -93,7 +93,7 @@ __device__ __forceinline__ void film_rows(const float* s_film, const float* __re
 }
 
 // One hidden layer for the wave's 16 columns: Y = act(W X), X / Y in the MFMA D layout (X[T][r] = unit 16 T + 4 q + r).  The slab
-// protocol is mfma_layer's (nerf.hip): slab `seq` is resident in slot seq & 1, every step prefetches seq + 1 while multiplying
+// protocol is mfma_layer's (nerf_mlp.h): slab `seq` is resident in slot seq & 1, every step prefetches seq + 1 while multiplying
 // and ends with wait + barrier; the upper half of the waves takes the barrier in front of its epilogue, so that it runs under
 // the partner wave's next matrix block.
 template <int NT, int TPS, bool FILM_LDS>

@@ -1420,11 +1420,13 @@ def nerf_forward_stash(B, img_size, n_samples, hidden, depth, device, n_chunks=N
 
 
 def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, film, layer_bias, packed, packed_t, img_size,
-                        n_samples, static_viewdirs, d_features, d_thumb, fwd=None, d_mask=None, d_xyz=None, xyz=None, n_chunks=None):
+                        n_samples, static_viewdirs, d_features, d_thumb, fwd=None, d_mask=None, d_xyz=None, xyz=None, n_chunks=None,
+                        stash=None):
     """The fused NeRF backward (csrc/nerf_bwd_fused.hip): returns (dfilm [B,L,2,H], dcam [B,3,4]); same contract as
     nerf_backward (d_mask / d_xyz / xyz included).  `fwd` = the nerf_forward_stash buffers a differentiable forward filled: the
     forward is then not recomputed.  `n_chunks` (without `fwd`, which carries its own): chunks a ray's samples are split into,
-    1 .. n_samples; None = nerf_suggest_chunks."""
+    1 .. n_samples; None = nerf_suggest_chunks.  `stash` (without `fwd`): a float32 buffer of cips3d_nerf_bwd_fused_stash_floats
+    floats that the forward recompute fills instead of a private allocation."""
     lib = _lib.load()
     dev = cam_poses.device
     B, H, D = cam_poses.shape[0], net.W, net.D
@@ -1439,6 +1441,8 @@ def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb
     g.perturb_u = dev_ptr(keep[4], "perturb_u", True)
     g.B, g.img_size, g.n_samples, g.static_viewdirs = B, img_size, n_samples, int(bool(static_viewdirs))
     if fwd is not None:
+        if stash is not None:
+            raise ValueError("stash= is the recompute route's buffer: with fwd= the forward's own stash is read")
         if n_chunks is not None and int(n_chunks) != fwd["n_chunks"]:
             raise ValueError(f"n_chunks = {n_chunks}, but the forward filled its stash for {fwd['n_chunks']} chunks")
         n_chunks, stash = fwd["n_chunks"], fwd["stash"]
@@ -1449,7 +1453,11 @@ def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb
         n_chunks = int(n_chunks)
         if not 1 <= n_chunks <= n_samples:
             raise ValueError(f"n_chunks = {n_chunks}: must lie in 1 .. n_samples = {n_samples}")
-        stash = torch.empty(int(lib.cips3d_nerf_bwd_fused_stash_floats(B, img_size, n_samples, H, D, n_chunks)), device=dev)
+        n_stash = int(lib.cips3d_nerf_bwd_fused_stash_floats(B, img_size, n_samples, H, D, n_chunks))
+        if stash is None:
+            stash = torch.empty(n_stash, device=dev)
+        elif stash.dtype != torch.float32 or stash.device != dev or not stash.is_contiguous() or stash.numel() != n_stash:
+            raise ValueError(f"stash: a contiguous float32 buffer of {n_stash} floats on {dev} is needed")
     scratch = torch.empty(int(lib.cips3d_nerf_bwd_fused_scratch_floats(B, img_size, n_samples, H, D)), device=dev)
     dfilm, dcam = torch.empty(B, L, 2, H, device=dev), torch.empty(B, 3, 4, device=dev)
     p.w_first, p.packed, p.packed_t = dev_ptr(net.pts_linears[0].weight), dev_ptr(packed), dev_ptr(packed_t)

@@ -102,3 +102,35 @@ def test_stash_filled_by_the_forward_gives_the_same_gradients(hidden, depth, B, 
     f1, c1 = hip.nerf_backward_fused(*args, packed, r._packed_transposed(), S, N, False, dF, dT, fwd=fwd)
     assert float((f0 - f1).abs().max() / f0.abs().max()) < 1e-5
     assert float((c0 - c1).abs().max() / c0.abs().max()) < 1e-5
+
+
+@pytest.mark.parametrize("hidden,depth,B,S,N,n_chunks", [
+    (32, 1, 2, 4, 3, 2),       # no MFMA hidden layer: the stash holds the view layer alone
+    (32, 2, 2, 4, 3, 2),       # the odd single hidden layer (the render's Y -> X layer in front of the pairs)
+    (32, 3, 2, 4, 3, 2),       # the X -> Y -> X pair
+    (256, 2, 1, 4, 2, 1),      # the four-tile slab step
+])
+def test_render_and_recompute_fill_the_same_stash(hidden, depth, B, S, N, n_chunks):
+    """The two routes to the accumulator stash -- cips3d_nerf_render with cips3d_nerf_params.stash and the backward's forward
+    recompute (nerf_stash_kernel) -- run one forward layer (csrc/nerf_mlp.h: first_layer, mfma_layer) and write the same floats,
+    bit for bit, over the whole buffer: the rows of a ragged last chunk's padded samples and of a workgroup's idle tasks included
+    (both routes evaluate them at the same clamped inputs).  At 32 x 2 chunks 6 of a view's 8 tasks are idle and the second
+    chunk holds one real sample of two."""
+    r, cam, focal, near, far, film = _setup(hidden, depth, B, S)
+    H = r.hidden_dim
+    u = weights.det_unit_uniform("nbf.u3", (B, S, S, 1), 2).to(DEV)
+    dF = (1e-4 * weights.det_normal("nbf.dF3", (B, H, S, S), 1.0, 3)).to(DEV)
+    dT = (1e-3 * weights.det_normal("nbf.dT3", (B, 3, S, S), 1.0, 4)).to(DEV)
+    packed, layer_bias = r._derived_buffers()
+    fwd = hip.nerf_forward_stash(B, S, N, H, depth, DEV, n_chunks=n_chunks)
+    fwd["stash"].zero_()
+    buf = torch.zeros_like(fwd["stash"])
+    r.render(cam, focal, near, far, None, S, N, perturb_u=u, film=film, stash=fwd)
+    args = (r.network, r.sigmoid_beta.detach(), cam, focal, near, far, u, film, layer_bias, packed, r._packed_transposed(), S, N,
+            False, dF, dT)
+    hip.nerf_backward_fused(*args, n_chunks=n_chunks, stash=buf)
+    assert buf.abs().max() > 0
+    differ = int((buf != fwd["stash"]).sum())
+    assert torch.equal(buf, fwd["stash"]), f"{differ} of {buf.numel()} stash floats differ"
+    with pytest.raises(ValueError):
+        hip.nerf_backward_fused(*args, fwd=fwd, stash=buf)
