@@ -48,6 +48,27 @@ class ReduceJob(C.Structure):
                 ("n4", C.c_int64), ("HW4", C.c_int64), ("slot_stride", C.c_int64), ("n_slots", C.c_int32), ("n_bias", C.c_int32)]
 
 
+# cips3d_dec_layer.flags (CIPS3D_DEC_*)
+DEC_CHAINED, DEC_SPLIT, DEC_PLANES_IN, DEC_PLANES_OUT, DEC_SPLIT16, DEC_P16, DEC_DEMOD, DEC_FLAT_HEAD = 1, 2, 4, 8, 16, 32, 64, 128
+# cips3d_dec_step.kind (CIPS3D_STEP_*), in this order from 0, and .form
+STEP_KINDS = ("lowres_gemm", "fused_stage", "planes_gemm", "gemm", "gemm_fir", "torgb", "flush")
+STEP_FUSED_STAGE = STEP_KINDS.index("fused_stage")
+STEP_FORMS = {1: "planes", 2: "p16", 4: "flat", 8: "chain", 16: "last", 32: "fold", 64: "ride"}
+TORGB_FOLD_MAX = 8              # CIPS3D_TORGB_FOLD_MAX
+MAX_DEC_STEPS = 80              # CIPS3D_MAX_DEC_STEPS
+
+
+class DecRouteOpts(C.Structure):
+    """cips3d_dec_route_opts (include/cips3d_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("B", "nerf_res", "mode", "chain_stages", "flat_stages", "planes_run", "planes16_run", "pad_")]
+
+
+class DecStep(C.Structure):
+    """cips3d_dec_step (include/cips3d_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "layer", "form", "out_format", "slot", "n_bias", "H", "W")] + [
+        ("bias_layer", C.c_int32 * TORGB_FOLD_MAX), ("mark", C.c_int32 * 4)]
+
+
 class AdamEntry(C.Structure):
     """cips3d_adam_entry (include/cips3d_hip.h)."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
@@ -288,6 +309,10 @@ _SIGS = {
     "cips3d_nerf_bwd_fused": (c_int, [C.c_void_p, C.c_void_p]),
     "cips3d_generator_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_style_phase": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
+    "cips3d_decoder_route_flags": (c_int, [C.c_void_p, c_int, C.POINTER(DecRouteOpts), C.POINTER(c_i64)]),
+    "cips3d_decoder_steps": (c_int, [C.c_void_p, c_int, c_int, c_int, c_i64, C.POINTER(DecStep), c_int]),
+    "cips3d_modconv1x1_torgb_blocks": (c_int, [c_int, c_int, c_int, c_i64]),
+    "cips3d_planes_torgb_blocks": (c_int, [c_int]),
     "cips3d_sqdiff_pair_partials": (c_int, [C.c_int64, C.c_int64]),
     "cips3d_sqdiff_pair": (c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -353,7 +378,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 41           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 42           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -362,7 +387,8 @@ def _struct_table():
     from . import plan
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
-            11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO}
+            11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO, 17: DecRouteOpts,
+            18: DecStep}
 
 
 def load(build_if_missing=True):

@@ -638,6 +638,9 @@ extern "C" int cips3d_planes_supported(int Cin, int Cout, int64_t HW) {
          (int64_t)(Cin > Cout ? Cin : Cout) * HW * 2 + 1024 < ((int64_t)1 << 31);
 }
 
+// row blocks of the ToRGB partial sums of a planes launch (one rgb_part slot each): 64-row slots, whatever the tile
+extern "C" int cips3d_planes_torgb_blocks(int Cout) { return Cout > 0 ? Cout / 64 : 0; }
+
 extern "C" int cips3d_to_planes(const float* x, void* planes, int B, int C, int64_t HW, const float* x_amax, int32_t* exp_out,
                                 float* pmax_out, void* stream) {
   if (!x || !planes || B < 0 || C <= 0 || HW <= 0 || ((x_amax == nullptr) != (exp_out == nullptr)) || (pmax_out && !x_amax))
@@ -690,7 +693,7 @@ extern "C" int cips3d_modconv1x1_planes16(const void* x_planes16, const float* w
                                           const float* noise_w, const float* bias, const float* rgb_w, float* rgb_part,
                                           int* n_row_blocks, const cips3d_range* rg, void* stream) {
   if ((rgb_w == nullptr) != (rgb_part == nullptr)) return CIPS3D_E_BADARG;
-  if (n_row_blocks) *n_row_blocks = Cout > 0 ? Cout / 64 : 0;
+  if (n_row_blocks) *n_row_blocks = cips3d_planes_torgb_blocks(Cout);
   if (!x_planes16 || !wm || !out || B < 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return CIPS3D_E_BADARG;
   if ((out_format != 0 && out_format != 2 && out_format != 3) || (epilogue != 0 && epilogue != 1) || (epilogue == 1 && !bias))
     return CIPS3D_E_BADARG;
@@ -713,7 +716,7 @@ extern "C" int cips3d_modconv1x1_planes(const void* x_planes, const float* wm, v
                                         const float* noise_w, const float* bias, const float* rgb_w, float* rgb_part,
                                         int* n_row_blocks, const cips3d_range* rg, void* stream) {
   if ((rgb_w == nullptr) != (rgb_part == nullptr)) return CIPS3D_E_BADARG;
-  if (n_row_blocks) *n_row_blocks = Cout > 0 ? Cout / 64 : 0;
+  if (n_row_blocks) *n_row_blocks = cips3d_planes_torgb_blocks(Cout);
   if (!x_planes || !wm || !out || B < 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return CIPS3D_E_BADARG;
   if (out_format < 0 || out_format > 2 || (epilogue != 0 && epilogue != 1) || (epilogue == 1 && !bias)) return CIPS3D_E_BADARG;
   if (!cips3d_planes_supported(Cin, Cout, HW)) return CIPS3D_E_UNSUPP;

@@ -34,6 +34,8 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 14: return (int64_t)sizeof(cips3d_vgg_split_ctx);
     case 15: return (int64_t)sizeof(cips3d_vgg_split_io);
     case 16: return (int64_t)sizeof(cips3d_lpips_io);
+    case 17: return (int64_t)sizeof(cips3d_dec_route_opts);
+    case 18: return (int64_t)sizeof(cips3d_dec_step);
     default: return -1;
   }
 }
@@ -158,17 +160,16 @@ extern "C" int cips3d_generator_forward(const cips3d_generator_plan* plan, const
   if (!IO.cam_poses || !IO.focals || !IO.near_ || !IO.far_ || !IO.rgb || !IO.thumb || !IO.xyz || !IO.mask)
     return CIPS3D_E_BADARG;
   const int B = P.B;
-  if (IO.rgb_is_u8) {      // a uint8 image leaves through a fused stage only: decided before anything is enqueued
-    const int n = P.n_dec_layers;
-    bool ok = n >= 3 && P.layers[n - 2].kind == 0 && P.layers[n - 2].Cin == P.layers[n - 3].Cout &&
-              P.layers[n - 2].Cout == P.layers[n - 3].Cout && P.layers[n - 1].Cin == P.layers[n - 3].Cout;
-    if (ok) {
-      const cips3d_dec_layer& h = P.layers[n - 3];
-      ok = (h.kind == 1 && P.layers[n - 1].kind == 3 && cips3d_fused_up_conv_supported(h.Cout, h.H, h.W)) ||
-           (h.kind == 0 && (h.flags & 128) && P.layers[n - 1].kind == 2 && cips3d_fused_flat_conv_supported(h.Cout, h.H, h.W));
-    }
-    if (!ok) return CIPS3D_E_UNSUPP;
-  }
+  const bool ranged = P.range_ws != nullptr;
+  // ---- the decoder's launches (decoder_route.hip): resolved from the layers' flags, and refused, before anything is enqueued
+  cips3d_dec_step steps[CIPS3D_MAX_DEC_STEPS];
+  const int n_steps = cips3d_decoder_steps(P.layers, P.n_dec_layers, B, ranged, P.rgb_part ? P.rgb_part_slots : 0, steps,
+                                           CIPS3D_MAX_DEC_STEPS);
+  if (n_steps < 0) return n_steps;
+  for (int k = 0; k < n_steps; ++k)       // a chained stage writes the next stage's y_lo while it reads its own
+    if ((steps[k].form & CIPS3D_STEP_CHAIN) && !P.y_lo2) return CIPS3D_E_BADARG;
+  // a uint8 image leaves through a fused stage only (a stand-alone ToRGB writes fp32)
+  if (IO.rgb_is_u8 && (n_steps == 0 || steps[n_steps - 1].kind != CIPS3D_STEP_FUSED_STAGE)) return CIPS3D_E_UNSUPP;
   const int gemm_flag = P.decoder_bf16 ? CIPS3D_GEMM_BF16 : 0;
   // decoder_bf16 == 2: the low-resolution GEMM results of the fused up-sampling stages (y_lo / y_next) live in HBM as bf16
   const int ybf_flag = P.decoder_bf16 == 2 ? CIPS3D_Y_BF16 : 0;
@@ -176,7 +177,6 @@ extern "C" int cips3d_generator_forward(const cips3d_generator_plan* plan, const
   // ---- mapping networks, FiLM heads, modulation heads, the call's draws (cips3d_style_phase); then the modulated weights:
   // the modulate table also writes every layer's range constants with this call's bound of |noise| (6: cips3d_rng_fill's
   // draws stay below 5.89).
-  const bool ranged = P.range_ws != nullptr;
   if (ranged && (P.range_ws_words <= 0 || P.range_ws_words > (1 << 30) || !P.feat_amax || !P.feat_exp || !P.tmp_amax)) return CIPS3D_E_BADARG;
   if (IO.styles_resident) {
     // a frame of a sequence: styles, FiLM / modulation tables and the modulated weights (with their range constants) are the
@@ -202,11 +202,11 @@ extern "C" int cips3d_generator_forward(const cips3d_generator_plan* plan, const
   np.o_features = P.features; np.o_thumb = IO.thumb; np.o_xyz = IO.xyz; np.o_mask = IO.mask;
   np.mask_planar = IO.mask_planar;
   const bool fused_finish = cips3d_nerf_fuses_finish(&np) != 0;
-  // the first decoder layer reads split-fp16 planes (flags bit 2): the render kernel's fused finish writes them directly,
-  // the stand-alone finish writes fp32 into the spare activation buffer and a conversion pass follows.  bf16 planes16
-  // (flags bit 5) always take the conversion pass.
-  const bool feat_planes = (P.layers[0].flags & 4) != 0;
-  const bool feat_p16 = feat_planes && (P.layers[0].flags & 32) != 0;
+  // the first decoder layer reads split-fp16 planes (CIPS3D_DEC_PLANES_IN): the render kernel's fused finish writes them
+  // directly, the stand-alone finish writes fp32 into the spare activation buffer and a conversion pass follows.  bf16 planes16
+  // (CIPS3D_DEC_P16) always take the conversion pass.
+  const bool feat_planes = (P.layers[0].flags & CIPS3D_DEC_PLANES_IN) != 0;
+  const bool feat_p16 = feat_planes && (P.layers[0].flags & CIPS3D_DEC_P16) != 0;
   np.features_planes = (feat_planes && !feat_p16 && fused_finish) ? 1 : 0;
   if (feat_planes && !feat_p16 && !ranged) return CIPS3D_E_BADARG;      // split-fp16 planes carry exponents: the plan owes the rows
   float* feat32 = (feat_planes && !np.features_planes) ? P.act[1] : P.features;
@@ -255,161 +255,120 @@ extern "C" int cips3d_generator_forward(const cips3d_generator_plan* plan, const
     x_amax = P.tmp_amax;
     return rc;
   };
+  // What the loop below owns is the running state that is about DATA: where x and the skip image live (act / skip / y_lo
+  // ping-pong), the range rows of x, and the ride job between a riding flush and the launch that carries it.  Which launch comes
+  // next, on which layers, in which form was decided above (steps).
   const float* skip = nullptr;
   int act_i = 0, skip_i = 0;
   float* ylo_cur = P.y_lo;                       // low-resolution GEMM result of the stage being run
   float* ylo_alt = P.y_lo2;                      // ... of the next stage, when the current stage's kernel computes it
-  bool ylo_ready = false;                        // ylo_cur was already filled by the previous stage's kernel
-  bool u8_done = false;                          // the final image left through a fused stage (the only form that writes uint8)
-  // ToRGB folding: a non-up-sampling ToRGB that follows a StyledConv is computed from that conv's registers (partial sums
-  // per row block, cips3d_modconv1x1_torgb); the slots of consecutive such layers are folded by ONE cips3d_torgb_reduce
-  // when their sum is first needed (the skip chain at an unchanged resolution is a plain sum).
-  int fold_slots = 0, fold_nb = 0, fold_H = 0, fold_W = 0;
-  const float* fold_bias[CIPS3D_TORGB_FOLD_MAX];
-  auto fold_flush = [&](float* dst) -> int {
-    if (fold_slots == 0) return 0;
-    const int rc = cips3d_torgb_reduce(P.rgb_part, fold_slots, fold_bias, fold_nb, skip, dst, B, (int64_t)fold_H * fold_W, stream);
-    mark(CIPS3D_MARK_TORGB, 0, 3, fold_H);
-    skip = dst;
-    fold_slots = fold_nb = 0;
-    return rc;
-  };
-  for (int li = 0; li < P.n_dec_layers; ++li) {
+  cips3d_reduce_job ride_job{};
+  bool ride = false;                             // ride_job is filled: the next step's launch carries it
+  for (int k = 0; k < n_steps; ++k) {
+    const cips3d_dec_step& S = steps[k];
+    const int li = S.layer;
     const cips3d_dec_layer& L = P.layers[li];
-    const bool last = li == P.n_dec_layers - 1;
-    if (L.kind == 0 || L.kind == 1) {
-      const float* nz = L.noise_index >= 0 ? IO.noise[L.noise_index] : nullptr;
-      const int64_t nbs = L.noise_index >= 0 ? IO.noise_bstride[L.noise_index] : 0;
-      float* out = P.act[act_i];
-      // resolution changes: the folded sum becomes the skip of this stage.  When the stage's low-resolution GEMM is the next
-      // launch and runs on split planes, the fold rides on it (cips3d_reduce_job) instead of taking a launch of its own
-      cips3d_reduce_job ride_job{};
-      bool ride = false;
-      if (L.kind == 1 && fold_slots) {
-        const bool fused_next = li + 2 < P.n_dec_layers && P.layers[li + 1].kind == 0 && P.layers[li + 2].kind == 3 &&
-                                P.layers[li + 1].Cin == L.Cout && P.layers[li + 1].Cout == L.Cout && P.layers[li + 2].Cin == L.Cout &&
-                                cips3d_fused_up_conv_supported(L.Cout, L.H, L.W);
-        const int64_t fhw = (int64_t)fold_H * fold_W;
-        if (ranged && fused_next && !ylo_ready && (L.flags & 4) && !(L.flags & 32) && fold_slots <= 48 && fhw % 4 == 0 &&
-            (int64_t)B * 3 * fhw / 4 <= ((int64_t)L.H * L.W + 127) / 128 * B * 128) {
+    const int64_t hw = (int64_t)L.H * L.W;
+    const float* nz = L.noise_index >= 0 ? IO.noise[L.noise_index] : nullptr;
+    const int64_t nbs = L.noise_index >= 0 ? IO.noise_bstride[L.noise_index] : 0;
+    float* out = P.act[act_i];
+    const int split_flag = (L.flags & CIPS3D_DEC_SPLIT) ? CIPS3D_GEMM_SPLIT : 0;
+    // a fused stage [L, L2, L3]; ranged: y_lo's maximum lives in the head's amax row (written by whoever computes y_lo)
+    const bool staged = S.kind == CIPS3D_STEP_LOWRES_GEMM || S.kind == CIPS3D_STEP_FUSED_STAGE;
+    const bool stage_ranged = staged && ranged && L.amax && L.lconst && P.layers[li + 1].lconst;
+    switch (S.kind) {
+      case CIPS3D_STEP_FLUSH: {
+        // the sum of the folded ToRGBs' slots (+ their biases + the skip so far) becomes the skip image
+        float* dst = P.skip[skip_i];
+        const int64_t fhw = (int64_t)S.H * S.W;
+        const float* bias[CIPS3D_TORGB_FOLD_MAX];
+        for (int b = 0; b < S.n_bias; ++b) bias[b] = P.layers[S.bias_layer[b]].bias;
+        if (S.form & CIPS3D_STEP_RIDE) {           // ... by the low-resolution GEMM that follows (cips3d_reduce_job)
+          ride_job = cips3d_reduce_job{};
           ride_job.part = P.rgb_part;
-          for (int k = 0; k < fold_nb; ++k) ride_job.bias[k] = fold_bias[k];
+          for (int b = 0; b < S.n_bias; ++b) ride_job.bias[b] = bias[b];
           ride_job.skip = skip;
-          ride_job.out = P.skip[skip_i];
+          ride_job.out = dst;
           ride_job.n4 = (int64_t)B * 3 * fhw / 4;
           ride_job.HW4 = fhw / 4;
           ride_job.slot_stride = (int64_t)B * 3 * fhw;
-          ride_job.n_slots = fold_slots;
-          ride_job.n_bias = fold_nb;
+          ride_job.n_slots = S.slot;
+          ride_job.n_bias = S.n_bias;
           ride = true;
-          skip = P.skip[skip_i];
-          fold_slots = fold_nb = 0;
         } else {
-          TRY(fold_flush(P.skip[skip_i]));
+          TRY(cips3d_torgb_reduce(P.rgb_part, S.slot, bias, S.n_bias, skip, dst, B, fhw, stream));
         }
+        skip = dst;
         skip_i ^= 1;
+        break;
       }
-      // up-sampling stage [StyledConv(up), StyledConv, ToRGB(up)] with equal widths: low-res GEMM, then ONE fused
-      // kernel for FIR + act -> conv2 + act -> ToRGB (+ FIR-upsampled skip); the full-resolution intermediate
-      // never reaches HBM and the last stage stores only the image.
-      // FLAT stage (flags bit 7, set by the plan): [StyledConv, StyledConv, ToRGB] of equal widths at one resolution -- a block
-      // above the last up-sampling one (model_v3.py:553-590 builds every block up to size_end) -- through the same kernel
-      // without the FIR (CIPS3D_STAGE_FLAT): conv1's GEMM, then one launch; chained with its neighbours like the others.
-      const bool same_w = li + 2 < P.n_dec_layers && P.layers[li + 1].kind == 0 && P.layers[li + 1].Cin == L.Cout &&
-                          P.layers[li + 1].Cout == L.Cout && P.layers[li + 2].Cin == L.Cout;
-      const bool flat = L.kind == 0 && (L.flags & 128);
-      if (flat && (!same_w || P.layers[li + 2].kind != 2 || (L.flags & 4) || !cips3d_fused_flat_conv_supported(L.Cout, L.H, L.W)))
-        return CIPS3D_E_BADARG;                      // the plan promised a block this kernel takes
-      if (flat && fold_slots) {                      // (a pending fold of ToRGB partial sums becomes this block's skip image)
-        TRY(fold_flush(P.skip[skip_i]));
-        skip_i ^= 1;
+      case CIPS3D_STEP_LOWRES_GEMM: {
+        cips3d_range rg{};
+        rg.out_amax = stage_ranged ? L.amax : nullptr;
+        if (S.form & CIPS3D_STEP_P16)              // the run's last activation arrives as planes16 (bf16 mode)
+          TRY(cips3d_modconv1x1_planes16(x, L.wm, ylo_cur, ybf_flag ? 2 : 0, B, L.Cin, L.Cout, hw, 0, nullptr, 0,
+                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream));
+        else if (S.form & CIPS3D_STEP_PLANES) {    // ... as split-fp16 planes
+          rg.x_exp = x_exp;
+          rg.x_exp_const = CIPS3D_FEATURES_EXP;
+          rg.ride = ride ? &ride_job : nullptr;
+          TRY(cips3d_modconv1x1_planes(x, L.wm, ylo_cur, ybf_flag ? 2 : 0, B, L.Cin, L.Cout, hw, 0, nullptr, 0,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, ranged ? &rg : nullptr, stream));
+          ride = false;
+        } else {
+          if (split_flag) TRY(amax_of(x, L.Cin, hw));
+          rg.x_amax = x_amax;
+          TRY(cips3d_modconv1x1(x, L.wm, ylo_cur, B, L.Cin, L.Cout, hw, 0 | gemm_flag | ybf_flag | split_flag, nullptr, 0, nullptr,
+                                nullptr, ranged ? &rg : nullptr, stream));
+        }
+        break;
       }
-      if (flat || (L.kind == 1 && same_w && P.layers[li + 2].kind == 3 && cips3d_fused_up_conv_supported(L.Cout, L.H, L.W))) {
-        const int OHs = flat ? L.H : 2 * L.H, OWs = flat ? L.W : 2 * L.W;       // the stage's output resolution
+      case CIPS3D_STEP_FUSED_STAGE: {
+        // FIR + act -> conv2 + act -> ToRGB (+ FIR-upsampled skip) on y_lo; CIPS3D_STEP_FLAT: the same without the FIR
+        const bool flat = (S.form & CIPS3D_STEP_FLAT) != 0, stage_last = (S.form & CIPS3D_STEP_LAST) != 0;
         const cips3d_dec_layer& L2 = P.layers[li + 1];
         const cips3d_dec_layer& L3 = P.layers[li + 2];
-        const bool stage_last = li + 2 == P.n_dec_layers - 1;
         const float* nz2 = L2.noise_index >= 0 ? IO.noise[L2.noise_index] : nullptr;
         const int64_t nbs2 = L2.noise_index >= 0 ? IO.noise_bstride[L2.noise_index] : 0;
-        if ((L.flags & 1) && !ylo_ready) return CIPS3D_E_BADARG;     // chained weights without the stage that chains them
-        // ranged: y_lo's maximum lives in the up-conv's amax row (written by whoever computes y_lo)
-        const bool stage_ranged = ranged && L.amax && L.lconst && L2.lconst;
-        if (!ylo_ready) {
-          cips3d_range rg{};
-          rg.out_amax = stage_ranged ? L.amax : nullptr;
-          if ((L.flags & 4) && (L.flags & 32))       // the run's last activation arrives as planes16 (bf16 mode)
-            TRY(cips3d_modconv1x1_planes16(x, L.wm, ylo_cur, ybf_flag ? 2 : 0, B, L.Cin, L.Cout, (int64_t)L.H * L.W, 0, nullptr, 0,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream));
-          else if (L.flags & 4) {  // ... as split-fp16 planes
-            rg.x_exp = x_exp;
-            rg.x_exp_const = CIPS3D_FEATURES_EXP;
-            rg.ride = ride ? &ride_job : nullptr;
-            TRY(cips3d_modconv1x1_planes(x, L.wm, ylo_cur, ybf_flag ? 2 : 0, B, L.Cin, L.Cout, (int64_t)L.H * L.W, 0, nullptr, 0,
-                                         nullptr, nullptr, nullptr, nullptr, nullptr, ranged ? &rg : nullptr, stream));
-            ride = false;
-          } else {
-            if (L.flags & 2) TRY(amax_of(x, L.Cin, (int64_t)L.H * L.W));
-            rg.x_amax = x_amax;
-            TRY(cips3d_modconv1x1(x, L.wm, ylo_cur, B, L.Cin, L.Cout, (int64_t)L.H * L.W,
-                                  0 | gemm_flag | ybf_flag | ((L.flags & 2) ? CIPS3D_GEMM_SPLIT : 0), nullptr, 0, nullptr, nullptr,
-                                  ranged ? &rg : nullptr, stream));
-          }
-          mark(CIPS3D_MARK_LOWRES_GEMM, L.Cin, L.Cout, L.H);
-        }
-        // the next stage's 1x1 up-conv reads nothing but this stage's output: when the plan packed its weights for it
-        // (flags bit 0) this kernel computes that GEMM from its registers and the activations are never stored
-        const cips3d_dec_layer* LN = li + 3 < P.n_dec_layers ? &P.layers[li + 3] : nullptr;
-        const bool ln_head = LN && (LN->kind == 1 || (LN->kind == 0 && (LN->flags & 128)));
-        const bool chain = ln_head && (LN->flags & 1) && LN->Cin == L.Cout && LN->Cout * 2 == L.Cout &&
-                           LN->H == OHs && LN->W == OWs && ylo_alt && cips3d_fused_up_conv_chains(L.Cout);
-        if (ln_head && (LN->flags & 1) && !chain) return CIPS3D_E_BADARG;
-        float* out2 = (stage_last || chain) ? nullptr : P.act[act_i];
+        // CIPS3D_STEP_CHAIN: the next stage's head reads nothing but this stage's output and its weights are packed for this kernel,
+        // which computes that GEMM from its registers: the activations are never stored
+        const cips3d_dec_layer* LN = (S.form & CIPS3D_STEP_CHAIN) ? &P.layers[li + 3] : nullptr;
+        float* out2 = (stage_last || LN) ? nullptr : out;
         float* rgb = stage_last ? IO.rgb : P.skip[skip_i];
         const int u8_flag = (stage_last && IO.rgb_is_u8) ? CIPS3D_RGB_U8 : 0;
-        if (stage_last) u8_done = true;
-        // flags bit 4: conv2's (and the chained up-conv's) weights are CIPS3D_MOD_SPLIT16-packed: the stage runs split-fp16
-        const int stage_split = (L2.flags & 16) ? CIPS3D_GEMM_SPLIT : 0;
-        if (chain && ((LN->flags & 16) != (L2.flags & 16))) return CIPS3D_E_BADARG;
-        if (stage_split && ranged && (!stage_ranged || (chain && !LN->amax))) return CIPS3D_E_BADARG;   // the plan owes the rows
+        // conv2's (and the chained head's) weights are CIPS3D_MOD_SPLIT16-packed: the stage runs split-fp16
+        const int stage_split = (L2.flags & CIPS3D_DEC_SPLIT16) ? CIPS3D_GEMM_SPLIT : 0;
+        if (stage_split && ranged && (!stage_ranged || (LN && !LN->amax))) return CIPS3D_E_BADARG;   // the plan owes the rows
         cips3d_range srg{};
         if (stage_ranged) {
           srg.x_amax = L.amax; srg.lconst = L.lconst; srg.lconst2 = L2.lconst;
-          srg.next_amax = chain ? LN->amax : nullptr;
+          srg.next_amax = LN ? LN->amax : nullptr;
           // The stage that feeds the LAST up-sampling stage publishes the bound of |y_next| instead of measuring it: that
           // consumer splits once more (act1) and nothing after it, so ~2^8 of slack is harmless there, and the measurement is
           // dearest exactly here (one reduction + atomic per workgroup, 4096 workgroups at C = 64: 4 us).  A non-demodulated
           // next up-conv has no sqrt(C) row bound: measured then.
-          const bool ln_last = chain && li + 6 >= P.n_dec_layers;
-          srg.next_gain = (ln_last && (LN->flags & 64)) ? sqrtf((float)L.Cout) : 0.f;
+          const bool ln_last = LN && li + 6 >= P.n_dec_layers;
+          srg.next_gain = (ln_last && (LN->flags & CIPS3D_DEC_DEMOD)) ? sqrtf((float)L.Cout) : 0.f;
         }
         TRY(cips3d_fused_up_conv_next(ylo_cur, L.fir, nz, nbs, L.noise_w, L.bias, L2.wm, nz2, nbs2, L2.noise_w, L2.bias, out2,
-                                      L3.wm, L3.bias, skip, (flat ? CIPS3D_STAGE_FLAT : 1) | gemm_flag | ybf_flag | stage_split | u8_flag, rgb, chain ? LN->wm : nullptr,
-                                      chain ? ylo_alt : nullptr, B, L.Cout, L.H, L.W, stage_ranged ? &srg : nullptr, stream));
-        mark(CIPS3D_MARK_FUSED_STAGE, L.Cout, chain ? LN->Cout : 0, OHs);
-        ylo_ready = chain;
-        if (chain) { float* t = ylo_cur; ylo_cur = ylo_alt; ylo_alt = t; }
+                                      L3.wm, L3.bias, skip, (flat ? CIPS3D_STAGE_FLAT : 1) | gemm_flag | ybf_flag | stage_split | u8_flag, rgb, LN ? LN->wm : nullptr,
+                                      LN ? ylo_alt : nullptr, B, L.Cout, L.H, L.W, stage_ranged ? &srg : nullptr, stream));
+        if (LN) { float* t = ylo_cur; ylo_cur = ylo_alt; ylo_alt = t; }
         x = out2;
         x_amax = nullptr;                // (a stored out2 is not tracked: its reader measures it)
         x_exp = nullptr;
         act_i ^= 1;
         skip = rgb;
         skip_i ^= 1;
-        li += 2;
-        continue;
+        break;
       }
-      if (L.kind == 0 && (L.flags & 4)) {
-        // a layer of the split-fp16 run (csrc/chain.hip): planes in; planes out (flags bit 3) with the ToRGB that follows
-        // folded from the registers -- nothing else may read this activation
-        const cips3d_dec_layer* T = li + 1 < P.n_dec_layers ? &P.layers[li + 1] : nullptr;
-        const int64_t hw = (int64_t)L.H * L.W;
-        const bool has_rgb = T && T->kind == 2;
-        const bool fold = has_rgb && li + 1 != P.n_dec_layers - 1 && T->Cin == L.Cout && P.rgb_part &&
-                          fold_nb < CIPS3D_TORGB_FOLD_MAX && fold_slots + 16 <= P.rgb_part_slots &&
-                          (fold_slots == 0 || (fold_H == L.H && fold_W == L.W));
-        const bool p16 = (L.flags & 32) != 0;           // bf16 mode: planes16 and CIPS3D_MOD_BF16 weights
-        const int fmt = (L.flags & 8) ? (p16 ? 3 : 1) : 0;   // planes for the next layer of the run, or fp32 when the run ends here
-        if ((!p16 && !(L.flags & 2)) || (fmt != 0 && has_rgb && !fold)) return CIPS3D_E_BADARG;   // the plan promised otherwise
-        int nblk = 0;
+      case CIPS3D_STEP_PLANES_GEMM: {
+        // a layer of the planes run (csrc/chain.hip): planes in; planes out (out_format 1 / 3) with the ToRGB that follows folded
+        // from the registers -- nothing else may read this activation
+        const bool fold = (S.form & CIPS3D_STEP_FOLD) != 0, p16 = (S.form & CIPS3D_STEP_P16) != 0;
+        const int fmt = S.out_format;
+        const float* rgb_w = fold ? P.layers[li + 1].wm : nullptr;
+        float* part = fold ? P.rgb_part + (int64_t)S.slot * B * 3 * hw : nullptr;
         cips3d_range rg{};
         const bool lr = ranged && !p16;
         if (lr) {
@@ -423,88 +382,61 @@ extern "C" int cips3d_generator_forward(const cips3d_generator_plan* plan, const
           rg.half_chip = IO.views_in_flight > 1;           // (another view's launches beside this one's: chain.hip)
         }
         if (p16)
-          TRY(cips3d_modconv1x1_planes16(x, L.wm, out, fmt, B, L.Cin, L.Cout, hw, 1, nz, nbs, L.noise_w, L.bias,
-                                         fold ? T->wm : nullptr, fold ? P.rgb_part + (int64_t)fold_slots * B * 3 * hw : nullptr,
-                                         &nblk, nullptr, stream));
+          TRY(cips3d_modconv1x1_planes16(x, L.wm, out, fmt, B, L.Cin, L.Cout, hw, 1, nz, nbs, L.noise_w, L.bias, rgb_w, part, nullptr,
+                                         nullptr, stream));
         else
-          TRY(cips3d_modconv1x1_planes(x, L.wm, out, fmt, B, L.Cin, L.Cout, hw, 1, nz, nbs, L.noise_w, L.bias,
-                                       fold ? T->wm : nullptr, fold ? P.rgb_part + (int64_t)fold_slots * B * 3 * hw : nullptr, &nblk,
+          TRY(cips3d_modconv1x1_planes(x, L.wm, out, fmt, B, L.Cin, L.Cout, hw, 1, nz, nbs, L.noise_w, L.bias, rgb_w, part, nullptr,
                                        lr ? &rg : nullptr, stream));
-        mark(CIPS3D_MARK_PLANES_GEMM, L.Cin, L.Cout, L.H);
         x_amax = (lr && fmt != 1) ? L.amax : nullptr;
         x_exp = (lr && fmt == 1) ? L.aexp : nullptr;
         x_pmax = (lr && fmt == 1) ? rg.out_pmax : nullptr;
-        if (fold) {
-          fold_slots += nblk;
-          fold_bias[fold_nb++] = T->bias;
-          fold_H = L.H; fold_W = L.W;
-          ++li;
-        }
         x = out;
         act_i ^= 1;
-        continue;
+        break;
       }
-      if (L.kind == 0) {
-        const cips3d_dec_layer* T = li + 1 < P.n_dec_layers ? &P.layers[li + 1] : nullptr;
-        const int64_t hw = (int64_t)L.H * L.W;
-        const bool fold = T && T->kind == 2 && li + 1 != P.n_dec_layers - 1 && T->Cin == L.Cout && hw % 4 == 0 && P.rgb_part &&
-                          fold_nb < CIPS3D_TORGB_FOLD_MAX && fold_slots + 16 <= P.rgb_part_slots &&
-                          (fold_slots == 0 || (fold_H == L.H && fold_W == L.W));
-        const int split_flag = (L.flags & 2) ? CIPS3D_GEMM_SPLIT : 0;
+      case CIPS3D_STEP_GEMM: {
         cips3d_range rg{};
         if (split_flag) TRY(amax_of(x, L.Cin, hw));
         rg.x_amax = x_amax;
         rg.out_amax = (ranged && L.amax) ? L.amax : nullptr;
         x_amax = rg.out_amax;            // (of this layer's output, from here on)
         x_exp = nullptr;
-        if (fold) {
-          int nblk = 0;
-          TRY(cips3d_modconv1x1_torgb(x, L.wm, out, B, L.Cin, L.Cout, hw, 1 | gemm_flag | split_flag, nz, nbs, L.noise_w, L.bias, T->wm,
-                                      P.rgb_part + (int64_t)fold_slots * B * 3 * hw, &nblk, ranged ? &rg : nullptr, stream));
-          mark(CIPS3D_MARK_GEMM, L.Cin, L.Cout, L.H);
-          fold_slots += nblk;
-          fold_bias[fold_nb++] = T->bias;
-          fold_H = L.H; fold_W = L.W;
-          x = out;
-          act_i ^= 1;
-          ++li;                                  // the ToRGB layer is done (its sum is pending in the slots)
-          continue;
-        }
-        TRY(cips3d_modconv1x1(x, L.wm, out, B, L.Cin, L.Cout, hw, 1 | gemm_flag | split_flag, nz, nbs, L.noise_w, L.bias,
-                              ranged ? &rg : nullptr, stream));
-        mark(CIPS3D_MARK_GEMM, L.Cin, L.Cout, L.H);
-      } else {
-        if (L.flags & 1) return CIPS3D_E_BADARG;   // chained packs only exist for stages that take the fused route above
-        if (L.flags & 4) return CIPS3D_E_BADARG;   // planes reach an up-conv only on the fused route (the plan guarantees it)
+        if (S.form & CIPS3D_STEP_FOLD)
+          TRY(cips3d_modconv1x1_torgb(x, L.wm, out, B, L.Cin, L.Cout, hw, 1 | gemm_flag | split_flag, nz, nbs, L.noise_w, L.bias,
+                                      P.layers[li + 1].wm, P.rgb_part + (int64_t)S.slot * B * 3 * hw, nullptr, ranged ? &rg : nullptr,
+                                      stream));
+        else
+          TRY(cips3d_modconv1x1(x, L.wm, out, B, L.Cin, L.Cout, hw, 1 | gemm_flag | split_flag, nz, nbs, L.noise_w, L.bias,
+                                ranged ? &rg : nullptr, stream));
+        x = out;
+        act_i ^= 1;
+        break;
+      }
+      case CIPS3D_STEP_GEMM_FIR: {
         cips3d_range rg{};
-        if (L.flags & 2) TRY(amax_of(x, L.Cin, (int64_t)L.H * L.W));
+        if (split_flag) TRY(amax_of(x, L.Cin, hw));
         rg.x_amax = x_amax;
-        TRY(cips3d_modconv1x1(x, L.wm, P.y_lo, B, L.Cin, L.Cout, (int64_t)L.H * L.W,
-                              0 | gemm_flag | ((L.flags & 2) ? CIPS3D_GEMM_SPLIT : 0), nullptr, 0, nullptr, nullptr,
+        TRY(cips3d_modconv1x1(x, L.wm, P.y_lo, B, L.Cin, L.Cout, hw, 0 | gemm_flag | split_flag, nullptr, 0, nullptr, nullptr,
                               ranged ? &rg : nullptr, stream));
         float* fir_amax = (ranged && L.amax) ? L.amax : nullptr;      // (this route leaves the row unused: y_lo is not tracked here)
         TRY(cips3d_up2_fir_act(P.y_lo, L.fir, out, B, L.Cout, L.H, L.W, nz, nbs, L.noise_w, L.bias, fir_amax, stream));
-        mark(CIPS3D_MARK_OTHER, L.Cout, L.Cout, 2 * L.H);
         x_amax = fir_amax;               // recorded by the FIR kernel itself (else its reader measures it)
         x_exp = nullptr;
+        x = out;
+        act_i ^= 1;
+        break;
       }
-      x = out;
-      act_i ^= 1;
-    } else if (L.kind == 2 || L.kind == 3) {
-      if (fold_slots) {                          // a ToRGB that could not be folded: settle the pending sum first
-        TRY(fold_flush(P.skip[skip_i]));
+      case CIPS3D_STEP_TORGB: {
+        float* dst = (S.form & CIPS3D_STEP_LAST) ? IO.rgb : P.skip[skip_i];
+        TRY(cips3d_torgb(x, L.wm, L.bias, skip, L.kind == 3 ? 1 : 0, L.fir, dst, B, L.Cin, L.H, L.W, stream));
+        skip = dst;
         skip_i ^= 1;
+        break;
       }
-      if (last && IO.rgb_is_u8) return CIPS3D_E_UNSUPP;     // a stand-alone ToRGB writes fp32 only
-      float* out = last ? IO.rgb : P.skip[skip_i];
-      TRY(cips3d_torgb(x, L.wm, L.bias, skip, L.kind == 3 ? 1 : 0, L.fir, out, B, L.Cin, L.H, L.W, stream));
-      mark(CIPS3D_MARK_TORGB, L.Cin, 3, L.kind == 3 ? 2 * L.H : L.H);
-      skip = out;
-      skip_i ^= 1;
-    } else {
-      return CIPS3D_E_BADARG;
+      default:
+        return CIPS3D_E_BADARG;
     }
+    if (S.mark[0] >= 0) mark(S.mark[0], S.mark[1], S.mark[2], S.mark[3]);
   }
-  if (IO.rgb_is_u8 && !u8_done) return CIPS3D_E_UNSUPP;
   return 0;
 }

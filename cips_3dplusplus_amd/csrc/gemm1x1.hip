@@ -547,6 +547,13 @@ static GemmTile gemm_tile(int B, int Cin, int Cout, int64_t HW, bool small_grid_
   return {1, 2, 2, 32, ns};                       // 32 x 128 (any Cout % 32 == 0)
 }
 
+// row blocks of the ToRGB partial sums: one rgb_part slot each
+static int row_blocks(const GemmTile& t, int Cout) { return Cout > 0 ? Cout / (16 * t.WM * t.WGM) : 0; }
+
+extern "C" int cips3d_modconv1x1_torgb_blocks(int B, int Cin, int Cout, int64_t HW) {
+  return row_blocks(gemm_tile(B, Cin, Cout, HW, false), Cout);
+}
+
 static int launch_gemm_tile(const GemmTile& t, bool actbwd, const GemmArgs& a, hipStream_t st) {
 #define GEMM_TILE_CASE(wm, wgm, wgn, bk, ns)                                                    \
   if (t.WM == wm && t.WGM == wgm && t.WGN == wgn && t.BK == bk && t.NS == ns)                   \
@@ -569,7 +576,7 @@ extern "C" int cips3d_modconv1x1_torgb(const float* x, const float* wm, float* o
                                        const cips3d_range* rg, void* stream) {
   if ((rgb_w == nullptr) != (rgb_part == nullptr)) return CIPS3D_E_BADARG;
   const GemmTile tile = gemm_tile(B, Cin, Cout, HW, !rgb_part);
-  if (n_row_blocks) *n_row_blocks = Cout > 0 ? Cout / (16 * tile.WM * tile.WGM) : 0;
+  if (n_row_blocks) *n_row_blocks = row_blocks(tile, Cout);
   if (!x || !wm || !out || B < 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return CIPS3D_E_BADARG;
   if ((epilogue & CIPS3D_GEMM_BF16) && (epilogue & CIPS3D_GEMM_SPLIT)) return CIPS3D_E_BADARG;
   const int bf16 = (epilogue & CIPS3D_GEMM_BF16) ? 1 : (epilogue & CIPS3D_GEMM_SPLIT) ? 2 : 0;

@@ -71,6 +71,11 @@ PLANES16_RUN = os.environ.get("CIPS3D_PLANES16", "1") != "0"
 FLAT_STAGES = os.environ.get("CIPS3D_FLAT_STAGES", "1") != "0"
 
 
+# the tags of ForwardPlan._layer_info: a layer's route, as cips3d_decoder_route_flags wrote it into cips3d_dec_layer.flags
+_TAGS = (("chained", _lib.DEC_CHAINED), ("split", _lib.DEC_SPLIT), ("planes_in", _lib.DEC_PLANES_IN), ("planes_out", _lib.DEC_PLANES_OUT),
+         ("split16", _lib.DEC_SPLIT16), ("p16", _lib.DEC_P16), ("flat_head", _lib.DEC_FLAT_HEAD))
+
+
 class PlanUnsupported(RuntimeError):
     """The configuration cannot be planned (k != 1 or channel counts the MFMA GEMM does not tile)."""
 
@@ -177,81 +182,24 @@ class ForwardPlan:
         self.out_res = res
         self._layer_info = layer_info
         self.noise_sizes = [li["Hout"] for li in layer_info if li["kind"] in (0, 1)]
-        # An up-sampling stage [StyledConv(up), StyledConv, ToRGB(up)] of equal widths runs as low-res GEMM + one fused kernel
-        # (forward.hip).  When the NEXT stage is one too and the fused kernel has the chained form for this width, that kernel
-        # also computes the next stage's low-res GEMM from its registers: the next up-conv's weights are then packed in the
-        # chained order and its own GEMM launch disappears.
-        # A block of the same shape that does NOT up-sample, above the NeRF resolution (the blocks at the NeRF resolution belong
-        # to the planes run below), takes the same kernel in its flat form: stage_kind 2.  (At the NeRF resolution itself -- a 64^2
-        # generator's 128 .. 1024 blocks -- the four flat launches take what the eight planes launches they replace do:
-        # 0.456 against 0.457 ms per view, measured; left with the run.)
-        def stage_kind(i):
-            if i + 2 >= len(layer_info):
-                return 0
-            a, b_, c = layer_info[i], layer_info[i + 1], layer_info[i + 2]
-            if not (b_["kind"] == 0 and b_["Cin"] == a["Cout"] and b_["Cout"] == a["Cout"] and c["Cin"] == a["Cout"]):
-                return 0
-            if a["kind"] == 1 and c["kind"] == 3 and lib.cips3d_fused_up_conv_supported(a["Cout"], a["H"], a["W"]):
-                return 1
-            if (FLAT_STAGES and a["kind"] == 0 and c["kind"] == 2 and a["H"] > img_size
-                    and lib.cips3d_fused_flat_conv_supported(a["Cout"], a["H"], a["W"])):
-                return 2
-            return 0
-
-        def fused_stage(i):
-            return stage_kind(i) == 1
-        for i, li in enumerate(layer_info):
-            if stage_kind(i) == 2:
-                li["flat_head"] = True
-                max_lo = max(max_lo, B * li["Cout"] * li["H"] * li["W"])       # conv1's GEMM result, at the block's resolution
-        # the image can leave as uint8 (cips3d_forward_io.rgb_is_u8) when the decoder ends in a fused stage
-        self.u8_capable = len(layer_info) >= 3 and stage_kind(len(layer_info) - 3) != 0
-        for i in range(len(layer_info) - 3):
-            a, nx = layer_info[i], layer_info[i + 3]
-            if (CHAIN_STAGES and stage_kind(i) and stage_kind(i + 3) and lib.cips3d_fused_up_conv_chains(a["Cout"])
-                    and nx["Cin"] == a["Cout"] and nx["Cout"] * 2 == a["Cout"] and nx["H"] == a["Hout"]):
-                nx["chained"] = True
-        # Which packed layers the stand-alone GEMM consumes (everything but conv2 of a fused stage and chained up-convs): in the
-        # default "fp32" precision those are packed as split-fp16 fragments and run in CIPS3D_GEMM_SPLIT mode.
+        # ---- the route: which launch form every layer takes -- fused up-sampling / flat stages, chained low-resolution GEMMs, the
+        # planes run at the NeRF resolution, folded ToRGBs -- is decided by csrc/decoder_route.hip.  Its flags say how every weight
+        # matrix below is packed; the tags of _layer_info are those flags, read back.
         use_split = bool(getattr(dec, "split", False)) and not getattr(dec, "bf16", False)
-        for i, li in enumerate(layer_info):
-            if not (use_split and li["packed"]):
-                continue
-            conv2_of_fused = li["kind"] == 0 and i >= 1 and stage_kind(i - 1) != 0
-            chained = bool(li.get("chained"))
-            li["split"] = not conv2_of_fused and not chained
-            li["split16"] = conv2_of_fused or chained           # consumed inside cips3d_fused_up_conv_next
-        # The run of equal-resolution StyledConvs at the NeRF resolution keeps its activations as split-fp16 planes
-        # (csrc/chain.hip): the render kernel writes the feature map as planes, every layer of the run reads and writes them,
-        # the ToRGBs in between are folded from registers, and the first up-sampling conv's low-resolution GEMM reads them.
-        # In the bf16 modes the run keeps ONE bf16 plane ("planes16", cips3d_modconv1x1_planes16): the stored activation is the
-        # rounded operand of the next GEMM, so the mode's results do not change while its operand bytes halve.
-        use_p16 = bool(getattr(dec, "bf16", False)) and PLANES16_RUN
-        if (use_split and PLANES_RUN) or use_p16:
-            hw = img_size * img_size
-            mine = (lambda c: c["packed"] and not c.get("chained")) if use_p16 else (lambda c: c.get("split"))  # noqa: E731
-            ok_conv = lambda c: (c is not None and mine(c) and c["kind"] in (0, 1) and c["H"] == img_size   # noqa: E731
-                                 and bool(lib.cips3d_planes_supported(c["Cin"], c["Cout"], hw)))
-            i, n_fold = 0, 0
-            while i < len(layer_info) and ok_conv(layer_info[i]):
-                li = layer_info[i]
-                if li["kind"] == 1:
-                    if fused_stage(i):
-                        li["planes_in"], li["p16"] = True, use_p16
-                    break
-                nxt = layer_info[i + 1] if i + 1 < len(layer_info) else None
-                has_rgb = nxt is not None and nxt["kind"] == 2
-                foldable = (has_rgb and i + 1 != len(layer_info) - 1 and nxt["Cin"] == li["Cout"] and hw % 4 == 0 and n_fold < 8)
-                j = i + (2 if has_rgb else 1)
-                nconv = layer_info[j] if j < len(layer_info) else None
-                next_takes = ok_conv(nconv) and (nconv["kind"] == 0 or fused_stage(j))
-                li["planes_in"], li["p16"] = True, use_p16
-                li["planes_out"] = bool(next_takes and (not has_rgb or foldable))
-                if has_rgb and foldable:
-                    n_fold += 1
-                if not li["planes_out"]:
-                    break
-                i = j
+        for L, info in zip(p.layers, layer_info):
+            L.kind, L.Cin, L.Cout, L.H, L.W, L.noise_index = (info["kind"], info["Cin"], info["Cout"], info["H"], info["W"],
+                                                              info["noise_index"])
+            L.flags = _lib.DEC_DEMOD if info["conv"].demodulate else 0
+        opts = _lib.DecRouteOpts(B=B, nerf_res=img_size, mode=2 if getattr(dec, "bf16", False) else int(use_split),
+                                 chain_stages=CHAIN_STAGES, flat_stages=FLAT_STAGES, planes_run=PLANES_RUN, planes16_run=PLANES16_RUN)
+        slots = C.c_int64(0)
+        _lib.check(lib.cips3d_decoder_route_flags(C.byref(p.layers), len(seq), C.byref(opts), C.byref(slots)),
+                   "cips3d_decoder_route_flags")
+        slots = slots.value
+        for L, info in zip(p.layers, layer_info):
+            info.update({tag: True for tag, bit in _TAGS if L.flags & bit})
+            if info.get("flat_head"):
+                max_lo = max(max_lo, B * info["Cout"] * info["H"] * info["W"])     # conv1's GEMM result, at the block's resolution
         wm_buf = torch.empty(sum(wm_sizes), device=dev)
         wm_tab = (_lib.ModulateDesc * len(seq))()
         rows, woff = 0, 0
@@ -296,11 +244,6 @@ class ForwardPlan:
             d.row_begin = rows
             rows += conv.out_channel
             L = p.layers[idx]
-            L.kind, L.Cin, L.Cout, L.H, L.W, L.noise_index = (info["kind"], info["Cin"], info["Cout"], info["H"],
-                                                              info["W"], info["noise_index"])
-            L.flags = ((1 if info.get("chained") else 0) | (2 if info.get("split") else 0) | (4 if info.get("planes_in") else 0) |
-                       (8 if info.get("planes_out") else 0) | (16 if info.get("split16") else 0) |
-                       (32 if info.get("p16") else 0) | (64 if conv.demodulate else 0) | (128 if info.get("flat_head") else 0))
             L.wm = d.out
             L.bias = dev_ptr(info["bias"])
             L.noise_w = dev_ptr(info["noise_w"], allow_none=True)
@@ -353,21 +296,30 @@ class ForwardPlan:
         p.y_lo = y_lo[0].data_ptr()
         p.y_lo2 = y_lo[1].data_ptr() if y_lo.shape[0] > 1 else None
         p.skip[0], p.skip[1] = skip[0].data_ptr(), skip[1].data_ptr()
-        # ToRGB layers at the input resolution fold into the epilogue of the conv that feeds them (forward.hip): one slot
-        # of [B,3,S,S] per row block per layer
-        n_fold = sum(1 for i, li in enumerate(layer_info) if li["kind"] == 2 and i > 0 and layer_info[i - 1]["kind"] == 0
-                     and li["H"] == img_size)
-        slots = 16 * n_fold
+        # (one rgb_part slot of [B,3,S,S] per row block of every ToRGB that folds into the conv that feeds it: `slots`, above)
         rgb_part = torch.empty(max(1, slots) * B * 3 * img_size * img_size, device=dev)
         p.rgb_part, p.rgb_part_slots = rgb_part.data_ptr(), slots
         self._keep.append(rgb_part)
 
         self.plan = p
+        # the image can leave as uint8 (cips3d_forward_io.rgb_is_u8) when the decoder ends in a fused stage
+        self.u8_capable = self.steps()[-1].kind == _lib.STEP_FUSED_STAGE
         self.key = self.weights_key(G)
         self._keep += [packed32, lat, film, film_tab, mod_tab, s_buf, wm_buf, wm_tab_dev, packed, layer_bias, part, features, act,
                        y_lo, skip]
         self.noise_total = sum(s * s for s in self.noise_sizes)
         self.film, self.s_buf, self.range_ws = film, s_buf, range_ws
+
+    def steps(self):
+        """The decoder launches of one forward of this plan (a list of _lib.DecStep), as cips3d_generator_forward resolves them
+        on every call (cips3d_decoder_steps); raises on a refusal."""
+        p = self.plan
+        steps = (_lib.DecStep * _lib.MAX_DEC_STEPS)()
+        n = _lib.load().cips3d_decoder_steps(C.byref(p.layers), p.n_dec_layers, p.B, int(bool(p.range_ws)),
+                                             p.rgb_part_slots if p.rgb_part else 0, steps, len(steps))
+        if n < 0:
+            _lib.check(n, "cips3d_decoder_steps")
+        return list(steps[:n])
 
     def style_phase(self, z_r, z_d, mode=-1, trunc_psi=1.0, mean_r=None, mean_d=None, rng=None):
         """cips3d_style_phase alone (tests, tools): the mapping networks and every style head of this plan for (z_r, z_d);

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 41  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 42  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -606,15 +606,7 @@ typedef struct cips3d_dec_layer {
   int32_t kind;            /* 0 StyledConv, 1 StyledConv with 2x up-sampling, 2 ToRGB, 3 ToRGB + up-sampled skip */
   int32_t Cin, Cout, H, W; /* H, W = INPUT resolution of the layer (ToRGB: its own resolution) */
   int32_t noise_index;     /* index into cips3d_forward_io.noise (StyledConv) or -1 */
-  int32_t flags;           /* bit 0 (kind 1, or kind 0 with bit 7): wm is in the CIPS3D_MOD_CHAINED order and this conv's GEMM is
-                              computed by the previous stage's kernel (cips3d_fused_up_conv_next);
-                              bit 1: wm is CIPS3D_MOD_SPLIT-packed and this layer's stand-alone GEMM runs in CIPS3D_GEMM_SPLIT mode;
-                              bit 2: the layer's input is stored as split-fp16 planes, bit 3: its output is (cips3d_modconv1x1_planes);
-                              bit 5 (with bit 2 / 3): the planes are bf16 planes16 and wm is CIPS3D_MOD_BF16-packed (cips3d_modconv1x1_planes16);
-                              bit 4: wm is CIPS3D_MOD_SPLIT16-packed (conv2 / chained up-conv of a fused stage run in CIPS3D_GEMM_SPLIT mode);
-                              bit 6: the conv is demodulated (its rows have unit norm: the sqrt(Cin) gain of the range bounds);
-                              bit 7 (kind 0): head of a FLAT stage -- this conv, the next StyledConv and the ToRGB behind them (equal
-                              widths, one resolution) run as one launch of the fused stage kernel (CIPS3D_STAGE_FLAT) */
+  int32_t flags;           /* CIPS3D_DEC_* bits (below): the route of the layer, written by cips3d_decoder_route_flags */
   int32_t pad_;
   const float* wm;         /* this layer's modulated weights (workspace, written by the modulate table) */
   const float* bias;       /* activate.bias [Cout] or ToRGB.bias [3] */
@@ -626,6 +618,20 @@ typedef struct cips3d_dec_layer {
   float* pmax;             /* [B][ceil(H*W / 64)][Cout / 16] patch maxima of a planes output */
   float* lconst;           /* [B][4] written by the modulate table */
 } cips3d_dec_layer;
+
+/* cips3d_dec_layer.flags */
+#define CIPS3D_DEC_CHAINED    1    /* (kind 1, or kind 0 with FLAT_HEAD): wm is in the CIPS3D_MOD_CHAINED order and this conv's GEMM is
+                                      computed by the previous stage's kernel (cips3d_fused_up_conv_next) */
+#define CIPS3D_DEC_SPLIT      2    /* wm is CIPS3D_MOD_SPLIT-packed and this layer's stand-alone GEMM runs in CIPS3D_GEMM_SPLIT mode */
+#define CIPS3D_DEC_PLANES_IN  4    /* the layer's input is stored as split-fp16 planes (cips3d_modconv1x1_planes) */
+#define CIPS3D_DEC_PLANES_OUT 8    /* ... and so is its output */
+#define CIPS3D_DEC_SPLIT16    16   /* wm is CIPS3D_MOD_SPLIT16-packed (conv2 / chained up-conv of a fused stage run in CIPS3D_GEMM_SPLIT mode) */
+#define CIPS3D_DEC_P16        32   /* (with PLANES_IN / PLANES_OUT): the planes are bf16 planes16 and wm is CIPS3D_MOD_BF16-packed
+                                      (cips3d_modconv1x1_planes16) */
+#define CIPS3D_DEC_DEMOD      64   /* the conv is demodulated (its rows have unit norm: the sqrt(Cin) gain of the range bounds).  A property
+                                      of the layer, not of its route: the caller sets it, cips3d_decoder_route_flags keeps it */
+#define CIPS3D_DEC_FLAT_HEAD  128  /* (kind 0): head of a FLAT stage -- this conv, the next StyledConv and the ToRGB behind them (equal
+                                      widths, one resolution) run as one launch of the fused stage kernel (CIPS3D_STAGE_FLAT) */
 
 typedef struct cips3d_generator_plan {
   int32_t B, z_dim, n_map_r, n_map_d, style_dim_r, style_dim_d, n_latent, n_dec_layers;
@@ -731,6 +737,72 @@ typedef struct cips3d_forward_io {
 #define CIPS3D_MARK_OTHER 6
 
 int cips3d_generator_forward(const cips3d_generator_plan* plan, const cips3d_forward_io* io, void* stream);
+
+/* ---- the decoder's route (csrc/decoder_route.hip): which launch form every layer of the one-call forward takes.  Host-only
+ * arithmetic on the layer list: nothing here launches, allocates or makes a HIP call, so both functions run on a machine without a
+ * GPU.  Two functions share one set of predicates: the first writes the flags a plan is packed by, the second turns flagged
+ * layers into the list of launches; cips3d_generator_forward calls the second before its first enqueue and runs what it says. */
+typedef struct cips3d_dec_route_opts {
+  int32_t B;
+  int32_t nerf_res;        /* resolution of the NeRF feature map = the decoder's input */
+  int32_t mode;            /* arithmetic of the decoder: 0 plain fp32 (or fp32_exact), 1 split-fp16, 2 bf16 */
+  /* the A/B knobs, != 0 = on: a fused stage also computes the next stage's low-resolution GEMM; blocks above the NeRF resolution
+   * that do not up-sample run as flat stages; the run at the NeRF resolution keeps split-fp16 planes (mode 1) / bf16 planes16 (mode 2) */
+  int32_t chain_stages, flat_stages, planes_run, planes16_run;
+  int32_t pad_;
+} cips3d_dec_route_opts;
+
+/* Reads kind, Cin, Cout, H, W (and CIPS3D_DEC_DEMOD of flags) of layers[0 .. n_layers), writes every other bit of their flags and
+ * *rgb_part_slots, the number of ToRGB partial-sum slots (cips3d_generator_plan.rgb_part_slots) the plan must allocate.
+ * CIPS3D_E_BADARG: a null pointer, n_layers outside [1, CIPS3D_MAX_DEC_LAYERS], a kind outside [0, 3], B or nerf_res < 1,
+ * mode outside [0, 2]. */
+int cips3d_decoder_route_flags(cips3d_dec_layer* layers, int n_layers, const cips3d_dec_route_opts* opts, int64_t* rgb_part_slots);
+
+#define CIPS3D_STEP_LOWRES_GEMM 0   /* the low-resolution GEMM of a fused stage's head -> y_lo (form: CIPS3D_STEP_PLANES / _P16 or fp32 input) */
+#define CIPS3D_STEP_FUSED_STAGE 1   /* cips3d_fused_up_conv_next on layers [layer, layer + 2] (form: CIPS3D_STEP_FLAT, _CHAIN, _LAST) */
+#define CIPS3D_STEP_PLANES_GEMM 2   /* a layer of the planes run (form: _P16, _FOLD; out_format as cips3d_modconv1x1_planes / _planes16 take it) */
+#define CIPS3D_STEP_GEMM        3   /* cips3d_modconv1x1, with _FOLD cips3d_modconv1x1_torgb */
+#define CIPS3D_STEP_GEMM_FIR    4   /* an up-sampling conv outside a fused stage: cips3d_modconv1x1 + cips3d_up2_fir_act */
+#define CIPS3D_STEP_TORGB       5   /* a stand-alone cips3d_torgb (form: _LAST) */
+#define CIPS3D_STEP_FLUSH       6   /* the pending ToRGB fold becomes the skip image: cips3d_torgb_reduce, or with _RIDE a
+                                       cips3d_reduce_job on the CIPS3D_STEP_LOWRES_GEMM that follows */
+/* cips3d_dec_step.form */
+#define CIPS3D_STEP_PLANES 1        /* the input is split-fp16 planes */
+#define CIPS3D_STEP_P16    2        /* the input is bf16 planes16 */
+#define CIPS3D_STEP_FLAT   4        /* the stage does not up-sample (CIPS3D_STAGE_FLAT) */
+#define CIPS3D_STEP_CHAIN  8        /* the stage also computes the low-resolution GEMM of layer + 3 */
+#define CIPS3D_STEP_LAST   16       /* the step writes the final image */
+#define CIPS3D_STEP_FOLD   32       /* the GEMM folds the ToRGB at layer + 1 into rgb_part slots [slot, slot + its row blocks) */
+#define CIPS3D_STEP_RIDE   64       /* the flush rides on the next step's launch */
+#define CIPS3D_MAX_DEC_STEPS (2 * CIPS3D_MAX_DEC_LAYERS)
+
+typedef struct cips3d_dec_step {
+  int32_t kind;          /* CIPS3D_STEP_* */
+  int32_t layer;         /* the (first) layer the step runs; FLUSH: the layer in front of which the sum is needed */
+  int32_t form;
+  int32_t out_format;    /* PLANES_GEMM: 0 fp32, 1 split-fp16 planes, 3 planes16 */
+  int32_t slot;          /* _FOLD: first slot of rgb_part the launch writes; FLUSH: the number of slots it sums */
+  int32_t n_bias;        /* FLUSH: folded ToRGB layers, whose biases join the sum */
+  int32_t H, W;          /* FLUSH: resolution of the slots */
+  int32_t bias_layer[CIPS3D_TORGB_FOLD_MAX];   /* FLUSH: those layers */
+  int32_t mark[4];       /* what the launch records on the timeline (cips3d_forward_io.ev_info): {CIPS3D_MARK_*, Cin, Cout, H};
+                            mark[0] < 0: nothing (a riding flush has no launch of its own) */
+} cips3d_dec_step;
+
+/* The launches of the decoder, in order, for layers whose flags are set; returns their number (<= max_steps) or a refusal.
+ * ranged: the plan tracks ranges (cips3d_generator_plan.range_ws != NULL); rgb_part_slots: the capacity the plan allocated.
+ * Flags that do not describe a route these layers can take -- CIPS3D_DEC_CHAINED without a preceding stage that chains,
+ * CIPS3D_DEC_PLANES_IN on an up-conv outside a fused stage, CIPS3D_DEC_FLAT_HEAD on a block the flat kernel does not take,
+ * CIPS3D_DEC_PLANES_OUT with a ToRGB that cannot be folded, ... -- are CIPS3D_E_BADARG, as are null pointers, n_layers outside
+ * [1, CIPS3D_MAX_DEC_LAYERS], a kind outside [0, 3] and max_steps too small (CIPS3D_MAX_DEC_STEPS always suffices).
+ * A decoder can leave its image as uint8 (cips3d_forward_io.rgb_is_u8) iff its last step is a CIPS3D_STEP_FUSED_STAGE. */
+int cips3d_decoder_steps(const cips3d_dec_layer* layers, int n_layers, int B, int ranged, int64_t rgb_part_slots,
+                         cips3d_dec_step* steps, int max_steps);
+
+/* Row blocks (= rgb_part slots) the ToRGB fold of a GEMM launch of this shape writes: cips3d_modconv1x1_torgb's *n_row_blocks /
+ * cips3d_modconv1x1_planes' and _planes16's, without the launch. */
+int cips3d_modconv1x1_torgb_blocks(int B, int Cin, int Cout, int64_t HW);
+int cips3d_planes_torgb_blocks(int Cout);
 
 /* The part of cips3d_generator_forward in front of the modulated weights: Generator.mapping_networks (models/model_v3.py:
  * 1299-1418) -> plan.styles_r / styles_d, the FiLM heads (cips3d/volume_renderer.py:66-67) and every
