@@ -725,6 +725,7 @@ def _range(**kw):
 GEMM_BF16 = 0x100      # CIPS3D_GEMM_BF16: bf16 compute mode of the decoder GEMMs (BASELINE config 3)
 Y_BF16 = 0x200         # CIPS3D_Y_BF16: the pre-FIR low-resolution GEMM result of an up-sampling stage is stored as bf16
 GEMM_SPLIT = 0x400     # CIPS3D_GEMM_SPLIT: fp32-equivalent split-fp16 products (weights packed with MOD_SPLIT)
+RGB_U8 = 0x800         # CIPS3D_RGB_U8: the fused stage stores its image as uint8 (cips3d_rgb_to_uint8 of the value it would have stored)
 STAGE_FLAT = 0x1000    # CIPS3D_STAGE_FLAT: the fused stage kernel on a block that does not up-sample
 
 
@@ -1025,7 +1026,8 @@ def fused_up_conv_chains(C_):
 
 
 def fused_up_conv(y_lo, fir, noise1, noise_w1, bias1, wm2_packed, noise2, noise_w2, bias2, wm_rgb=None, bias_rgb=None,
-                  skip=None, skip_up=True, want_out2=True, bf16=False, wm_next=None, split=False, ranged=True, flat=False):
+                  skip=None, skip_up=True, want_out2=True, bf16=False, wm_next=None, split=False, ranged=True, flat=False,
+                  rgb_u8=False, out=None):
     """FIR up-sampling + act -> 1x1 conv + act -> ToRGB for one up-sampling stage (see cips3d_fused_up_conv).
     wm_next (MOD_PACKED | MOD_CHAINED weights of the next stage's C -> C/2 up-conv): also returns its low-res GEMM y_next.
     A torch.bfloat16 `y_lo` selects the bf16-storage form (CIPS3D_Y_BF16, needs bf16=True): y_next is then bf16 as well.
@@ -1033,7 +1035,9 @@ def fused_up_conv(y_lo, fir, noise1, noise_w1, bias1, wm2_packed, noise2, noise_
     then split under power-of-two scales from rigorous bounds (cips3d_range): y_lo's amax array is taken from its tag or
     measured, the two layers' constants are made here (noise bounds measured on the device); out2 / y_next leave tagged.
     flat: a block that does not up-sample (CIPS3D_STAGE_FLAT): y_lo is conv1's GEMM result at the block's resolution, fir is
-    not read, outputs and skip have y_lo's size (skip_up must be False)."""
+    not read, outputs and skip have y_lo's size (skip_up must be False).
+    rgb_u8: the image leaves as a torch.uint8 tensor (CIPS3D_RGB_U8).  out: (out2, rgb, y_next), contiguous tensors of the shapes
+    and dtypes this function would allocate, to write into; an entry that is None is allocated here."""
     lib = _lib.load()
     B, Cc, H, W = y_lo.shape
     up = 1 if flat else 2
@@ -1049,9 +1053,21 @@ def fused_up_conv(y_lo, fir, noise1, noise_w1, bias1, wm2_packed, noise2, noise_
     ydt = y_lo.dtype
     if ydt == torch.bfloat16 and not bf16:
         raise RuntimeError("a bf16 y_lo needs the bf16 GEMM mode (bf16=True)")
-    out2 = torch.empty(B, Cc, up * H, up * W, device=dev) if want_out2 else None
-    rgb = torch.empty(B, 3, up * H, up * W, device=dev) if wm_rgb is not None else None
-    y_next = torch.empty(B, Cc // 2, up * H, up * W, device=dev, dtype=ydt) if wm_next is not None else None
+    rdt = torch.uint8 if rgb_u8 else torch.float32
+
+    def result(given, wanted, ch, dtype, name):
+        if not wanted:
+            return None
+        if given is None:
+            return torch.empty(B, ch, up * H, up * W, device=dev, dtype=dtype)
+        if given.shape != (B, ch, up * H, up * W) or given.device != dev:
+            raise RuntimeError(f"fused_up_conv: `out` {name} must be [{B}, {ch}, {up * H}, {up * W}] on {dev}")
+        return given
+
+    o2, orgb, onext = out if out is not None else (None, None, None)
+    out2 = result(o2, want_out2, Cc, torch.float32, "out2")
+    rgb = result(orgb, wm_rgb is not None, 3, rdt, "rgb")
+    y_next = result(onext, wm_next is not None, Cc // 2, ydt, "y_next")
 
     def bs(nz):
         return up * up * H * W if (nz is not None and nz.shape[0] == B and B > 1) else 0
@@ -1062,8 +1078,9 @@ def fused_up_conv(y_lo, fir, noise1, noise_w1, bias1, wm2_packed, noise2, noise_
                                         dev_ptr(bias2, "bias2"), dev_ptr(out2, "out2", True), dev_ptr(wm_rgb, "wm_rgb", True),
                                         dev_ptr(bias_rgb, "bias_rgb", True), dev_ptr(skip, "skip", True),
                                         int(bool(skip_up)) | (GEMM_BF16 if bf16 else 0) |
-                                        (Y_BF16 if ydt == torch.bfloat16 else 0) | (GEMM_SPLIT if split else 0) | (STAGE_FLAT if flat else 0),
-                                        dev_ptr(rgb, "rgb", True), dev_ptr(wm_next, "wm_next", True),
+                                        (Y_BF16 if ydt == torch.bfloat16 else 0) | (GEMM_SPLIT if split else 0) | (STAGE_FLAT if flat else 0) |
+                                        (RGB_U8 if rgb_u8 else 0),
+                                        dev_ptr(rgb, "rgb", True, dtype=rdt), dev_ptr(wm_next, "wm_next", True),
                                         dev_ptr(y_next, "y_next", True, dtype=ydt), B, Cc, H, W,
                                         C.byref(rg) if rg is not None else None, stream_ptr()), "cips3d_fused_up_conv_next")
     if next_amax is not None:
