@@ -130,6 +130,13 @@ class MeshResolveParams(C.Structure):
         (n, C.c_float) for n in ("fill", "ka", "kd", "ks", "shininess")]
 
 
+class MeshColorParams(C.Structure):
+    """cips3d_mesh_color_params (include/cips3d_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("verts", "normals", "images", "workspace", "keys", "colors", "weight", "seen")] + [
+        (n, C.c_int32) for n in ("V", "n_views", "S", "R", "power")] + [("depth_tol", C.c_float), ("fill", C.c_float),
+                                                                         ("pad_", C.c_int32)]
+
+
 VGG_CONVS = 13                  # CIPS3D_VGG_CONVS
 
 
@@ -340,6 +347,8 @@ _SIGS = {
     "cips3d_mesh_raster_workspace_bytes": (c_i64, [c_i64, c_i64, c_int, c_int]),
     "cips3d_mesh_rasterize": (c_int, [c_f32p, c_i64, C.c_void_p, c_i64, c_f32p, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_mesh_resolve": (c_int, [C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_vertex_colors": (c_int, [C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_albedo_frame": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, C.c_void_p]),
     "cips3d_vgg_supported": (c_int, [c_int, c_int, c_int]),
     "cips3d_vgg_channels": (c_int, [c_int]),
     "cips3d_vgg_stride": (c_int, [c_int]),
@@ -378,7 +387,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 42           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 43           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -388,7 +397,7 @@ def _struct_table():
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
             11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO, 17: DecRouteOpts,
-            18: DecStep}
+            18: DecStep, 19: MeshColorParams}
 
 
 def load(build_if_missing=True):

@@ -16,26 +16,11 @@
 // cross products of the corners RELATIVE TO THE PIXEL CENTRE: the two faces of a shared edge evaluate exactly negated
 // values, so a pixel centre is never lost between them (and is drawn by both only when the value is exactly zero).
 // No LDS, no scratch; the library builds with -ffp-contract=off, so every expression below rounds as written.
-#include "common.h"
+#include "mesh_raster.h"          // the workspace layout, MR_EMPTY, mr_check, mr_grid: shared with mesh_color.hip
 
 namespace {
 
-constexpr int MR_THREADS = 256;
-constexpr int MR_CAM_FLOATS = 16;                   // eye(3) x_ax(3) y_ax(3) z_ax(3) s znear pad(2)
 constexpr int MR_WAVE_BOX = 64;                     // boxes of more pixels than this go to the wave path
-constexpr unsigned long long MR_EMPTY = ~0ull;
-
-struct MrWorkspace {
-  float* cams;      // [n, MR_CAM_FLOATS]
-  float4* proj;     // [n, V]: x_p, y_p, z, 1/z (1/z = -1: dropped by znear)
-};
-
-MrWorkspace mr_workspace(void* ws, int n_views) {
-  MrWorkspace m;
-  m.cams = static_cast<float*>(ws);
-  m.proj = reinterpret_cast<float4*>(static_cast<char*>(ws) + ceil_div<int64_t>((int64_t)n_views * MR_CAM_FLOATS * 4, 256) * 256);
-  return m;
-}
 
 __global__ void __launch_bounds__(64) mr_camera_kernel(const float* __restrict__ cams_in, float* __restrict__ cams, int n_views) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -246,16 +231,6 @@ __global__ void __launch_bounds__(MR_THREADS) mr_resolve_kernel(cips3d_mesh_reso
     }
   }
 }
-
-// 0, or the error code, for the sizes every entry point takes
-int mr_check(int64_t V, int64_t F, int n_views, int S) {
-  if (V < 0 || F < 0 || n_views < 0 || S < 1) return CIPS3D_E_BADARG;
-  // vertex and face ids are int32 (the key's low word holds the face id, `face` is int32); S bounds the pixel-space floats
-  if (V > INT32_MAX || F > INT32_MAX || S > 16384 || n_views > 65536) return CIPS3D_E_UNSUPP;
-  return 0;
-}
-
-int mr_grid(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div<int64_t>(items, MR_THREADS), 1 << 16)); }
 
 }  // namespace
 

@@ -108,13 +108,25 @@ def vertex_normals(verts, faces):
     return vn / np.maximum(n, 1e-20)
 
 
-def write_obj(path, verts, faces, normals=None):
-    """normals [V,3] (one per vertex): written as `vn` lines, and the faces as `f a//a b//b c//c`."""
+def _unit_colors(colors, n_verts, what):
+    """[V,3] colours in [-1, 1] (the generator's image range) -> numpy fp64 in [0, 1]."""
+    c = np.asarray(colors, np.float64)
+    if c.shape != (n_verts, 3):
+        raise ValueError(f"{what}: colors of shape {c.shape} for {n_verts} vertices")
+    return np.clip((c + 1) / 2, 0, 1)
+
+
+def write_obj(path, verts, faces, normals=None, colors=None):
+    """normals [V,3] (one per vertex): written as `vn` lines, and the faces as `f a//a b//b c//c`.
+    colors [V,3] in [-1, 1]: every vertex line becomes `v x y z r g b`, r g b = (c + 1) / 2 clamped to [0, 1] (the common
+    vertex-colour extension; mesh.read_obj ignores the extra columns)."""
     if normals is not None and len(normals) != len(verts):
         raise ValueError(f"write_obj: {len(normals)} normals for {len(verts)} vertices")
+    rgb = None if colors is None else _unit_colors(colors, len(verts), "write_obj")
     with open(path, "w") as f:
-        for v in verts:
-            f.write(f"v {v[0]:.7g} {v[1]:.7g} {v[2]:.7g}\n")
+        for i, v in enumerate(verts):
+            tail = "" if rgb is None else f" {rgb[i][0]:.6f} {rgb[i][1]:.6f} {rgb[i][2]:.6f}"
+            f.write(f"v {v[0]:.7g} {v[1]:.7g} {v[2]:.7g}{tail}\n")
         if normals is None:
             for t in faces + 1:
                 f.write(f"f {t[0]} {t[1]} {t[2]}\n")
@@ -123,4 +135,41 @@ def write_obj(path, verts, faces, normals=None):
                 f.write(f"vn {n[0]:.7g} {n[1]:.7g} {n[2]:.7g}\n")
             for t in faces + 1:
                 f.write(f"f {t[0]}//{t[0]} {t[1]}//{t[1]} {t[2]}//{t[2]}\n")
+    return path
+
+
+def write_ply(path, verts, faces, normals=None, colors=None):
+    """Binary little-endian PLY: float x y z, float nx ny nz with `normals` [V,3], uchar red green blue with `colors` [V,3] in
+    [-1, 1] (floor(255 clamp((c + 1) / 2, 0, 1) + 0.5)), then the triangles as `list uchar int`.  mesh.read_ply reads it back."""
+    verts, faces = np.asarray(verts, np.float32), np.asarray(faces)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(verts)):
+        raise ValueError("write_ply: a face names a vertex that is not there")
+    fields = [(n, "<f4") for n in "xyz"]
+    if normals is not None:
+        if len(normals) != len(verts):
+            raise ValueError(f"write_ply: {len(normals)} normals for {len(verts)} vertices")
+        fields += [(n, "<f4") for n in ("nx", "ny", "nz")]
+    if colors is not None:
+        rgb = np.floor(255 * _unit_colors(colors, len(verts), "write_ply") + 0.5).astype(np.uint8)
+        fields += [(n, "u1") for n in ("red", "green", "blue")]
+    v = np.zeros(len(verts), np.dtype(fields))
+    for k, n in enumerate("xyz"):
+        v[n] = verts[:, k]
+    if normals is not None:
+        for k, n in enumerate(("nx", "ny", "nz")):
+            v[n] = np.asarray(normals, np.float32)[:, k]
+    if colors is not None:
+        for k, n in enumerate(("red", "green", "blue")):
+            v[n] = rgb[:, k]
+    f = np.zeros(len(faces), np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    f["n"] = 3
+    f["idx"] = faces.reshape(-1, 3)
+    names = {"<f4": "float", "u1": "uchar", "|u1": "uchar"}
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"] + \
+           [f"property {names[t]} {n}" for n, t in fields] + \
+           [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(f.tobytes())
     return path

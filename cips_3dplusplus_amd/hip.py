@@ -1856,6 +1856,61 @@ def mesh_resolve(verts, faces, ws, keys, want=("face", "zbuf", "bary"), attr=Non
     return out
 
 
+# ---------------------------------------------------------------------------------------------- mesh colours (csrc/mesh_color.hip)
+def mesh_vertex_colors(verts, normals, images, ws, keys, S, power=2, depth_tol=0.0, fill=0.0, want=("colors", "weight", "seen"),
+                       out=None):
+    """cips3d_mesh_vertex_colors after mesh_rasterize (same verts, workspace, keys, S): verts / normals [V,3] fp32, images
+    [n,3,R,R] fp32, one per rasterised view -> dict with the entries named in `want` (and every entry `out` holds a tensor
+    for): colors [V,3] fp32, weight [V] fp32, seen [V] int32.  Enqueued only."""
+    lib = _lib.load()
+    V, n, S = verts.shape[0], keys.shape[0], int(S)
+    if verts.dim() != 2 or verts.shape[1] != 3 or tuple(normals.shape) != (V, 3):
+        raise RuntimeError("mesh_vertex_colors: verts and normals must be [V, 3]")
+    if images.dim() != 4 or images.shape[0] != n or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+        raise RuntimeError(f"mesh_vertex_colors: images must be [{n}, 3, R, R], one square picture per rasterised view")
+    if tuple(keys.shape) != (n, S, S) or ws.numel() < lib.cips3d_mesh_raster_workspace_bytes(V, 0, n, S):
+        raise RuntimeError("mesh_vertex_colors: workspace / keys do not fit these sizes")
+    out = dict(out or {})
+    names = set(want) | set(out)
+    shapes = {"colors": ((V, 3), torch.float32), "weight": ((V,), torch.float32), "seen": ((V,), torch.int32)}
+    if not names or names - set(shapes):
+        raise RuntimeError(f"mesh_vertex_colors: outputs must be among {sorted(shapes)}, at least one")
+    for name in names:
+        shape, dt = shapes[name]
+        if out.get(name) is None:
+            out[name] = torch.empty(shape, dtype=dt, device=verts.device)
+        elif tuple(out[name].shape) != shape:
+            raise RuntimeError(f"mesh_vertex_colors: {name} must be {shape}")
+
+    def ptr(t, name, dtype=torch.float32):
+        return None if t is None or t.numel() == 0 else dev_ptr(t, name, dtype=dtype)
+    p = _lib.MeshColorParams(
+        verts=ptr(verts, "verts"), normals=ptr(normals, "normals"), images=ptr(images, "images"),
+        workspace=dev_ptr(ws, "ws", dtype=torch.uint8), keys=dev_ptr(keys, "keys", dtype=torch.int64),
+        colors=ptr(out.get("colors"), "colors"), weight=ptr(out.get("weight"), "weight"), seen=ptr(out.get("seen"), "seen", torch.int32),
+        V=V, n_views=n, S=S, R=int(images.shape[2]), power=int(power), depth_tol=float(depth_tol), fill=float(fill))
+    if V:
+        check(lib.cips3d_mesh_vertex_colors(C.byref(p), stream_ptr()), "cips3d_mesh_vertex_colors")
+    return out
+
+
+def mesh_albedo_frame(face, shade, attr, out=None):
+    """cips3d_mesh_albedo_frame: mesh_resolve's face [n,S,S] int32, shade [n,S,S] and attr [n,3,S,S] (colours in [-1, 1]) ->
+    uint8 [n,3,S,S] = shade x (attr + 1) / 2, white where empty."""
+    n, S = face.shape[0], face.shape[1]
+    if tuple(face.shape) != (n, S, S) or tuple(shade.shape) != (n, S, S) or tuple(attr.shape) != (n, 3, S, S):
+        raise RuntimeError("mesh_albedo_frame: face and shade must be [n, S, S], attr [n, 3, S, S]")
+    if out is None:
+        out = torch.empty(n, 3, S, S, dtype=torch.uint8, device=face.device)
+    elif tuple(out.shape) != (n, 3, S, S):
+        raise RuntimeError(f"mesh_albedo_frame: out must be {(n, 3, S, S)}")
+    if n:
+        check(_lib.load().cips3d_mesh_albedo_frame(dev_ptr(face, "face", dtype=torch.int32), dev_ptr(shade, "shade"),
+                                                   dev_ptr(attr, "attr"), dev_ptr(out, "out", dtype=torch.uint8), n, S, stream_ptr()),
+              "cips3d_mesh_albedo_frame")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- VGG16 conv loss (csrc/vgg.hip)
 def vgg_supported(B, H, W):
     """cips3d_vgg_supported as a bool: B >= 1, H and W multiples of 16 (decided on the host; perceptual.VGG16ConvLoss)."""

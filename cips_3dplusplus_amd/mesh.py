@@ -14,6 +14,10 @@ interpolate; the triangles of ambiguous cells can differ.
 The second half rasterises that mesh (csrc/mesh_raster.hip; the reference uses pytorch3d): `rasterize_mesh`, the Phong
 `render_mesh_frames` of exp/cips3d/utils.py:260-308, and `NoiseProjector`, the surface-bound decoder noise of
 models/model_v3.py:344-415 (`NoiseInjection.project_noise`), with the midpoint `subdivide` its mesh ladder needs.
+
+The third colours the mesh (csrc/mesh_color.hip; an extension, the reference exports a grey surface): `vertex_colors` gathers
+pictures of the mesh onto its vertices through the rasteriser's own visibility, `color_mesh` takes those pictures from the
+generator, and `render_mesh_frames(colors=)` draws the result.
 """
 import math
 
@@ -63,7 +67,7 @@ def extract_mesh_with_marching_cubes(sdf, level=0.0, normals=False):
 
 @torch.no_grad()
 def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_samples=None, locations=None, fov_ang=6,
-                 dist_radius=0.12, near=0.88, far=1.12, level=0.0, normals=False):
+                 dist_radius=0.12, near=0.88, far=1.12, level=0.0, normals=False, colors=False, color_kw=None):
     """The reference's surface extraction on the renderer only (the decoder is not run): mapping network ->
     `G.renderer.render(..., return_sdf=True)` at resolution^2 rays x N_samples (default: resolution) with perturbation off
     -> align_volume -> marching cubes per view.
@@ -72,11 +76,19 @@ def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_
     given; both None: one random z.  locations: (B, 2) azimuth / elevation, default the frontal view.
     Returns {"sdf": (B, S, S, N, 1), "aligned": the same shape, "meshes": [(verts, faces) or None per view]}; with
     normals=True each mesh is (verts, faces, normals).
+    colors=True (needs normals=True and a decoder latent: zs = [z_renderer, z_decoder]): every mesh is coloured by
+    `color_mesh(G, ..., **color_kw)` from its own sample's latents and becomes (verts, faces, normals, colors); the dict gains
+    "color_weight" and "color_seen", one entry per view (None where there is no mesh).
 
     Runs on the caller's stream through the renderer's lane-0 tables: do not issue it from inside a `ViewPipeline` lane
     (pipeline.py) while that pipeline has views in flight."""
     from .camera import Camera
     dev = next(G.parameters()).device
+    if colors:
+        if not normals:
+            raise ValueError("surface_mesh(colors=True) needs normals=True: the colours are weighted by the vertex normals")
+        if style_render is not None or not isinstance(zs, (list, tuple)) or len(zs) < 2:
+            raise ValueError("surface_mesh(colors=True) needs the decoder's latent too: zs = [z_renderer, z_decoder]")
     if style_render is None:
         if zs is None:
             zs = [torch.randn(1, G.z_dim, device=dev)]
@@ -97,7 +109,18 @@ def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_
                                         return_sdf=True)
     aligned = align_volume(sdf, near, far)
     meshes = [extract_mesh_with_marching_cubes(aligned[b:b + 1], level, normals=normals) for b in range(B)]
-    return {"sdf": sdf, "aligned": aligned, "meshes": meshes}
+    out = {"sdf": sdf, "aligned": aligned, "meshes": meshes}
+    if colors:
+        kw = dict(fov_ang=fov_ang, dist_radius=dist_radius, truncation=truncation)
+        kw.update(color_kw or {})
+        out["color_weight"], out["color_seen"] = [None] * B, [None] * B
+        for b, m in enumerate(meshes):
+            if m is None:
+                continue
+            c = color_mesh(G, m[0], m[1], m[2], zs=[z[b:b + 1].to(dev) for z in zs[:2]], **kw)
+            meshes[b] = (m[0], m[1], m[2], c["colors"])
+            out["color_weight"][b], out["color_seen"][b] = c["weight"], c["seen"]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ rasterisation
@@ -139,18 +162,91 @@ def rasterize_mesh(verts, faces, azim, elev, image_size, fov_deg=12.0, dist=1.0,
                            light=None if light is None else light.float().contiguous(), out=out)
 
 
-def render_mesh_frames(verts, faces, normals, trajectory, image_size=512, light=None):
+def render_mesh_frames(verts, faces, normals, trajectory, image_size=512, light=None, colors=None):
     """The reference's mesh panel (create_cameras / create_mesh_renderer, utils.py:260-308, as the frame loops call it): the
     Phong picture of the mesh from every row (azim, elev, fov / 2) of `trajectory`, camera fov = 2 trajectory[:,2] degrees at
     distance 1, point light (5 sin az, 0, 5 cos az) unless `light` [n,3] is given -> uint8 [n,3,S,S], white where empty.
-    The rasteriser is hard (one face per pixel); pytorch3d's soft blending is not reproduced."""
+    The rasteriser is hard (one face per pixel); pytorch3d's soft blending is not reproduced.
+    colors [V,3] in [-1, 1] (vertex_colors / color_mesh): the same frames with the interpolated vertex colour as albedo,
+    floor(255 clamp(shade (colour + 1) / 2, 0, 1) + 0.5); white exactly where the plain panel is white."""
     traj = torch.as_tensor(trajectory, dtype=torch.float32).to(verts.device)
     az, el = traj[:, 0], traj[:, 1]
     if light is None:
         light = torch.stack([5 * torch.sin(az), torch.zeros_like(az), 5 * torch.cos(az)], 1)
+    if colors is not None:
+        if tuple(colors.shape) != (verts.shape[0], 3):
+            raise ValueError("render_mesh_frames: colors must be [V, 3]")
+        out = rasterize_mesh(verts, faces, az, el, image_size, fov_deg=2.0 * traj[:, 2], dist=1.0, attrs=colors, normals=normals,
+                             light=light.float().contiguous(), want=("face", "shade", "attr"))
+        return hip.mesh_albedo_frame(out["face"], out["shade"], out["attr"])
     out = rasterize_mesh(verts, faces, az, el, image_size, fov_deg=2.0 * traj[:, 2], dist=1.0, normals=normals,
                          light=light.float().contiguous(), want=("shade_u8",))
     return out["shade_u8"]
+
+
+def vertex_colors(verts, faces, normals, images, azim, elev, fov_deg=12.0, dist=1.0, znear=0.01, raster_size=512, depth_tol=None,
+                  power=2, fill=0.0, ws=None, keys=None):
+    """Colours of the vertices of (verts [V,3], faces [F,3]) from `images` [n,3,R,R], pictures of the mesh taken by the cameras
+    (azim, elev) [radians; one value or n] of `rasterize_mesh`: the mesh is rasterised at raster_size^2 from every camera, and
+    every vertex takes, from each view whose z-buffer shows it (vertex depth <= the depth of its pixel + depth_tol) and that it
+    faces (c = normal . direction to the eye > 0), the bilinear sample of that view's image at its projection, weighted by
+    c^power (an integer 1..8).  normals [V,3]: unit, outward (extract_mesh_with_marching_cubes(normals=True)).
+    -> {"colors": [V,3] fp32, the weighted mean, `fill` where no view sees the vertex; "weight": [V] fp32, the sum of the
+    weights; "seen": [V] int32, the number of views that see the vertex}.
+    depth_tol=None: FRAME_SCALE / 128, one cell of the default 128^3 volume in the output frame.  depth_tol, power and
+    raster_size are design defaults, not measured optima.  ws / keys: buffers of hip.mesh_raster_workspace to reuse.
+    Visibility is quantised to the z-buffer's pixels: a front-facing vertex at a grazing angle can be hidden by
+    the nearer surface that owns its pixel centre.  Contract: include/cips3d_hip.h (cips3d_mesh_vertex_colors)."""
+    verts = verts.float().contiguous()
+    f32 = _faces_i32(faces)
+    cams = camera_rows(azim, elev, fov_deg, dist, znear, device=verts.device)
+    images = images.float().contiguous()
+    if images.dim() != 4 or images.shape[0] != cams.shape[0]:
+        raise ValueError(f"vertex_colors: {cams.shape[0]} cameras need images [{cams.shape[0]}, 3, R, R]")
+    if depth_tol is None:
+        depth_tol = FRAME_SCALE / 128
+    if f32.shape[0] == 0 and verts.shape[0]:
+        raise ValueError("vertex_colors: a mesh without faces has no surface to colour (the rasteriser projects nothing)")
+    ws, keys = hip.mesh_rasterize(verts, f32, cams, raster_size, ws=ws, keys=keys)
+    return hip.mesh_vertex_colors(verts, normals.float().contiguous(), images, ws, keys, raster_size, power=power,
+                                  depth_tol=depth_tol, fill=fill)
+
+
+DEFAULT_COLOR_VIEWS = ((0, 0), (0.4, 0), (-0.4, 0))       # (azim, elev): frontal and two side views; a design default
+
+
+@torch.no_grad()
+def color_mesh(G, verts, faces, normals, zs=None, style_render=None, style_decoder=None, truncation=1, views=DEFAULT_COLOR_VIEWS,
+               img_size=64, N_samples=24, fov_ang=6, dist_radius=0.12, noise_bufs=None, **vertex_colors_kw):
+    """Colours the mesh of a latent with the generator's own pictures of that latent: one full forward (renderer and decoder,
+    perturbation off) per (azim, elev) of `views` at img_size^2 rays x N_samples, then `vertex_colors` from the same cameras
+    (`view_angles`' correspondence: fov_deg = 2 fov_ang at distance 1) -> its dict.
+    zs: [z_renderer, z_decoder], each (1, z_dim); or style_render and style_decoder, both.  noise_bufs: the decoder's noise
+    maps, shared by the views; default `G.create_noise_bufs`, drawn from torch's generator on the device, so that a seed
+    reproduces the colours.  The default views are a design default, not a measured optimum.  vertex_colors_kw: raster_size,
+    depth_tol, power, fill, znear, ws, keys.
+
+    Runs on the caller's stream through the generator's lane-0 plans and tables, like `surface_mesh`: do not issue it from
+    inside a `ViewPipeline` lane (pipeline.py) while that pipeline has views in flight."""
+    from .camera import Camera
+    dev = verts.device
+    if (style_render is None) != (style_decoder is None):
+        raise ValueError("color_mesh: give style_render and style_decoder together")
+    if style_render is None and (not isinstance(zs, (list, tuple)) or len(zs) < 2):
+        raise ValueError("color_mesh needs zs = [z_renderer, z_decoder] or both styles")
+    locs = torch.as_tensor(views, dtype=torch.float32).reshape(-1, 2).to(dev)
+    if noise_bufs is None:
+        noise_bufs = G.create_noise_bufs(img_size, dev)
+    images = []
+    for k in range(locs.shape[0]):
+        cam, focal, near, far, _ = Camera.generate_camera_params(img_size, dev, locations=locs[k:k + 1].contiguous(),
+                                                                 fov_ang=fov_ang, dist_radius=dist_radius)
+        out = G(zs=zs if style_render is None else [None, None], cam_poses=cam, focals=focal, img_size=img_size, near=near, far=far,
+                truncation=truncation, style_render=style_render, style_decoder=style_decoder, noise_bufs=noise_bufs,
+                nerf_cfg=dict(N_samples=N_samples, perturb=False))
+        images.append(out["rgb"].float())
+    return vertex_colors(verts, faces, normals, torch.cat(images, 0), locs[:, 0], locs[:, 1], fov_deg=2.0 * float(fov_ang),
+                         dist=1.0, **vertex_colors_kw)
 
 
 def subdivide(verts, faces):
@@ -193,6 +289,47 @@ def read_obj(path, device=None):
     verts = torch.tensor(vs, dtype=torch.float32).reshape(-1, 3)
     faces = torch.tensor(fs, dtype=torch.int64).reshape(-1, 3)
     return verts.to(device), faces.to(device)
+
+
+def read_ply(path, device=None):
+    """The binary little-endian PLY that gen_images.write_ply writes -> {"verts": [V,3] fp32, "faces": [F,3] int64, and, where
+    the file holds them, "normals": [V,3] fp32 and "colors": [V,3] uint8}."""
+    import numpy as np
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        counts, props, elem = {}, {}, None
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError(f"{path}: no end_header")
+            tok = line.decode("ascii").split()
+            if tok[:1] == ["end_header"]:
+                break
+            if tok[:1] == ["format"] and tok[1] != "binary_little_endian":
+                raise ValueError(f"{path}: only binary_little_endian is read")
+            if tok[:1] == ["element"]:
+                elem = tok[1]
+                counts[elem], props[elem] = int(tok[2]), []
+            elif tok[:1] == ["property"]:
+                props[elem].append(tok[1:])
+        kinds = {"float": "<f4", "uchar": "u1"}
+        if list(counts) != ["vertex", "face"] or props["face"] != [["list", "uchar", "int", "vertex_indices"]] or \
+                any(len(p) != 2 or p[0] not in kinds for p in props["vertex"]):
+            raise ValueError(f"{path}: not the layout gen_images.write_ply writes")
+        vt = np.dtype([(p[1], kinds[p[0]]) for p in props["vertex"]])
+        v = np.frombuffer(fh.read(vt.itemsize * counts["vertex"]), vt)
+        ft = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])
+        f = np.frombuffer(fh.read(ft.itemsize * counts["face"]), ft)
+    if len(v) != counts["vertex"] or len(f) != counts["face"] or (f["n"] != 3).any():
+        raise ValueError(f"{path}: truncated, or a face that is not a triangle")
+    cols = lambda names: torch.from_numpy(np.stack([v[n] for n in names], 1).copy()).to(device)      # noqa: E731
+    out = {"verts": cols(("x", "y", "z")), "faces": torch.from_numpy(f["idx"].astype(np.int64)).to(device)}
+    if "nx" in vt.names:
+        out["normals"] = cols(("nx", "ny", "nz"))
+    if "red" in vt.names:
+        out["colors"] = cols(("red", "green", "blue"))
+    return out
 
 
 class NoiseProjector:

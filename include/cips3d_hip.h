@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 42  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 43  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1345,6 +1345,41 @@ int64_t cips3d_mesh_raster_workspace_bytes(int64_t V, int64_t F, int n_views, in
 int cips3d_mesh_rasterize(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* cams, int n_views,
                           int S, void* workspace, uint64_t* keys, void* stream);
 int cips3d_mesh_resolve(const cips3d_mesh_resolve_params* p, void* stream);
+
+/* ------------------------------------------------------------------ mesh vertex colours (csrc/mesh_color.hip) */
+
+/* Colours the mesh's vertices from n_views pictures of it: images [n_views,3,R,R] fp32, picture k taken by camera k of the
+ * rasterisation (R is independent of S).  Called after cips3d_mesh_rasterize on the same stream with the same verts, workspace,
+ * keys, n_views and S: it reads the rasteriser's projected vertices (x_p, y_p, z, 1/z), derived cameras and keys, so that
+ * visibility is the z-buffer's own and nothing is projected twice (a rasterisation with F = 0 projects nothing: its
+ * workspace must not be handed to this call).  normals [V,3]: unit, outward.  One thread per vertex,
+ * views in ascending order, no atomics: the result does not depend on the grid and is bit-reproducible.  Per vertex p and view k:
+ *   skipped when 1/z <= 0 (the rasteriser dropped the vertex behind znear);
+ *   j = rintf(x_p), i = rintf(y_p); off the S x S frame: not seen;
+ *   z* = the depth of keys[k,i,j], +inf for an empty pixel;  visible = z <= z* + depth_tol;
+ *   d = (C_k - p) / max(|C_k - p|, 1e-12);  c = (n.x d.x + n.y d.y) + n.z d.z;  faces = visible && c > 0;
+ *   w = faces ? c^power : 0, the power by repeated multiplication (w = c; w *= c, power - 1 times);
+ *   w > 0: rgb = the bilinear sample of images[k] at u = (x_p + 1/2) R / S - 1/2, v = (y_p + 1/2) R / S - 1/2 (the rasteriser's
+ *   pixel-centre convention carried to R), u and v clamped to [0, R - 1]: x0 = floor(u), x1 = min(x0 + 1, R - 1), fx = u - x0,
+ *   row = (1 - fx) a + fx b, value = (1 - fy) top + fy bottom;  acc += w rgb, wsum += w;  seen += faces.
+ * Outputs (each may be NULL, at least one is required): colors [V,3] = acc / wsum, or `fill` where wsum == 0; weight [V] = wsum;
+ * seen [V] int32.  Does not synchronise.  CIPS3D_E_BADARG, nothing launched: a null required pointer, no output, a negative
+ * size, S < 1, R < 1, power outside 1..8.  CIPS3D_E_UNSUPP: V > INT32_MAX, S > 16384, n_views > 65536 (the rasteriser's
+ * limits), R > 16384. */
+typedef struct cips3d_mesh_color_params {
+  const float* verts; const float* normals; const float* images; const void* workspace; const uint64_t* keys;
+  float* colors; float* weight; int32_t* seen;
+  int32_t V, n_views, S, R, power;
+  float depth_tol, fill;
+  int32_t pad_;
+} cips3d_mesh_color_params;
+int cips3d_mesh_vertex_colors(const cips3d_mesh_color_params* p, void* stream);
+
+/* The coloured mesh frame from cips3d_mesh_resolve's maps: face [n,S,S] int32, shade [n,S,S], attr [n,3,S,S] (the interpolated
+ * vertex colours, in [-1, 1]) -> out [n,3,S,S] uint8 = floor(255 clamp(shade (attr + 1) / 2, 0, 1) + 0.5), 255 where
+ * face < 0.  CIPS3D_E_BADARG: a null pointer, n_views < 0, S < 1.  CIPS3D_E_UNSUPP: S > 16384, n_views > 65536. */
+int cips3d_mesh_albedo_frame(const int32_t* face, const float* shade, const float* attr, uint8_t* out, int n_views, int S,
+                             void* stream);
 
 /* VGG16 conv perceptual loss of flip inversion (csrc/vgg.hip; reference exp/cips3d/models/vgg_per_loss.py:203-334,
  * models/projector_v10.py:131-151, 1170-1174).  The network is the 13 convolutions of torchvision's vgg16.features

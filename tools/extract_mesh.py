@@ -2,6 +2,7 @@
 
     python tools/extract_mesh.py [--ckpt DIR] [--depth 2] [--seed 0] [--resolution 128] [--out mesh.obj] [--normals] [--time]
                                  [--frames N [--frames-out DIR] [--image-size 512]]
+                                 [--colors [--color-views "az,el;az,el;..."] [--ply]]
 
 --normals writes the vertex normals too (`vn` lines, `f a//a b//b c//c`).  Without --ckpt the generator is the FFHQ 256^2 configuration with synthetic weights (`--depth` renderer layers).  With
 --time it prints one JSON line of device-event timings (ms, median of --reps runs) of the renderer-only SDF pass, the
@@ -12,6 +13,10 @@ writes frame_000.png ... into --frames-out (default: next to --out); with --time
 of those N frames in one call on the sphere mesh at --image-size, and `levels`: V / F of the production mesh after 0, 1 and 3
 midpoint subdivisions (mesh.subdivision_levels) with the one-view rasterise / resolve times of a noise projection at every
 layer size that uses the level.
+--colors colours the mesh from the generator's own pictures of the same latent (mesh.color_mesh; --color-views: the (azim, elev)
+of those pictures in radians): the OBJ's vertex lines become `v x y z r g b`, --ply writes a binary PLY with uchar colours next
+to it, and the --frames are the coloured ones.  With --time the JSON line gains `color`: one cips3d_mesh_vertex_colors call at
+the production mesh's V, 3 views, S = 512, R = 1024, against the same gather written with torch's grid_sample on the device.
 """
 import argparse
 import json
@@ -24,7 +29,7 @@ import torch  # noqa: E402
 import cips_3dplusplus_amd as pkg  # noqa: E402
 from cips_3dplusplus_amd import configs, hip, mesh  # noqa: E402
 from cips_3dplusplus_amd.camera import Camera  # noqa: E402
-from cips_3dplusplus_amd.gen_images import write_obj  # noqa: E402
+from cips_3dplusplus_amd.gen_images import write_obj, write_ply  # noqa: E402
 
 
 def timed(fn, reps):
@@ -59,6 +64,49 @@ def raster_steps(verts, faces, cams, size, reps, **resolve_kw):
     return round(t_raster, 4), round(t_resolve, 4)
 
 
+def color_steps(verts, faces, normals, reps, views=mesh.DEFAULT_COLOR_VIEWS, S=512, R=1024, power=2):
+    """median device ms of one cips3d_mesh_vertex_colors call, and of the same gather in torch ops (the visibility test on the
+    resolved z-buffer, grid_sample for the bilinear taps), both after the rasterisation, on preallocated inputs."""
+    import torch.nn.functional as F
+    dev = verts.device
+    f32 = faces.to(torch.int32).contiguous()
+    az, el = (torch.tensor([v[k] for v in views], dtype=torch.float32) for k in (0, 1))
+    cams = mesh.camera_rows(az, el, 12.0, device=dev)
+    n, V = cams.shape[0], verts.shape[0]
+    images = torch.rand(n, 3, R, R, device=dev) * 2 - 1
+    tol = mesh.FRAME_SCALE / 128
+    ws, keys = hip.mesh_rasterize(verts, f32, cams, S)
+    out, _ = timed(lambda: hip.mesh_vertex_colors(verts, normals, images, ws, keys, S, power=power, depth_tol=tol), 1)
+    _, t_kernel = timed(lambda: hip.mesh_vertex_colors(verts, normals, images, ws, keys, S, power=power, depth_tol=tol, out=out), reps)
+    zbuf = hip.mesh_resolve(verts, f32, ws, keys, want=("zbuf",))["zbuf"]
+    zbuf = torch.where(zbuf < 0, torch.full_like(zbuf, float("inf")), zbuf)
+    nbytes = -(-n * 16 * 4 // 256) * 256                 # the derived cameras, then proj [n,V,4] (csrc/mesh_raster.h)
+    eye = ws[:n * 64].view(torch.float32).view(n, 16)[:, :3]
+    proj = ws[nbytes:nbytes + n * V * 16].view(torch.float32).view(n, V, 4)
+
+    def torch_gather():
+        x, y, z = proj[..., 0], proj[..., 1], proj[..., 2]
+        j, i = torch.round(x), torch.round(y)
+        on = (proj[..., 3] > 0) & (j >= 0) & (j <= S - 1) & (i >= 0) & (i <= S - 1)
+        pix = (i.clamp(0, S - 1) * S + j.clamp(0, S - 1)).long()
+        vis = on & (z <= torch.gather(zbuf.view(n, -1), 1, pix) + tol)
+        d = F.normalize(eye[:, None] - verts[None], dim=-1)
+        c = (d * normals[None]).sum(-1)
+        w = torch.where(vis & (c > 0), c ** power, torch.zeros_like(c))
+        grid = torch.stack([(x + 0.5) * (2.0 / S) - 1, (y + 0.5) * (2.0 / S) - 1], -1)[:, :, None]
+        rgb = F.grid_sample(images, grid, mode="bilinear", padding_mode="border", align_corners=False)[..., 0]
+        wsum = w.sum(0)
+        return torch.where(wsum[:, None] > 0, (w[:, None] * rgb).sum(0).t() / wsum[:, None].clamp_min(1e-30), torch.zeros(V, 3, device=dev))
+    ref, _ = timed(torch_gather, 2)
+    _, t_torch = timed(torch_gather, reps)
+    return {"V": V, "views": n, "S": S, "R": R, "kernel_ms": round(t_kernel, 4), "grid_sample_ms": round(t_torch, 4),
+            "max_abs_diff": round(float((ref - out["colors"]).abs().max()), 6)}
+
+
+def parse_views(text):
+    return tuple(tuple(float(x) for x in pair.split(",")) for pair in text.split(";") if pair.strip())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt", default=None)
@@ -72,6 +120,9 @@ def main():
     ap.add_argument("--frames", type=int, default=0)
     ap.add_argument("--frames-out", default=None)
     ap.add_argument("--image-size", type=int, default=512)
+    ap.add_argument("--colors", action="store_true")
+    ap.add_argument("--color-views", default=None)
+    ap.add_argument("--ply", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     if args.ckpt:
@@ -80,13 +131,34 @@ def main():
     else:
         G = pkg.build_generator(configs.ffhq_G_cfg(256, args.depth), dev, seed=args.seed)
     S = args.resolution
-    z = torch.randn(1, G.z_dim, generator=torch.Generator().manual_seed(args.seed)).to(dev)
-    out = mesh.surface_mesh(G, zs=[z], resolution=S, normals=args.normals or args.frames > 0)
+    gen = torch.Generator().manual_seed(args.seed)
+    z = torch.randn(1, G.z_dim, generator=gen).to(dev)
+    zs = [z]
+    color_kw = {}
+    if args.colors:
+        zs.append(torch.randn(1, G.z_dim, generator=gen).to(dev))
+        torch.manual_seed(args.seed)                    # the decoder's noise maps are drawn from torch's generator
+        if args.color_views:
+            color_kw["views"] = parse_views(args.color_views)
+    out = mesh.surface_mesh(G, zs=zs, resolution=S, normals=args.normals or args.frames > 0 or args.colors, colors=args.colors,
+                            color_kw=color_kw)
     m = out["meshes"][0]
+    colors = m[3] if m is not None and args.colors else None
     if m is not None:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        write_obj(args.out, m[0].cpu().numpy(), m[1].cpu().numpy(), m[2].cpu().numpy() if args.normals else None)
+        v_np, f_np = m[0].cpu().numpy(), m[1].cpu().numpy()
+        n_np = m[2].cpu().numpy() if args.normals or args.colors else None
+        c_np = None if colors is None else colors.cpu().numpy()
+        write_obj(args.out, v_np, f_np, n_np, c_np)
         print(f"wrote {args.out}: {m[0].shape[0]} vertices, {m[1].shape[0]} faces")
+        if args.ply:
+            ply = os.path.splitext(args.out)[0] + ".ply"
+            write_ply(ply, v_np, f_np, n_np, c_np)
+            print(f"wrote {ply}")
+        if colors is not None:
+            unseen = int((out["color_seen"][0] == 0).sum())
+            print(f"coloured from {len(color_kw.get('views', mesh.DEFAULT_COLOR_VIEWS))} views: {unseen} of {m[0].shape[0]} "
+                  "vertices are seen by none and keep the fill colour")
     else:
         print("no surface: the SDF volume has no zero crossing")
     traj = None
@@ -95,7 +167,7 @@ def main():
         traj = yaw_trajectory(args.frames)
         if m is not None:
             from PIL import Image
-            frames = mesh.render_mesh_frames(m[0], m[1], m[2], traj, image_size=args.image_size)
+            frames = mesh.render_mesh_frames(m[0], m[1], m[2], traj, image_size=args.image_size, colors=colors)
             fdir = args.frames_out or os.path.dirname(os.path.abspath(args.out))
             os.makedirs(fdir, exist_ok=True)
             for i, fr in enumerate(frames.permute(0, 2, 3, 1).cpu().numpy()):
@@ -147,6 +219,8 @@ def main():
                     row["sizes"][str(s)] = {"raster_ms": t_r, "resolve_ms": t_s}
                 levels.append(row)
         extra["levels"] = levels
+    if args.colors and m is not None:
+        extra["color"] = color_steps(m[0], m[1], m[2], reps)
     print(json.dumps({
         "workload": f"surface_mesh depth={args.depth} {S}^2 rays x {S} samples, frontal", "device": torch.cuda.get_device_name(0),
         "render_ms": round(t_render, 4), "align_ms": round(t_align, 4), "count_ms": round(t_count, 4),
