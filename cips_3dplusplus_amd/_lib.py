@@ -137,6 +137,14 @@ class MeshColorParams(C.Structure):
                                                                          ("pad_", C.c_int32)]
 
 
+class MeshTextureParams(C.Structure):
+    """cips3d_mesh_texture_params (include/cips3d_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("verts", "faces", "normals", "images", "workspace", "keys", "vertex_colors", "filled",
+                                          "texture", "weight", "seen")] + [
+        (n, C.c_int32) for n in ("V", "F", "n_views", "S", "R", "power", "T", "cols", "rows")] + [
+        ("depth_tol", C.c_float), ("fill", C.c_float), ("pad_", C.c_int32)]
+
+
 VGG_CONVS = 13                  # CIPS3D_VGG_CONVS
 
 
@@ -349,6 +357,15 @@ _SIGS = {
     "cips3d_mesh_resolve": (c_int, [C.c_void_p, C.c_void_p]),
     "cips3d_mesh_vertex_colors": (c_int, [C.c_void_p, C.c_void_p]),
     "cips3d_mesh_albedo_frame": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, C.c_void_p]),
+    "cips3d_mesh_atlas_layout": (c_int, [c_i64, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_atlas_uv": (c_int, [c_i64, c_int, c_int, C.c_void_p]),
+    "cips3d_mesh_atlas_texels": (c_int, [c_i64, c_int, c_int, c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_fill_workspace_bytes": (c_i64, [c_i64]),
+    "cips3d_mesh_fill_colors": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64, c_i64, c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "cips3d_mesh_texture_bake": (c_int, [C.c_void_p, C.c_void_p]),
+    "cips3d_mesh_textured_frame": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_i64, c_int,
+                                           c_int, c_int, C.c_void_p]),
     "cips3d_vgg_supported": (c_int, [c_int, c_int, c_int]),
     "cips3d_vgg_channels": (c_int, [c_int]),
     "cips3d_vgg_stride": (c_int, [c_int]),
@@ -387,7 +404,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 43           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 44           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -397,7 +414,7 @@ def _struct_table():
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
             11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO, 17: DecRouteOpts,
-            18: DecStep, 19: MeshColorParams}
+            18: DecStep, 19: MeshColorParams, 20: MeshTextureParams}
 
 
 def load(build_if_missing=True):

@@ -37,6 +37,7 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 17: return (int64_t)sizeof(cips3d_dec_route_opts);
     case 18: return (int64_t)sizeof(cips3d_dec_step);
     case 19: return (int64_t)sizeof(cips3d_mesh_color_params);
+    case 20: return (int64_t)sizeof(cips3d_mesh_texture_params);
     default: return -1;
   }
 }

@@ -138,6 +138,57 @@ def write_obj(path, verts, faces, normals=None, colors=None):
     return path
 
 
+def write_textured_obj(path, verts, faces, uv, width, height, normals=None, mtl=None, material="textured"):
+    """The OBJ of a mesh with a texture atlas (mesh.texture_atlas): uv [F,3,2], the faces' corner UVs in continuous texel
+    coordinates of a width x height atlas, become 3F `vt` lines, u = x / width, v = 1 - y / height (OBJ's v points up, the
+    atlas' row 0 is its top); the faces are `f a/t/a b/t/b c/t/c` with normals [V,3], `f a/t b/t c/t` without.  mtl: the name
+    of the material file (write_mtl) for the `mtllib` line, with `usemtl <material>` before the faces.  mesh.read_obj reads
+    the positions and faces back."""
+    uv = np.asarray(uv, np.float64).reshape(-1, 3, 2)
+    if len(uv) != len(faces):
+        raise ValueError(f"write_textured_obj: {len(uv)} UV triangles for {len(faces)} faces")
+    if normals is not None and len(normals) != len(verts):
+        raise ValueError(f"write_textured_obj: {len(normals)} normals for {len(verts)} vertices")
+    with open(path, "w") as f:
+        if mtl is not None:
+            f.write(f"mtllib {mtl}\n")
+        for v in verts:
+            f.write(f"v {v[0]:.7g} {v[1]:.7g} {v[2]:.7g}\n")
+        for tri in uv:
+            for x, y in tri:
+                f.write(f"vt {x / width:.7f} {1.0 - y / height:.7f}\n")
+        if normals is not None:
+            for n in normals:
+                f.write(f"vn {n[0]:.7g} {n[1]:.7g} {n[2]:.7g}\n")
+        if mtl is not None:
+            f.write(f"usemtl {material}\n")
+        for k, t in enumerate(np.asarray(faces) + 1):
+            a, b, c = 3 * k + 1, 3 * k + 2, 3 * k + 3
+            if normals is None:
+                f.write(f"f {t[0]}/{a} {t[1]}/{b} {t[2]}/{c}\n")
+            else:
+                f.write(f"f {t[0]}/{a}/{t[0]} {t[1]}/{b}/{t[1]} {t[2]}/{c}/{t[2]}\n")
+    return path
+
+
+def write_mtl(path, texture_file, material="textured"):
+    """A one-material MTL file whose diffuse map is `texture_file` (a path relative to the MTL file): white Kd, so that a viewer
+    shows the texture as it is."""
+    with open(path, "w") as f:
+        f.write(f"newmtl {material}\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {texture_file}\n")
+    return path
+
+
+def write_texture_png(path, texture_u8):
+    """uint8 [3,Ht,Wt] (mesh.texture_to_uint8 of a baked texture) -> an RGB PNG of Wt x Ht."""
+    from PIL import Image
+    t = np.asarray(texture_u8)
+    if t.ndim != 3 or t.shape[0] != 3 or t.dtype != np.uint8:
+        raise ValueError("write_texture_png: the texture must be uint8 [3, Ht, Wt]")
+    Image.fromarray(np.ascontiguousarray(t.transpose(1, 2, 0))).save(path)
+    return path
+
+
 def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY: float x y z, float nx ny nz with `normals` [V,3], uchar red green blue with `colors` [V,3] in
     [-1, 1] (floor(255 clamp((c + 1) / 2, 0, 1) + 0.5)), then the triangles as `list uchar int`.  mesh.read_ply reads it back."""

@@ -1911,6 +1911,146 @@ def mesh_albedo_frame(face, shade, attr, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- mesh texture (csrc/mesh_texture.hip)
+def mesh_atlas_layout(n_faces, texels=8, cols=None):
+    """cips3d_mesh_atlas_layout (host only): (cols, rows, width, height) of the atlas of n_faces faces at `texels` texels per
+    cell side; cols=None: the default."""
+    out = [C.c_int32(0) for _ in range(4)]
+    if cols is not None and int(cols) < 1:
+        raise RuntimeError("mesh_atlas_layout: cols must be at least 1")
+    check(_lib.load().cips3d_mesh_atlas_layout(int(n_faces), int(texels), 0 if cols is None else int(cols), *(C.byref(o) for o in out)),
+          "cips3d_mesh_atlas_layout")
+    return tuple(o.value for o in out)
+
+
+def mesh_atlas_uv(n_faces, texels, cols):
+    """cips3d_mesh_atlas_uv (host only): numpy [F,3,2] fp32, the faces' corner UVs in continuous texel coordinates."""
+    import numpy as np
+    uv = np.zeros((int(n_faces), 3, 2), np.float32)
+    check(_lib.load().cips3d_mesh_atlas_uv(int(n_faces), int(texels), int(cols), uv.ctypes.data if n_faces else None),
+          "cips3d_mesh_atlas_uv")
+    return uv
+
+
+def mesh_atlas_texels(n_faces, texels, cols, rows):
+    """cips3d_mesh_atlas_texels (host only): numpy (face [Ht,Wt] int32, -1 where unowned; bary [Ht,Wt,3] fp32; gutter [Ht,Wt]
+    bool) -- what the bake kernel decides per texel."""
+    import numpy as np
+    T, cols, rows = int(texels), int(cols), int(rows)
+    shape = (max(rows, 0) * T, max(cols, 0) * (T + 1))
+    face, bary, gutter = np.zeros(shape, np.int32), np.zeros(shape + (3,), np.float32), np.zeros(shape, np.uint8)
+    check(_lib.load().cips3d_mesh_atlas_texels(int(n_faces), T, cols, rows, face.ctypes.data, bary.ctypes.data, gutter.ctypes.data),
+          "cips3d_mesh_atlas_texels")
+    return face, bary, gutter.astype(bool)
+
+
+def mesh_fill_colors(colors, weight, faces, iters=64, out=None, ws=None):
+    """cips3d_mesh_fill_colors: colors [V,3] fp32, weight [V] fp32, faces [F,3] int32 -> {"colors": [V,3] fp32, "filled": [V]
+    int32 (0: seen, r: filled in ring r, -1: never)}.  `out`: tensors to write into; `ws`: a uint8 workspace to reuse.
+    Enqueued only."""
+    lib = _lib.load()
+    V, F = colors.shape[0], faces.shape[0]
+    if tuple(colors.shape) != (V, 3) or tuple(weight.shape) != (V,) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("mesh_fill_colors: colors must be [V, 3], weight [V], faces [F, 3]")
+    out = dict(out or {})
+    if set(out) - {"colors", "filled"}:
+        raise RuntimeError("mesh_fill_colors: outputs are colors and filled")
+    for name, shape, dt in (("colors", (V, 3), torch.float32), ("filled", (V,), torch.int32)):
+        if out.get(name) is None:
+            out[name] = torch.empty(shape, dtype=dt, device=colors.device)
+        elif tuple(out[name].shape) != shape:
+            raise RuntimeError(f"mesh_fill_colors: {name} must be {shape}")
+    nbytes = lib.cips3d_mesh_fill_workspace_bytes(V)
+    if nbytes < 0:
+        check(int(nbytes), "cips3d_mesh_fill_workspace_bytes")
+    if ws is None:
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=colors.device)
+    elif ws.numel() < nbytes or ws.data_ptr() % 8:
+        raise RuntimeError("mesh_fill_colors: the workspace is too small or not 8-byte aligned (it holds 64-bit sums)")
+    if V == 0 or F == 0:                  # the library launches nothing: no ring can reach anything
+        if int(iters) < 0 or int(iters) > 4096:
+            raise RuntimeError("mesh_fill_colors: iters must lie in 0..4096")
+        out["colors"].copy_(colors)
+        out["filled"].copy_(torch.where(weight > 0, 0, -1))
+        return out
+    check(lib.cips3d_mesh_fill_colors(dev_ptr(colors, "colors"), dev_ptr(weight, "weight"), dev_ptr(faces, "faces", dtype=torch.int32),
+                                      V, F, int(iters), dev_ptr(out["colors"], "colors_out"),
+                                      dev_ptr(out["filled"], "filled", dtype=torch.int32), dev_ptr(ws, "ws", dtype=torch.uint8),
+                                      stream_ptr()), "cips3d_mesh_fill_colors")
+    return out
+
+
+def mesh_texture_bake(verts, faces, normals, images, ws, keys, S, T, cols, rows, power=2, depth_tol=0.0, fill=0.0,
+                      vertex_colors=None, filled=None, want=("texture", "weight", "seen"), out=None):
+    """cips3d_mesh_texture_bake after mesh_rasterize (same verts, faces, workspace, keys, S) into the atlas (T, cols, rows) of
+    mesh_atlas_layout -> dict with the entries named in `want` (and every entry `out` holds a tensor for): texture [3,Ht,Wt]
+    fp32, weight [Ht,Wt] fp32, seen [Ht,Wt] int32.  vertex_colors [V,3] / filled [V] int32 (mesh_fill_colors), both or neither:
+    the colour of the texels no view sees.  Enqueued only."""
+    lib = _lib.load()
+    V, F, n, S = verts.shape[0], faces.shape[0], keys.shape[0], int(S)
+    T, cols, rows = int(T), int(cols), int(rows)
+    if verts.dim() != 2 or verts.shape[1] != 3 or tuple(normals.shape) != (V, 3) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("mesh_texture_bake: verts and normals must be [V, 3], faces [F, 3]")
+    if images.dim() != 4 or images.shape[0] != n or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+        raise RuntimeError(f"mesh_texture_bake: images must be [{n}, 3, R, R], one square picture per rasterised view")
+    if tuple(keys.shape) != (n, S, S) or ws.numel() < lib.cips3d_mesh_raster_workspace_bytes(V, F, n, S):
+        raise RuntimeError("mesh_texture_bake: workspace / keys do not fit these sizes")
+    if (vertex_colors is None) != (filled is None):
+        raise RuntimeError("mesh_texture_bake: give vertex_colors and filled together")
+    if vertex_colors is not None and (tuple(vertex_colors.shape) != (V, 3) or tuple(filled.shape) != (V,)):
+        raise RuntimeError("mesh_texture_bake: vertex_colors must be [V, 3], filled [V]")
+    if T < 3 or T > 64 or cols < 1 or rows < 0 or cols * rows < (F + 1) // 2:
+        raise RuntimeError(f"mesh_texture_bake: an atlas of {cols} x {rows} cells of {T} texels does not hold {F} faces")
+    Ht, Wt = rows * T, cols * (T + 1)
+    out = dict(out or {})
+    names = set(want) | set(out)
+    shapes = {"texture": ((3, Ht, Wt), torch.float32), "weight": ((Ht, Wt), torch.float32), "seen": ((Ht, Wt), torch.int32)}
+    if not names or names - set(shapes):
+        raise RuntimeError(f"mesh_texture_bake: outputs must be among {sorted(shapes)}, at least one")
+    for name in names:
+        shape, dt = shapes[name]
+        if out.get(name) is None:
+            out[name] = torch.empty(shape, dtype=dt, device=verts.device)
+        elif tuple(out[name].shape) != shape:
+            raise RuntimeError(f"mesh_texture_bake: {name} must be {shape}")
+
+    def ptr(t, name, dtype=torch.float32):
+        return None if t is None or t.numel() == 0 else dev_ptr(t, name, dtype=dtype)
+    p = _lib.MeshTextureParams(
+        verts=ptr(verts, "verts"), faces=ptr(faces, "faces", torch.int32), normals=ptr(normals, "normals"), images=ptr(images, "images"),
+        workspace=dev_ptr(ws, "ws", dtype=torch.uint8), keys=dev_ptr(keys, "keys", dtype=torch.int64),
+        vertex_colors=ptr(vertex_colors, "vertex_colors"), filled=ptr(filled, "filled", torch.int32),
+        texture=ptr(out.get("texture"), "texture"), weight=ptr(out.get("weight"), "weight"), seen=ptr(out.get("seen"), "seen", torch.int32),
+        V=V, F=F, n_views=n, S=S, R=int(images.shape[2]), power=int(power), T=T, cols=cols, rows=rows, depth_tol=float(depth_tol),
+        fill=float(fill))
+    if V and F:
+        check(lib.cips3d_mesh_texture_bake(C.byref(p), stream_ptr()), "cips3d_mesh_texture_bake")
+    return out
+
+
+def mesh_textured_frame(face, bary, shade, texture, n_faces, T, cols, rows, out=None):
+    """cips3d_mesh_textured_frame: mesh_resolve's face [n,S,S] int32, bary [n,S,S,3] and shade [n,S,S], texture [3,Ht,Wt] of the
+    atlas (T, cols, rows) for n_faces faces -> uint8 [n,3,S,S] = shade x (texel + 1) / 2, white where empty.  Enqueued only."""
+    n, S = face.shape[0], face.shape[1]
+    T, cols, rows, F = int(T), int(cols), int(rows), int(n_faces)
+    if tuple(face.shape) != (n, S, S) or tuple(shade.shape) != (n, S, S) or tuple(bary.shape) != (n, S, S, 3):
+        raise RuntimeError("mesh_textured_frame: face and shade must be [n, S, S], bary [n, S, S, 3]")
+    if tuple(texture.shape) != (3, rows * T, cols * (T + 1)):
+        raise RuntimeError(f"mesh_textured_frame: texture must be {(3, rows * T, cols * (T + 1))}")
+    if out is None:
+        out = torch.empty(n, 3, S, S, dtype=torch.uint8, device=face.device)
+    elif tuple(out.shape) != (n, 3, S, S):
+        raise RuntimeError(f"mesh_textured_frame: out must be {(n, 3, S, S)}")
+    if n and F == 0:
+        out.fill_(255)                        # no face: every pixel is empty (the library launches nothing)
+    elif n:
+        check(_lib.load().cips3d_mesh_textured_frame(dev_ptr(face, "face", dtype=torch.int32), dev_ptr(bary, "bary"),
+                                                     dev_ptr(shade, "shade"), dev_ptr(texture, "texture"),
+                                                     dev_ptr(out, "out", dtype=torch.uint8), n, S, F, T, cols, rows, stream_ptr()),
+              "cips3d_mesh_textured_frame")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- VGG16 conv loss (csrc/vgg.hip)
 def vgg_supported(B, H, W):
     """cips3d_vgg_supported as a bool: B >= 1, H and W multiples of 16 (decided on the host; perceptual.VGG16ConvLoss)."""

@@ -18,6 +18,10 @@ models/model_v3.py:344-415 (`NoiseInjection.project_noise`), with the midpoint `
 The third colours the mesh (csrc/mesh_color.hip; an extension, the reference exports a grey surface): `vertex_colors` gathers
 pictures of the mesh onto its vertices through the rasteriser's own visibility, `color_mesh` takes those pictures from the
 generator, and `render_mesh_frames(colors=)` draws the result.
+
+The fourth gives it a texture (csrc/mesh_texture.hip): `texture_atlas` lays two faces into every cell of an arithmetic atlas,
+`fill_colors` grows the vertex colours into the vertices no view saw, `bake_texture` applies `vertex_colors`' rule to every
+texel, `texture_mesh` does all of it from the generator's pictures, and `render_textured_frames` draws the result.
 """
 import math
 
@@ -67,7 +71,8 @@ def extract_mesh_with_marching_cubes(sdf, level=0.0, normals=False):
 
 @torch.no_grad()
 def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_samples=None, locations=None, fov_ang=6,
-                 dist_radius=0.12, near=0.88, far=1.12, level=0.0, normals=False, colors=False, color_kw=None):
+                 dist_radius=0.12, near=0.88, far=1.12, level=0.0, normals=False, colors=False, color_kw=None, texture=False,
+                 texture_kw=None):
     """The reference's surface extraction on the renderer only (the decoder is not run): mapping network ->
     `G.renderer.render(..., return_sdf=True)` at resolution^2 rays x N_samples (default: resolution) with perturbation off
     -> align_volume -> marching cubes per view.
@@ -79,16 +84,20 @@ def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_
     colors=True (needs normals=True and a decoder latent: zs = [z_renderer, z_decoder]): every mesh is coloured by
     `color_mesh(G, ..., **color_kw)` from its own sample's latents and becomes (verts, faces, normals, colors); the dict gains
     "color_weight" and "color_seen", one entry per view (None where there is no mesh).
+    texture=True (the same needs): every mesh gets a texture atlas by `texture_mesh(G, ..., **color_kw, **texture_kw)`; the dict
+    gains "textures", one `texture_mesh` dict per view (None where there is no mesh).  With colors=True as well the pictures are
+    rendered once, and the colours are the ones colors=True alone gives.
 
     Runs on the caller's stream through the renderer's lane-0 tables: do not issue it from inside a `ViewPipeline` lane
     (pipeline.py) while that pipeline has views in flight."""
     from .camera import Camera
     dev = next(G.parameters()).device
-    if colors:
+    if colors or texture:
+        what = "colors=True" if colors else "texture=True"
         if not normals:
-            raise ValueError("surface_mesh(colors=True) needs normals=True: the colours are weighted by the vertex normals")
+            raise ValueError(f"surface_mesh({what}) needs normals=True: the colours are weighted by the vertex normals")
         if style_render is not None or not isinstance(zs, (list, tuple)) or len(zs) < 2:
-            raise ValueError("surface_mesh(colors=True) needs the decoder's latent too: zs = [z_renderer, z_decoder]")
+            raise ValueError(f"surface_mesh({what}) needs the decoder's latent too: zs = [z_renderer, z_decoder]")
     if style_render is None:
         if zs is None:
             zs = [torch.randn(1, G.z_dim, device=dev)]
@@ -110,16 +119,26 @@ def surface_mesh(G, zs=None, style_render=None, truncation=1, resolution=128, N_
     aligned = align_volume(sdf, near, far)
     meshes = [extract_mesh_with_marching_cubes(aligned[b:b + 1], level, normals=normals) for b in range(B)]
     out = {"sdf": sdf, "aligned": aligned, "meshes": meshes}
-    if colors:
+    if colors or texture:
         kw = dict(fov_ang=fov_ang, dist_radius=dist_radius, truncation=truncation)
         kw.update(color_kw or {})
-        out["color_weight"], out["color_seen"] = [None] * B, [None] * B
+        if colors:
+            out["color_weight"], out["color_seen"] = [None] * B, [None] * B
+        if texture:
+            kw.update(texture_kw or {})
+            out["textures"] = [None] * B
         for b, m in enumerate(meshes):
             if m is None:
                 continue
-            c = color_mesh(G, m[0], m[1], m[2], zs=[z[b:b + 1].to(dev) for z in zs[:2]], **kw)
-            meshes[b] = (m[0], m[1], m[2], c["colors"])
-            out["color_weight"][b], out["color_seen"][b] = c["weight"], c["seen"]
+            zb = [z[b:b + 1].to(dev) for z in zs[:2]]
+            if texture:
+                t = out["textures"][b] = texture_mesh(G, m[0], m[1], m[2], zs=zb, **kw)
+                c = {"colors": t["seen_colors"], "weight": t["color_weight"], "seen": t["color_seen"]}
+            else:
+                c = color_mesh(G, m[0], m[1], m[2], zs=zb, **kw)
+            if colors:
+                meshes[b] = (m[0], m[1], m[2], c["colors"])
+                out["color_weight"][b], out["color_seen"][b] = c["weight"], c["seen"]
     return out
 
 
@@ -228,8 +247,15 @@ def color_mesh(G, verts, faces, normals, zs=None, style_render=None, style_decod
 
     Runs on the caller's stream through the generator's lane-0 plans and tables, like `surface_mesh`: do not issue it from
     inside a `ViewPipeline` lane (pipeline.py) while that pipeline has views in flight."""
+    images, locs = _color_views(G, verts.device, zs, style_render, style_decoder, truncation, views, img_size, N_samples, fov_ang,
+                                dist_radius, noise_bufs)
+    return vertex_colors(verts, faces, normals, images, locs[:, 0], locs[:, 1], fov_deg=2.0 * float(fov_ang), dist=1.0,
+                         **vertex_colors_kw)
+
+
+def _color_views(G, dev, zs, style_render, style_decoder, truncation, views, img_size, N_samples, fov_ang, dist_radius, noise_bufs):
+    """The generator's pictures of one latent from `views` (color_mesh's renders) -> (images [n,3,R,R] fp32, locs [n,2])."""
     from .camera import Camera
-    dev = verts.device
     if (style_render is None) != (style_decoder is None):
         raise ValueError("color_mesh: give style_render and style_decoder together")
     if style_render is None and (not isinstance(zs, (list, tuple)) or len(zs) < 2):
@@ -245,8 +271,125 @@ def color_mesh(G, verts, faces, normals, zs=None, style_render=None, style_decod
                 truncation=truncation, style_render=style_render, style_decoder=style_decoder, noise_bufs=noise_bufs,
                 nerf_cfg=dict(N_samples=N_samples, perturb=False))
         images.append(out["rgb"].float())
-    return vertex_colors(verts, faces, normals, torch.cat(images, 0), locs[:, 0], locs[:, 1], fov_deg=2.0 * float(fov_ang),
-                         dist=1.0, **vertex_colors_kw)
+    return torch.cat(images, 0), locs
+
+
+# ------------------------------------------------------------------------------------------------ texture atlas
+def texture_atlas(n_faces, texels=8, cols=None):
+    """The atlas of a mesh of n_faces faces (csrc/mesh_texture.h; pure arithmetic, no unwrap): faces 2c and 2c + 1 share cell c
+    of (T + 1) x T texels, T = texels in 3..64; `cols` cells per row (default: the atlas about square) ->
+    {"T", "cols", "rows", "width", "height", "n_faces", "uv": [F,3,2] fp32 on the CPU, the faces' corner UVs in continuous
+    texel coordinates (the centre of texel k is k + 1/2; gen_images.write_textured_obj turns them into `vt` lines)}.
+    Every face owns T (T - 1) / 2 texels and T gutter texels; a bilinear fetch inside a face's UV triangle touches only those.
+    Raises RuntimeError when a side would exceed 16384 texels."""
+    c, r, w, h = hip.mesh_atlas_layout(n_faces, texels, cols)
+    return {"T": int(texels), "cols": c, "rows": r, "width": w, "height": h, "n_faces": int(n_faces),
+            "uv": torch.from_numpy(hip.mesh_atlas_uv(n_faces, texels, c))}
+
+
+def atlas_texels(atlas):
+    """Per texel of `atlas` (texture_atlas), on the CPU: {"face": [Ht,Wt] int32, -1 where no face owns the texel; "bary":
+    [Ht,Wt,3] fp32, the texel's barycentrics in its face; "gutter": [Ht,Wt] bool} -- the bake kernel's own decisions."""
+    face, bary, gutter = hip.mesh_atlas_texels(atlas["n_faces"], atlas["T"], atlas["cols"], atlas["rows"])
+    return {"face": torch.from_numpy(face), "bary": torch.from_numpy(bary), "gutter": torch.from_numpy(gutter)}
+
+
+def fill_colors(colors, weight, faces, iters=64):
+    """Grows the colours of the vertices some view saw (weight > 0: vertex_colors' outputs) into the others, ring by ring over
+    the faces' edges: a vertex unfilled at the start of ring r takes the mean of the corners, filled before ring r, of the faces
+    it belongs to (one term per (face, corner) pair) -> {"colors": [V,3] fp32, "filled": [V] int32: 0 seen, r filled in ring r,
+    -1 never reached (it keeps its input colour)}.  iters in 0..4096, a design default; the sums are integers (2^-20 steps), so
+    the result is exact and bit-reproducible.  Contract: include/cips3d_hip.h (cips3d_mesh_fill_colors)."""
+    return hip.mesh_fill_colors(colors.float().contiguous(), weight.float().contiguous(), _faces_i32(faces), iters=iters)
+
+
+def bake_texture(verts, faces, normals, images, azim, elev, texels=8, cols=None, vertex_colors=None, filled=None, fov_deg=12.0,
+                 dist=1.0, znear=0.01, raster_size=512, depth_tol=None, power=2, fill=0.0, ws=None, keys=None, atlas=None):
+    """A texture for the mesh from `images` [n,3,R,R], pictures of it taken by the cameras (azim, elev) -- `vertex_colors`'
+    inputs and rule, applied to every texel of `texture_atlas(F, texels, cols)` instead of every vertex: the texel's surface
+    point and normal come from its barycentrics in its face, the point is projected with the rasteriser's arithmetic, and
+    visibility, facing, weight and the bilinear sample follow vertex_colors word for word.
+    vertex_colors [V,3] / filled [V] (fill_colors' outputs), both or neither: a texel no view sees takes the barycentric mix
+    of its corners' colours when all three are filled, else `fill`.
+    -> {"texture": [3,Ht,Wt] fp32 in [-1, 1], "weight": [Ht,Wt] fp32, "seen": [Ht,Wt] int32, "atlas": the atlas dict}.
+    Contract: include/cips3d_hip.h (cips3d_mesh_texture_bake)."""
+    verts = verts.float().contiguous()
+    f32 = _faces_i32(faces)
+    cams = camera_rows(azim, elev, fov_deg, dist, znear, device=verts.device)
+    images = images.float().contiguous()
+    if images.dim() != 4 or images.shape[0] != cams.shape[0]:
+        raise ValueError(f"bake_texture: {cams.shape[0]} cameras need images [{cams.shape[0]}, 3, R, R]")
+    if depth_tol is None:
+        depth_tol = FRAME_SCALE / 128
+    if f32.shape[0] == 0:
+        raise ValueError("bake_texture: a mesh without faces has no surface to texture")
+    if atlas is None:
+        atlas = texture_atlas(f32.shape[0], texels, cols)
+    elif atlas["n_faces"] != f32.shape[0]:
+        raise ValueError(f"bake_texture: the atlas was laid out for {atlas['n_faces']} faces, the mesh has {f32.shape[0]}")
+    ws, keys = hip.mesh_rasterize(verts, f32, cams, raster_size, ws=ws, keys=keys)
+    out = hip.mesh_texture_bake(verts, f32, normals.float().contiguous(), images, ws, keys, raster_size, atlas["T"], atlas["cols"],
+                                atlas["rows"], power=power, depth_tol=depth_tol, fill=fill,
+                                vertex_colors=None if vertex_colors is None else vertex_colors.float().contiguous(),
+                                filled=None if filled is None else filled.to(torch.int32).contiguous())
+    out["atlas"] = atlas
+    return out
+
+
+@torch.no_grad()
+def texture_mesh(G, verts, faces, normals, zs=None, style_render=None, style_decoder=None, truncation=1, views=DEFAULT_COLOR_VIEWS,
+                 img_size=64, N_samples=24, fov_ang=6, dist_radius=0.12, noise_bufs=None, texels=8, cols=None, fill_iters=64,
+                 **vertex_colors_kw):
+    """`color_mesh`'s pictures, rendered once, used three times: vertex colours -> `fill_colors` (fill_iters rings) ->
+    `bake_texture` with the filled colours behind the texels no view sees.  One rasterisation serves the colours and the bake.
+    -> {"texture", "weight", "seen", "atlas" (bake_texture), "colors", "filled" (fill_colors), "seen_colors", "color_weight",
+    "color_seen" (vertex_colors' colors, weight, seen), "images"}.  vertex_colors_kw: raster_size, depth_tol, power, fill, znear.  Counts of seen / filled / unfilled
+    texels: `texel_counts`.  Runs on the caller's stream, like `color_mesh`."""
+    images, locs = _color_views(G, verts.device, zs, style_render, style_decoder, truncation, views, img_size, N_samples, fov_ang,
+                                dist_radius, noise_bufs)
+    kw = dict(fov_deg=2.0 * float(fov_ang), dist=1.0, **vertex_colors_kw)
+    S = kw.get("raster_size", 512)
+    verts = verts.float().contiguous()
+    ws, keys = hip.mesh_raster_workspace(verts.shape[0], faces.shape[0], locs.shape[0], S, verts.device)
+    col = vertex_colors(verts, faces, normals, images, locs[:, 0], locs[:, 1], ws=ws, keys=keys, **kw)
+    grown = fill_colors(col["colors"], col["weight"], faces, iters=fill_iters)
+    out = bake_texture(verts, faces, normals, images, locs[:, 0], locs[:, 1], texels=texels, cols=cols, vertex_colors=grown["colors"],
+                       filled=grown["filled"], ws=ws, keys=keys, **kw)
+    out.update(colors=grown["colors"], filled=grown["filled"], seen_colors=col["colors"], color_weight=col["weight"],
+               color_seen=col["seen"], images=images)
+    return out
+
+
+def texel_counts(baked, filled, faces):
+    """(seen, filled, never) texel counts of a baked atlas (one synchronisation): owned and gutter texels some view sees; those
+    none sees whose three corners `fill_colors` reached; those left at the constant fill.  Unowned texels are not counted."""
+    tex = atlas_texels(baked["atlas"])
+    face = tex["face"].to(baked["seen"].device)
+    owned = face >= 0
+    seen = owned & (baked["weight"] > 0)
+    ok = (filled[faces.long()] >= 0).all(1)[face.clamp_min(0).long()]
+    return int(seen.sum()), int((owned & ~seen & ok).sum()), int((owned & ~seen & ~ok).sum())
+
+
+def texture_to_uint8(texture):
+    """[3,Ht,Wt] fp32 in [-1, 1] -> uint8 with the image pipeline's rounding (cips3d_rgb_to_uint8 takes any map size)."""
+    return hip.rgb_to_uint8(texture)
+
+
+def render_textured_frames(verts, faces, normals, trajectory, texture, atlas, image_size=512, light=None):
+    """`render_mesh_frames` at texture resolution: the Phong shade of every pixel times the bilinear fetch of `texture`
+    [3,Ht,Wt] (bake_texture) at the pixel's point in its face's UV triangle of `atlas` -> uint8 [n,3,S,S], white exactly where
+    the plain panel is white.  Contract: include/cips3d_hip.h (cips3d_mesh_textured_frame)."""
+    traj = torch.as_tensor(trajectory, dtype=torch.float32).to(verts.device)
+    az, el = traj[:, 0], traj[:, 1]
+    if light is None:
+        light = torch.stack([5 * torch.sin(az), torch.zeros_like(az), 5 * torch.cos(az)], 1)
+    if atlas["n_faces"] != faces.shape[0]:
+        raise ValueError(f"render_textured_frames: the atlas was laid out for {atlas['n_faces']} faces, the mesh has {faces.shape[0]}")
+    out = rasterize_mesh(verts, faces, az, el, image_size, fov_deg=2.0 * traj[:, 2], dist=1.0, normals=normals,
+                         light=light.float().contiguous(), want=("face", "bary", "shade"))
+    return hip.mesh_textured_frame(out["face"], out["bary"], out["shade"], texture.float().contiguous(), atlas["n_faces"], atlas["T"],
+                                   atlas["cols"], atlas["rows"])
 
 
 def subdivide(verts, faces):

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 43  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 44  /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1380,6 +1380,78 @@ int cips3d_mesh_vertex_colors(const cips3d_mesh_color_params* p, void* stream);
  * face < 0.  CIPS3D_E_BADARG: a null pointer, n_views < 0, S < 1.  CIPS3D_E_UNSUPP: S > 16384, n_views > 65536. */
 int cips3d_mesh_albedo_frame(const int32_t* face, const float* shade, const float* attr, uint8_t* out, int n_views, int S,
                              void* stream);
+
+/* ------------------------------------------------------------------ mesh texture atlas (csrc/mesh_texture.hip) */
+
+/* Atlas layout (csrc/mesh_texture.h; pure arithmetic, no unwrap).  T = texels, 3 <= T <= 64, m = T - 2.  Faces 2c and 2c + 1
+ * share cell c, (T + 1) x T texels at cell column c % cols, cell row c / cols; cells = ceil(F / 2); cols defaults to the
+ * smallest integer with cols^2 (T + 1) >= cells T (= max(1, ceil(sqrt(cells T / (T + 1))))); rows = ceil(cells / cols);
+ * Wt = cols (T + 1), Ht = rows T, both <= 16384.  A texel at local (i, j) of its cell, d = i + j:
+ *   d <= m: face 2c, owned, lattice (li, lj) = (i, j);            d == m + 1: face 2c, gutter, (i - 1/2, j - 1/2);
+ *   d == m + 2: face 2c + 1, gutter, (i' - 1/2, j' - 1/2);        d >= m + 3: face 2c + 1, owned, (i', j');   i' = T - i, j' = T - 1 - j.
+ * A texel whose face is >= F is unowned.  Barycentrics of a texel: b1 = clamp(li / m, 0, 1), b2 = clamp(lj / m, 0, 1),
+ * b0 = max(0, (1 - b1) - b2).  Every face has T (T - 1) / 2 owned and T gutter texels.  Corner UVs in continuous texel
+ * coordinates (the centre of texel k is k + 1/2; (ox, oy) the cell's origin): face 2c: (ox + 1/2, oy + 1/2), (ox + 1/2 + m, oy + 1/2),
+ * (ox + 1/2, oy + 1/2 + m); face 2c + 1: (ox + T + 1/2, oy + T - 1/2), (ox + T + 1/2 - m, oy + T - 1/2), (ox + T + 1/2, oy + T - 1/2 - m).
+ * A bilinear fetch at a point inside a face's UV triangle touches, with non-zero weight, only that face's owned and gutter texels.
+ * The three calls below run on the host: the layout for F faces (cols_in = 0: the default), uv_host [F,3,2], and the texel
+ * maps face_host [Ht,Wt] int32 (-1: unowned), bary_host [Ht,Wt,3], gutter_host [Ht,Wt] (each may be NULL).
+ * CIPS3D_E_BADARG: T outside 3..64, a negative size, a null required pointer, cols x rows cells that do not hold F faces;
+ * CIPS3D_E_UNSUPP: Wt or Ht > 16384, F > INT32_MAX. */
+int cips3d_mesh_atlas_layout(int64_t F, int T, int cols_in, int32_t* cols, int32_t* rows, int32_t* width, int32_t* height);
+int cips3d_mesh_atlas_uv(int64_t F, int T, int cols, float* uv_host);
+int cips3d_mesh_atlas_texels(int64_t F, int T, int cols, int rows, int32_t* face_host, float* bary_host, uint8_t* gutter_host);
+
+/* Grows colours from the vertices some view saw into those none saw, ring by ring.  colors [V,3], weight [V] (of
+ * cips3d_mesh_vertex_colors), faces [F,3] -> colors_out [V,3] (not `colors` itself), filled [V] int32.  Initially
+ * filled[v] = weight[v] > 0 ? 0 : -1.  For ring r = 1..iters (0 <= iters <= 4096) and every vertex a unfilled at the start of the
+ * ring: S_a = sum of q(col[b]), q(x) = (int64) rintf(x 2^20) per channel, over all (face containing a, other corner b of it) pairs
+ * whose b was filled before ring r; n_a = the number of such pairs; n_a > 0: col[a] = (float) ((double) S_a / ((double) n_a 1048576.0)),
+ * filled[a] = r.  Seen vertices keep their bits; a vertex no ring reaches keeps its input colour and -1.  The sums are 64-bit
+ * integer atomic adds: exact, independent of order and grid.  workspace: cips3d_mesh_fill_workspace_bytes(V) bytes, cleared by
+ * the call.  All rings are enqueued at once (2 launches each); after a ring that filled nothing the remaining launches return on
+ * a device flag.  Does not synchronise.  A face with a vertex id outside [0, V) is skipped.
+ * CIPS3D_E_BADARG, nothing launched: a null pointer, a negative size, iters outside 0..4096, colors_out == colors.
+ * CIPS3D_E_UNSUPP: V or F > INT32_MAX.  V == 0 or F == 0: returns 0, launches nothing, writes nothing. */
+int64_t cips3d_mesh_fill_workspace_bytes(int64_t V);
+int cips3d_mesh_fill_colors(const float* colors, const float* weight, const int32_t* faces, int64_t V, int64_t F, int iters,
+                            float* colors_out, int32_t* filled, void* workspace, void* stream);
+
+/* Bakes the atlas from n_views pictures of the mesh.  Called after cips3d_mesh_rasterize on the same stream with the same verts,
+ * faces, workspace, keys, n_views and S (images, normals, R, depth_tol, power, fill: as cips3d_mesh_vertex_colors).  One thread
+ * per atlas texel, views in ascending order, no atomics: independent of the grid, bit-reproducible.
+ *   unowned texel (or a face with a vertex id outside [0, V)): `fill`, weight 0, seen 0;
+ *   p = (b0 v0 + b1 v1) + b2 v2 per component; n = the same combination of the corners' normals, divided by max(|n|, 1e-12);
+ *   per view: p is projected with the rasteriser's vertex arithmetic (derived camera of the workspace; x_p, y_p, z; dropped when
+ *   z < znear or z <= 0), and from there cips3d_mesh_vertex_colors' contract holds word for word (pixel rint, off-frame, z* of
+ *   the key, z <= z* + depth_tol, c = n . d > 0, w = c^power, bilinear sample at u = (x_p + 1/2) R / S - 1/2);
+ *   texel = acc / wsum; where wsum == 0: (b0 c0 + b1 c1) + b2 c2 of vertex_colors [V,3] when vertex_colors and filled [V]
+ *   (cips3d_mesh_fill_colors) are given and the three corners have filled >= 0, else `fill`.
+ * Outputs (each may be NULL, at least one is required): texture [3,Ht,Wt] fp32, weight [Ht,Wt] fp32, seen [Ht,Wt] int32.
+ * Does not synchronise.  CIPS3D_E_BADARG, nothing launched: a null required pointer, no output, vertex_colors without filled or
+ * the reverse, a negative size, S < 1, R < 1, power outside 1..8, T outside 3..64, cols x rows cells that do not hold F faces.
+ * CIPS3D_E_UNSUPP: the rasteriser's limits, R > 16384, Wt or Ht > 16384.  V == 0 or F == 0: returns 0, launches nothing. */
+typedef struct cips3d_mesh_texture_params {
+  const float* verts; const int32_t* faces; const float* normals; const float* images; const void* workspace; const uint64_t* keys;
+  const float* vertex_colors; const int32_t* filled;
+  float* texture; float* weight; int32_t* seen;
+  int32_t V, F, n_views, S, R, power, T, cols, rows;
+  float depth_tol, fill;
+  int32_t pad_;
+} cips3d_mesh_texture_params;
+int cips3d_mesh_texture_bake(const cips3d_mesh_texture_params* p, void* stream);
+
+/* The coloured mesh frame at texture resolution, from cips3d_mesh_resolve's maps face [n,S,S] int32, bary [n,S,S,3], shade [n,S,S]
+ * and texture [3,Ht,Wt] of an atlas (T, cols, rows) for F faces -> out [n,3,S,S] uint8.  A hit pixel (0 <= face < F):
+ * b1 = clamp(w1, 0, 1), b2 = clamp(w2, 0, 1 - b1); the point b0 uv0 + b1 uv1 + b2 uv2 of the face's corner UVs is fetched
+ * bilinearly at (x - 1/2, y - 1/2).  In the face's lattice that point is (fx, fy) = (b1 m, min(b2 m, fl(m - fx))), its taps are
+ * the lattice texels (floor(fx) + {0,1}, floor(fy) + {0,1}) with weights (1 - frac, frac): all of them inside the face's cell,
+ * and those of non-zero weight among the face's own owned and gutter texels.  c = (1 - wy) ((1 - wx) t00 + wx t10) +
+ * wy ((1 - wx) t01 + wx t11);  out = floor(255 clamp(shade (c + 1) / 2, 0, 1) + 0.5); every other pixel is 255 (the albedo
+ * frame's formula and background).  CIPS3D_E_BADARG: a null pointer, a negative size, S < 1, a bad atlas; CIPS3D_E_UNSUPP:
+ * S > 16384, n_views > 65536, Wt or Ht > 16384.  n_views == 0 or F == 0: returns 0, launches nothing. */
+int cips3d_mesh_textured_frame(const int32_t* face, const float* bary, const float* shade, const float* texture, uint8_t* out,
+                               int n_views, int S, int64_t F, int T, int cols, int rows, void* stream);
 
 /* VGG16 conv perceptual loss of flip inversion (csrc/vgg.hip; reference exp/cips3d/models/vgg_per_loss.py:203-334,
  * models/projector_v10.py:131-151, 1170-1174).  The network is the 13 convolutions of torchvision's vgg16.features
