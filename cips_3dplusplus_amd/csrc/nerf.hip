@@ -463,7 +463,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     float sigma;
     if (raw_density) {        // with_sdf = False (nerf_utils.py:288-297): softplus of the raw density.  A real (uniform) branch and
       // the hardware exp / log: the library forms held enough temporaries here to spill four registers of the default path
-      sigma = sdf > 20.f ? sdf : __logf(1.f + __expf(sdf));
+      sigma = nerf_softplus_hw(sdf);
     } else {
       sigma = nerf_sdf_density(sdf, sig_beta);
     }

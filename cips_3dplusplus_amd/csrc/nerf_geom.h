@@ -22,6 +22,18 @@ __device__ __forceinline__ float nerf_sigmoid(float v) { return 1.f / (1.f + exp
 // with_sdf density (nerf_utils.py:276-286), and F.softplus of the raw density (:288-297; torch's threshold 20: identity above it)
 __device__ __forceinline__ float nerf_sdf_density(float sdf, float beta) { return nerf_sigmoid(-sdf / beta) / beta; }
 __device__ __forceinline__ float nerf_softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }
+// The render kernel's softplus (nerf.hip; every other kernel uses nerf_softplus): the library log1pf / expf held enough temporaries
+// to spill four registers of the kernel's default (with_sdf) path, so it takes the hardware exp and log behind its uniform
+// branch.  log(1 + e) alone is 0 once e = exp(v) < 2^-24 (v < -16.6), yet the last sample of a ray (delta = 1e10) still has
+// alpha = 1 - exp(-e 1e10 |d|) ~ 1 down to v ~ -21: an empty ray of a density model lost its background weight.  Below
+// e = 2^-12 the series e - e^2 / 2 (relative error < e^2 / 3 = 2e-8) takes over; above it the rounding of 1 + e costs sigma at
+// most 2^-24 absolute: nothing for a sample of finite delta, and the last sample's alpha is 1 there anyway (sigma 1e10 > 2e6).
+// tests/test_gpu_nerf_fwd.py holds it to fp64 at biases -20 .. +25 of the density head.
+__device__ __forceinline__ float nerf_softplus_hw(float v) {
+  if (v > 20.f) return v;
+  const float e = __expf(v);
+  return e < 0x1p-12f ? fmaf(-0.5f * e, e, e) : __logf(1.f + e);
+}
 
 __device__ __forceinline__ float nerf_norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 

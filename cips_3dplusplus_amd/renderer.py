@@ -344,12 +344,15 @@ class VolumeFeatureRenderer(nn.Module):
         return self.network(torch.cat([inputs, dirs], -1), styles=styles)
 
     @torch.no_grad()
-    def forward(self, pts, rays_d, viewdirs, z_vals, near, far, styles=None, return_eikonal=False, N_samples_forward=None):
+    def forward(self, pts, rays_d, viewdirs, z_vals, near, far, styles=None, return_eikonal=False, N_samples_forward=None,
+                film=None, n_chunks=None):
         """The reference entry (volume_renderer.py:192-303): explicit sample points instead of a camera.
         pts (b h w N 3) or (b hw N 3); rays_d / viewdirs (b h w 3) | (b hw 3); z_vals (b h w N) | (b hw N); near / far
         (b 1 1); styles (b, D+1, style_dim) -> rgb_map (.., 3), feature_map (.., C), sdf (.., N, 1), mask (.., 2),
         xyz (.., 3), eikonal_term.  Runs the same fused kernel in its explicit-geometry instantiation;
         `N_samples_forward` (a memory bound of the reference) is accepted and ignored.
+        film: a FiLM table [B, D+1, 2, H] computed by the caller (styles is then not read), n_chunks: the chunks a ray's samples
+        are split into -- both as in `render`.
         return_eikonal: eikonal_term = d sdf / d pts, the shape of `pts` (volume_renderer.py:223-226), from the gradient kernel
         (`sdf_gradient`; a constant, no graph); None otherwise and for with_sdf=False renderers, as in the reference."""
         if return_eikonal and self.with_sdf and not hip.nerf_sdf_grad_supported(self.hidden_dim, self.N_layers_renderer):
@@ -367,10 +370,14 @@ class VolumeFeatureRenderer(nn.Module):
         z = z_vals.float().reshape(B, R, N).contiguous()
         net = self.network
         packed, layer_bias = self._derived_buffers()
-        styles_buf, film, tab = self._film_table(B, dev)
-        styles_buf.copy_(styles)
-        tab.run(B)
-        n_chunks = max(1, min(N, hip.nerf_suggest_chunks(B, max(1, int(R ** 0.5)), N)))
+        if film is None:
+            styles_buf, film, tab = self._film_table(B, dev)
+            styles_buf.copy_(styles)
+            tab.run(B)
+        else:
+            film = film.detach().float().contiguous()
+        if n_chunks is None:
+            n_chunks = max(1, min(N, hip.nerf_suggest_chunks(B, max(1, int(R ** 0.5)), N)))
         sdf = torch.empty(B, R, N, device=dev)
         features, thumb, xyz, mask = hip.nerf_render_maps(near_=near.float().reshape(B).contiguous(), far_=far.float().reshape(B).contiguous(),
                         w_first=net.pts_linears[0].weight, packed=packed, w_view=net.views_linears.weight, film=film,
