@@ -401,10 +401,16 @@ _SIGS = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_ssim_loss_bwd": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, C.c_float, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "cips3d_resample_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    "cips3d_resample_route": (c_int, [c_int] * 6),
+    "cips3d_resample_workspace_bytes": (c_i64, [c_int] * 9),
+    "cips3d_resample_u8": (c_int, [C.c_void_p, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, C.c_void_p, c_int, c_int, c_i64,
+                                   c_i64, c_i64, C.c_void_p, C.c_void_p, c_int, C.c_void_p, C.c_void_p, c_int, c_int, C.c_void_p,
+                                   c_i64, c_int, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 44           # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 45          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

@@ -82,8 +82,7 @@ __global__ void __launch_bounds__(256) rgb_to_u8_kernel(const float* __restrict_
       uint32_t pk = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float c = fminf(fmaxf(f[j], -1.f), 1.f);
-        pk |= (uint32_t)__float2int_rn((c + 1.f) * 127.5f) << (8 * j);
+        pk |= cips3d_quant_u8(f[j]) << (8 * j);
       }
       w[k] = pk;
     }
@@ -91,10 +90,7 @@ __global__ void __launch_bounds__(256) rgb_to_u8_kernel(const float* __restrict_
   }
   // tail (n % 16 elements), one thread
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (int64_t e = n16 * 16; e < n; ++e) {
-      const float c = fminf(fmaxf(x[e], -1.f), 1.f);
-      out[e] = (uint8_t)__float2int_rn((c + 1.f) * 127.5f);
-    }
+    for (int64_t e = n16 * 16; e < n; ++e) out[e] = (uint8_t)cips3d_quant_u8(x[e]);
 }
 
 }  // namespace

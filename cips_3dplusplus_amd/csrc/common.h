@@ -63,6 +63,13 @@ __device__ static inline float wave_sum(float v) {
   return v;
 }
 
+// The image pipeline's 8-bit quantiser, stated once: clamp to [-1, 1], (c + 1) 127.5, round to nearest even.  cips3d_rgb_to_uint8
+// (bias_act.hip), the fused stage's CIPS3D_RGB_U8 store, the metrics' and the frame resampler's quantise-on-load all call this.
+__device__ static inline unsigned cips3d_quant_u8(float v) {
+  const float c = fminf(fmaxf(v, -1.f), 1.f);
+  return (unsigned)__float2int_rn((c + 1.f) * 127.5f);
+}
+
 // leaky ReLU, slope 0.2: max(v, 0.2 v) is the select (v > 0 ? v : 0.2 v) for every finite v and both zeros, in two
 // instructions (v_mul, v_max) instead of three (v_mul, v_cmp, v_cndmask)
 __device__ static inline float lrelu02(float v) { return fmaxf(v, v * 0.2f); }

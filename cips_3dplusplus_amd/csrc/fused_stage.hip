@@ -706,10 +706,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, MINW) fused_up_conv_kernel(Fus
       // (render_video_web_v10.py:1825-1826) without the fp32 image's round trip through memory
       unsigned pk = 0;
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float cl = fminf(fmaxf(v[c], -1.f), 1.f);
-        pk |= (unsigned)__float2int_rn((cl + 1.f) * 127.5f) << (8 * c);
-      }
+      for (int c = 0; c < 4; ++c) pk |= cips3d_quant_u8(v[c]) << (8 * c);
       *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(a.rgb) + (int64_t)b * 3 * HWo + (ch * HWo + oy * OW + ox)) = pk;
     } else {
       cips3d_store_wt16(a.rgb + (int64_t)b * 3 * HWo + (ch * HWo + oy * OW + ox), v);

@@ -40,10 +40,7 @@ static_assert((int64_t)MT_ROWS * MT_COLS * 255 * 255 < ((int64_t)1 << 32), "a ti
 
 struct MtPartial { unsigned long long sse; float ssim; unsigned pad_; };   // 16 bytes per (image, channel, tile)
 
-__device__ static inline unsigned mt_quant(float v) {       // cips3d_rgb_to_uint8's arithmetic (csrc/bias_act.hip)
-  const float c = fminf(fmaxf(v, -1.f), 1.f);
-  return (unsigned)__float2int_rn((c + 1.f) * 127.5f);
-}
+__device__ static inline unsigned mt_quant(float v) { return cips3d_quant_u8(v); }       // cips3d_rgb_to_uint8's arithmetic (common.h)
 template <bool U8>
 __device__ static inline unsigned mt_load(const void* __restrict__ img, int64_t i) {
   if (U8) return static_cast<const uint8_t*>(img)[i];

@@ -125,7 +125,8 @@ def render_views_sharded(render_fn, n_views, keys=("rgb",), dst=0, group=None, c
 def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, truncation_ratio=0.5, N_samples=128,
                       zero_noise_bufs=False, noise_bufs=None, azim_range=(-0.77, 0.77), elev=0.0, circle=None,
                       trans_max=0.04, only_rotate=False, chunk=1, gather=("rgb", "thumb_rgb", "xyz"), to_uint8=True,
-                      group=None, hoist=True, uint8_in_kernel=True, lanes=2, project_noise=None):
+                      group=None, hoist=True, uint8_in_kernel=True, lanes=2, project_noise=None,
+                      panel=("rgb", "thumb_rgb", "shaded"), panel_resample="lanczos"):
     """The frame loop of `_sample_multi_view_web` (render_video_web_v10.py:1651-1899) without the web page: one z pair,
     one set of noise buffers, `perturb=False`, a camera trajectory (`yaw` / `circle` / `translate_rotate`), one
     `G(...)` call per `chunk` frames with `truncation=truncation_ratio, return_xyz=True`.  With torch.distributed
@@ -154,7 +155,14 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     (`G(project_noise=True, mesh_path=...)`, mesh.NoiseProjector), so the decoder's noise sticks to the surface.  chunk must be 1
     (the projection runs at batch 1).  Barycentric interpolation is convex, so max(|noise_bufs|, |vertex noise|) bounds every
     frame's maps: it is measured once here and handed to every call (`noise_bound=`), which keeps the range constants, and with
-    them `hoist`, valid without a measurement per frame; every call writes fresh maps on its own lane's stream."""
+    them `hoist`, valid without a measurement per frame; every call writes fresh maps on its own lane's stream.
+    `gather` may name "panel": the picture the demo shows and writes for a frame (render_video_web_v10.py:1825-1890) -- the panes
+    named in `panel` (of "rgb", "thumb_rgb", "shaded", "normal"), each resized to the image's size with Pillow's
+    `panel_resample` filter, bit for bit (`pil_utils.pil_resize`), side by side in one row (`merge_image_pil(..., nrow=3)`), as
+    uint8 (n, 3, R, len(panel) R).  Each call's panes are composed on the call's own lane straight into the rank's panel block
+    (frames.compose_panels, csrc/frame_resample.hip; fp32 panes are quantised on load), which travels to rank 0 as uint8 like
+    `rgb`.  Panes the panel needs are produced even when they are not gathered themselves; everything else the call returns
+    is what it returns without "panel"."""
     from . import hip
     from .camera import yaw_trajectory, circle_trajectory, cameras_from_trajectory, translate_rotate_cameras
     dev = next(G.parameters()).device
@@ -197,7 +205,15 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     from .pipeline import pipeline_for
     ws = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     lo, hi = view_slice(n_views, dist.get_rank(group) if ws > 1 else 0, ws)
-    want_normal, want_shaded = "normal" in gather, "shaded" in gather
+    want_panel = "panel" in gather
+    panel = tuple(panel)
+    if want_panel and (not panel or any(k not in ("rgb", "thumb_rgb", "shaded", "normal") for k in panel)):
+        raise ValueError(f'panel {panel!r}: one or more of "rgb", "thumb_rgb", "shaded", "normal"')
+    if want_panel:
+        from . import frames
+        frames._filter_name(panel_resample)            # (an unknown filter fails here, on every rank, before anything renders)
+    need = tuple(gather) + (panel if want_panel else ())
+    want_normal, want_shaded = "normal" in need, "shaded" in need
     if want_normal or want_shaded:
         if not G.renderer.with_sdf:
             raise NotImplementedError('gather "normal" / "shaded": a with_sdf=False renderer has no surface normal')
@@ -217,11 +233,24 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     full_done = [set() for _ in range(pipe.lanes)]     # per lane: call shapes (views per call) whose tables this sequence has computed
     frames_u8 = None                   # this rank's uint8 frames land in ONE block (no concatenation copy at the end)
     shaded_u8 = torch.empty(hi - lo, 3, img_size, img_size, dtype=torch.uint8, device=dev) if want_shaded else None
+    panel_u8 = None                    # this rank's panels: one block as well, every call composes into its slice
+
+    def compose_panel(r, a, b):
+        nonlocal panel_u8
+        Rh, Rw = r["rgb"].shape[-2:]
+        if panel_u8 is None:
+            panel_u8 = torch.empty(hi - lo, 3, Rh, len(panel) * Rw, dtype=torch.uint8, device=dev)
+        return frames.compose_panels([r[k] for k in panel], size=(Rh, Rw), resample=panel_resample, out=panel_u8[a - lo:b - lo])
 
     def render(a, b):
-        nonlocal frames_u8
+        nonlocal frames_u8, panel_u8
         direct = None
         static = bool(ncfg.get("static_viewdirs", False))
+        if want_panel and panel_u8 is None:
+            # made on the caller's stream, which every lane is ordered behind, where the image's size is known before the first call
+            plan = G._forward_plan(b - a, img_size, int(N_samples), static) if dev.type == "cuda" else None
+            if plan is not None:
+                panel_u8 = torch.empty(hi - lo, 3, plan.out_res, len(panel) * plan.out_res, dtype=torch.uint8, device=dev)
         if to_uint8 and uint8_in_kernel and G.can_emit_uint8(b - a, img_size, N_samples, static):
             # this rank's frames land in ONE uint8 block; where the decoder ends in a fused up-sampling stage the image leaves
             # that kernel as uint8 straight into its slice of the block (no fp32 image, no conversion launch)
@@ -252,6 +281,9 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
                 if frames_u8 is None:
                     frames_u8 = torch.empty((hi - lo,) + tuple(r["rgb"].shape[1:]), dtype=torch.uint8, device=dev)
                 r["rgb"] = hip.rgb_to_uint8(r["rgb"], out=frames_u8[a - lo:b - lo])
+            if want_panel:
+                r = dict(r)
+                r["panel"] = compose_panel(r, a, b)
             return r
 
         r = pipe.run(one_call)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 44  /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 45 /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -1643,6 +1643,51 @@ int cips3d_ssim_loss(const float* a, const float* b, int B, int C, int H, int W,
                      int need_grad, float* map, double* ssim, float* loss, void* stream);
 int cips3d_ssim_loss_bwd(const float* a, const float* b, int B, int C, int H, int W, float weight, const void* workspace,
                          const float* gloss, float* da, void* stream);
+
+/* ------------------------------------------------------------------ frame panels: Pillow's 8-bit resampling (csrc/frame_resample.hip)
+ * PIL.Image.resize((ow, oh), BOX | BILINEAR | BICUBIC | LANCZOS) (default box, reducing_gap=None) of every channel of planar 8-bit
+ * images, bit for bit: what the reference's demo pages do to each frame's thumbnail and geometry picture on the host before they
+ * paste the panel (render_video_web_v10.py:1825-1890), and `load_pil_crop_resize` to an inversion's target.
+ *
+ * The caller makes the tables on the host in float64 (cips_3dplusplus_amd/frames.py: resample_coeffs; Pillow's precompute_coeffs
+ * and normalize_coeffs_8bpc) and keeps them on the device.  Per axis of input size I and output size O:
+ *     bounds [O][2] int32   (xmin, n) of output index xx: its taps are input indices xmin .. xmin + n - 1, xmin + n <= I, both
+ *                           ends non-decreasing in xx
+ *     coeffs [O][ksize] int32   k = round(w 2^22) of the n normalised weights, zero behind them; ksize = 2 ceil(support) + 1
+ * and the kernels compute  clamp((2^21 + sum_x p[xmin + x] k_x) >> 22, 0, 255)  in 32-bit integers, the horizontal pass first,
+ * its uint8 result the input of the vertical pass.  An axis whose size does not change is not filtered: ksize 0 and null
+ * tables for it, and only for it (CIPS3D_E_BADARG otherwise).
+ *
+ * src [n][C][H][W] uint8, or fp32 in [-1, 1] with src_is_f32 != 0 (quantised on load with cips3d_rgb_to_uint8's arithmetic; no
+ * uint8 copy is written), with its row, channel and image pitch in ELEMENTS (unit pitch in W); dst [n][C][oh][ow] uint8 with
+ * its own three pitches in bytes: a result can land in one cell of a panel block or in a slice of a frame block, and only the
+ * oh x ow bytes of each plane are written.  Dword loads / stores are used where the pointer and the three pitches are
+ * multiples of 4, byte accesses otherwise and at a row's ragged end.
+ *
+ * Routes (cips3d_resample_route: decided on the host from the shape alone, nothing launched):
+ *     FUSED        both axes change and what an output tile of tile_h x tile_w reaches -- at most max_stage_rows input rows, and
+ *                  with their columns, the intermediate rows and the tile's tables at most 160 KB -- is staged in LDS: one
+ *                  launch, the intermediate picture never goes to memory
+ *     TWO_LAUNCH   the rest (strong down-scaling; an axis that does not change): horizontal into `workspace`, vertical from
+ *                  there; the pass of an unchanged axis is skipped, the other one then writes dst itself and no workspace is
+ *                  needed (neither changes: the unfiltered path of the horizontal kernel copies / quantises)
+ * `route`: CIPS3D_RESAMPLE_AUTO, or the shape's own route, or TWO_LAUNCH for a FUSED shape (the same bytes; CIPS3D_E_UNSUPP
+ * for any other request).  `workspace`: cips3d_resample_workspace_bytes(...) bytes (0 unless TWO_LAUNCH), 4-byte aligned,
+ * free again once the stream has passed the call.  Grids never exceed 65535 workgroups: the kernels loop.
+ * cips3d_resample_tile returns the threads per workgroup.  Nothing synchronises.  n C == 0: returns 0, launches nothing.
+ * CIPS3D_E_BADARG, nothing launched: a null required pointer, a size < 1, a row pitch below the row, a negative pitch, a
+ * workspace too small; CIPS3D_E_UNSUPP: n C > INT32_MAX, a misaligned fp32 source or workspace. */
+#define CIPS3D_RESAMPLE_AUTO       0
+#define CIPS3D_RESAMPLE_FUSED      1
+#define CIPS3D_RESAMPLE_TWO_LAUNCH 2
+int cips3d_resample_tile(int* tile_h, int* tile_w, int* max_stage_rows);
+int cips3d_resample_route(int H, int W, int oh, int ow, int ksize_x, int ksize_y);
+int64_t cips3d_resample_workspace_bytes(int n, int C, int H, int W, int oh, int ow, int ksize_x, int ksize_y, int route);
+int cips3d_resample_u8(const void* src, int n, int C, int H, int W, int64_t src_row_pitch, int64_t src_channel_pitch,
+                       int64_t src_image_pitch, uint8_t* dst, int oh, int ow, int64_t dst_row_pitch, int64_t dst_channel_pitch,
+                       int64_t dst_image_pitch, const int32_t* bounds_x, const int32_t* coeffs_x, int ksize_x,
+                       const int32_t* bounds_y, const int32_t* coeffs_y, int ksize_y, int src_is_f32, void* workspace,
+                       int64_t workspace_bytes, int route, void* stream);
 
 #ifdef __cplusplus
 }
