@@ -659,13 +659,14 @@ class NerfRenderFn(Function):
         img_size, n_samples, static = ctx.cfg
         r = ctx.renderer
         _, layer_bias = r._derived_buffers()
+        sig_beta = r.sigmoid_beta.detach() if r.with_sdf else None      # None: raw density
         B, H = cam_poses.shape[0], r.hidden_dim
         if dfeat is None:
             dfeat = torch.zeros(B, H, img_size, img_size, device=cam_poses.device)
         if dthumb is None:
             dthumb = torch.zeros(B, 3, img_size, img_size, device=cam_poses.device)
         if ctx.want_params:
-            dfilm, dcam, pg = hip.nerf_backward(r.network, r.sigmoid_beta.detach() if r.with_sdf else None, cam_poses, focals, near, far, perturb_u, film,
+            dfilm, dcam, pg = hip.nerf_backward(r.network, sig_beta, cam_poses, focals, near, far, perturb_u, film,
                                                 layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(),
                                                 need_params=True, **geo)
             names = [n for n, _ in nerf_named_parameters(r)]
@@ -674,11 +675,11 @@ class NerfRenderFn(Function):
             return (None, dcam, None, None, None, dfilm, None, None, None, None) + grads
         if hip.FUSED_NERF_BACKWARD and hip.nerf_backward_fused_supported(H, r.N_layers_renderer, img_size, n_samples):
             packed, _ = r._derived_buffers()
-            dfilm, dcam = hip.nerf_backward_fused(r.network, r.sigmoid_beta.detach() if r.with_sdf else None, cam_poses, focals, near, far, perturb_u,
+            dfilm, dcam = hip.nerf_backward_fused(r.network, sig_beta, cam_poses, focals, near, far, perturb_u,
                                                   film, layer_bias, packed, r._packed_transposed(), img_size, n_samples,
                                                   static, dfeat, dthumb, fwd=ctx.fwd, **geo)
             ctx.fwd = None
         else:
-            dfilm, dcam = hip.nerf_backward(r.network, r.sigmoid_beta.detach() if r.with_sdf else None, cam_poses, focals, near, far, perturb_u, film,
+            dfilm, dcam = hip.nerf_backward(r.network, sig_beta, cam_poses, focals, near, far, perturb_u, film,
                                             layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(), **geo)
         return (None, dcam, None, None, None, dfilm, None, None, None, None) + (None,) * ctx.n_params

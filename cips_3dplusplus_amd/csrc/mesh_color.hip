@@ -40,8 +40,7 @@ __global__ void __launch_bounds__(MR_THREADS) mc_vertex_kernel(cips3d_mesh_color
       if (!(q.z <= zstar + P.depth_tol)) continue;
       const float* cm = cams + (int64_t)k * MR_CAM_FLOATS;
       float dx = cm[0] - px, dy = cm[1] - py, dz = cm[2] - pz;
-      const float dn = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-12f);
-      dx /= dn; dy /= dn; dz /= dn;
+      normalize3(dx, dy, dz);
       const float c = (nx * dx + ny * dy) + nz * dz;
       if (!(c > 0.f)) continue;
       ++seen;
@@ -83,7 +82,7 @@ __global__ void __launch_bounds__(MR_THREADS) mc_albedo_kernel(const int32_t* __
     const float sh = shade[idx];
     for (int c = 0; c < 3; ++c) {
       uint8_t q = 255;                                // the reference's white background
-      if (hit) q = (uint8_t)floorf(255.f * fminf(fmaxf(sh * (attr[o + c * SS] + 1.f) / 2.f, 0.f), 1.f) + 0.5f);
+      if (hit) q = unit_to_u8(sh * (attr[o + c * SS] + 1.f) / 2.f);
       out[o + c * SS] = q;
     }
   }

@@ -1,9 +1,10 @@
 // What the mesh rasteriser (mesh_raster.hip) shares with the passes that read its workspace (mesh_color.hip): the layout of
-// the workspace, the empty key and the size limits of every entry point.
+// the workspace, the empty key and the size limits of every entry point; and, through shade.h, the shade and its byte.
 #pragma once
 #include <algorithm>
 
 #include "common.h"
+#include "shade.h"
 
 namespace {
 

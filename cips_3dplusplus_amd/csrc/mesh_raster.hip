@@ -16,7 +16,7 @@
 // cross products of the corners RELATIVE TO THE PIXEL CENTRE: the two faces of a shared edge evaluate exactly negated
 // values, so a pixel centre is never lost between them (and is drawn by both only when the value is exactly zero).
 // No LDS, no scratch; the library builds with -ffp-contract=off, so every expression below rounds as written.
-#include "mesh_raster.h"          // the workspace layout, MR_EMPTY, mr_check, mr_grid: shared with mesh_color.hip
+#include "mesh_raster.h"          // the workspace layout, MR_EMPTY, mr_check, mr_grid: shared with mesh_color.hip; shade.h
 
 namespace {
 
@@ -160,12 +160,6 @@ __global__ void __launch_bounds__(MR_THREADS) mr_face_kernel(const int32_t* __re
   }
 }
 
-// F.normalize of a 3-vector (eps 1e-12)
-__device__ __forceinline__ void mr_normalize3(float& x, float& y, float& z) {
-  const float n = fmaxf(sqrtf((x * x + y * y) + z * z), 1e-12f);
-  x /= n; y /= n; z /= n;
-}
-
 __global__ void __launch_bounds__(MR_THREADS) mr_resolve_kernel(cips3d_mesh_resolve_params P, const float* __restrict__ cams,
                                                                 const float4* __restrict__ proj) {
   const int S = P.S, V = P.V;
@@ -209,22 +203,15 @@ __global__ void __launch_bounds__(MR_THREADS) mr_resolve_kernel(cips3d_mesh_reso
               nz = (w0 * n0[2] + w1 * n1[2]) + w2 * n2[2];
         const float px = (w0 * p0[0] + w1 * p1[0]) + w2 * p2[0], py = (w0 * p0[1] + w1 * p1[1]) + w2 * p2[1],
                     pz = (w0 * p0[2] + w1 * p1[2]) + w2 * p2[2];
-        mr_normalize3(nx, ny, nz);
+        normalize3(nx, ny, nz);
         const float* cm = cams + (int64_t)view * MR_CAM_FLOATS;
         float lx = P.light[3 * view] - px, ly = P.light[3 * view + 1] - py, lz = P.light[3 * view + 2] - pz;
         float vx = cm[0] - px, vy = cm[1] - py, vz = cm[2] - pz;
-        mr_normalize3(lx, ly, lz);
-        mr_normalize3(vx, vy, vz);
-        // csrc/nerf_normals.hip's Phong (pytorch3d's, white vertex colour)
-        const float cs = (nx * lx + ny * ly) + nz * lz;
-        const float rx = 2.f * cs * nx - lx, ry = 2.f * cs * ny - ly, rz = 2.f * cs * nz - lz;
-        const float vr = fmaxf((vx * rx + vy * ry) + vz * rz, 0.f);
-        const float spec = cs > 0.f ? powf(vr, P.shininess) : 0.f;
-        sh = (P.ka + P.kd * fmaxf(cs, 0.f)) + P.ks * spec;
+        sh = phong_white(nx, ny, nz, lx, ly, lz, vx, vy, vz, P.ka, P.kd, P.ks, P.shininess);
       }
       if (P.shade) P.shade[idx] = sh;
       if (P.shade_u8) {
-        const uint8_t q = (uint8_t)floorf(255.f * fminf(fmaxf(sh, 0.f), 1.f) + 0.5f);
+        const uint8_t q = unit_to_u8(sh);
         const int64_t o = (int64_t)view * 3 * SS + pix;
         P.shade_u8[o] = q; P.shade_u8[o + SS] = q; P.shade_u8[o + 2 * SS] = q;
       }

@@ -15,12 +15,6 @@
 
 namespace {
 
-// F.normalize of a 3-vector (eps 1e-12): mesh_raster.hip's mr_normalize3
-__device__ __forceinline__ void mt_normalize3(float& x, float& y, float& z) {
-  const float n = fmaxf(sqrtf((x * x + y * y) + z * z), 1e-12f);
-  x /= n; y /= n; z /= n;
-}
-
 // The projection of a point by the derived camera c [MR_CAM_FLOATS] into an S x S frame -> (x_p, y_p, z, 1/z; 1/z = -1: dropped
 // by znear).  This restates the body of mr_vertex_kernel (mesh_raster.hip) expression by expression: calling one shared device
 // function from that kernel changed its instruction schedule, and the rasteriser's code objects are kept as they are.
@@ -140,7 +134,7 @@ __global__ void __launch_bounds__(MR_THREADS) mt_bake_kernel(cips3d_mesh_texture
                   pz = (b0 * p0[2] + b1 * p1[2]) + b2 * p2[2];
       float nx = (b0 * n0[0] + b1 * n1[0]) + b2 * n2[0], ny = (b0 * n0[1] + b1 * n1[1]) + b2 * n2[1],
             nz = (b0 * n0[2] + b1 * n1[2]) + b2 * n2[2];
-      mt_normalize3(nx, ny, nz);
+      normalize3(nx, ny, nz);
       float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
       // from the projection on: cips3d_mesh_vertex_colors' contract, as mc_vertex_kernel (mesh_color.hip) states it
       for (int k = 0; k < P.n_views; ++k) {
@@ -153,8 +147,7 @@ __global__ void __launch_bounds__(MR_THREADS) mt_bake_kernel(cips3d_mesh_texture
         const float zstar = key == MR_EMPTY ? __builtin_inff() : __uint_as_float((unsigned)(key >> 32));
         if (!(q.z <= zstar + P.depth_tol)) continue;
         float dx = cm[0] - px, dy = cm[1] - py, dz = cm[2] - pz;
-        const float dn = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-12f);
-        dx /= dn; dy /= dn; dz /= dn;
+        normalize3(dx, dy, dz);
         const float c = (nx * dx + ny * dy) + nz * dz;
         if (!(c > 0.f)) continue;
         ++seen;
@@ -226,9 +219,9 @@ __global__ void __launch_bounds__(MR_THREADS) mt_frame_kernel(const int32_t* __r
       const float sh = shade[idx];
       const float c0 = mt_bilinear(tex, r0, r1, xa, xb, wx, wy), c1 = mt_bilinear(tex + HW, r0, r1, xa, xb, wx, wy),
                   c2 = mt_bilinear(tex + 2 * HW, r0, r1, xa, xb, wx, wy);
-      q0 = (uint8_t)floorf(255.f * fminf(fmaxf(sh * (c0 + 1.f) / 2.f, 0.f), 1.f) + 0.5f);
-      q1 = (uint8_t)floorf(255.f * fminf(fmaxf(sh * (c1 + 1.f) / 2.f, 0.f), 1.f) + 0.5f);
-      q2 = (uint8_t)floorf(255.f * fminf(fmaxf(sh * (c2 + 1.f) / 2.f, 0.f), 1.f) + 0.5f);
+      q0 = unit_to_u8(sh * (c0 + 1.f) / 2.f);
+      q1 = unit_to_u8(sh * (c1 + 1.f) / 2.f);
+      q2 = unit_to_u8(sh * (c2 + 1.f) / 2.f);
     }
     out[o] = q0; out[o + SS] = q1; out[o + 2 * SS] = q2;
   }

@@ -459,7 +459,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     sdf += b_sigma;
 
     // ---- compositing weight of this sample (nerf_utils.py:264-307); known before the view layer
-    const float delta = (sk < N - 1 ? zsample(sk + 1) - z : 1e10f) * dnorm;
+    const float delta = (sk < N - 1 ? zsample(sk + 1) - z : NERF_DZ_LAST) * dnorm;
     float sigma;
     if (raw_density) {        // with_sdf = False (nerf_utils.py:288-297): softplus of the raw density.  A real (uniform) branch and
       // the hardware exp / log: the library forms held enough temporaries here to spill four registers of the default path
@@ -467,9 +467,9 @@ __global__ void __launch_bounds__(WAVES * 64, 2) nerf_render_kernel(NerfArgs a) 
     } else {
       sigma = nerf_sdf_density(sdf, sig_beta);
     }
-    const float alpha = 1.f - expf(-sigma * delta);
+    const float alpha = nerf_alpha(sigma, delta);
     const float w = live ? alpha * T : 0.f;
-    if (live) T *= (1.f - alpha) + 1e-10f;
+    if (live) T *= nerf_keep(alpha);
 
     STAMP(3);   // sigma head + weight
     // ---- view layer -> features, folded into FA; rgb head partial sums

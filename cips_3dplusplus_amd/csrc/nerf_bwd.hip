@@ -39,10 +39,9 @@ __device__ __forceinline__ RayGeom ray_geom(const cips3d_nerf_bwd_geom& G, int b
   return r;
 }
 
-// Upstreams of the geometry maps of one ray (nerf_utils.py:329-336: xyz = sum_k w_k p_k, mask[0] = w_{N-1}, mask[1] = -|xyz|):
+// Upstreams of the geometry maps of one ray (GeoAdj, nerf_geom.h):
 // m = d loss / d mask[0], (x, y, z) = the effective adjoint of xyz = d_xyz - d_depth * xyz / |xyz| (0 from the depth where
 // |xyz| == 0: torch's subgradient of norm).  d_mask [2,B,R] (needs the forward's xyz [B,3,R]) and d_xyz [B,3,R] may each be NULL.
-struct GeoAdj { float x, y, z, m; };
 __device__ __forceinline__ GeoAdj geo_adjoint(const float* __restrict__ d_mask, const float* __restrict__ d_xyz,
                                               const float* __restrict__ xyz, int B, int R, int b, int ray) {
   GeoAdj a{0.f, 0.f, 0.f, 0.f};
@@ -192,7 +191,8 @@ __global__ void __launch_bounds__(256) dot_kernel(const float* __restrict__ dF, 
 }
 
 // ---------------------------------------------------------------------------------------------- compositing fwd + bwd
-// One thread per ray (nerf_utils.py:264-307).  Writes w, T (scratch), then d(sdf) [B,P] and d(rgb logits) [B,3,P].
+// One thread per ray (nerf_utils.py:264-307; the step and its per-sample adjoint, NerfSampleAdj: nerf_geom.h).  Writes w, T
+// (scratch), then d(sdf) [B,P] and d(rgb logits) [B,3,P].
 // d_mask / d_xyz (either set; wave-uniform): G_k gains <xbar, p_k> + [k == N-1] mbar, p_k the world point the forward composites,
 // and the ray's sum_k w_k, sum_k w_k z_k go to wsum / wzsum [B,R] (the direct path through the points: camera_chain_kernel).
 __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, const float* __restrict__ sdf,
@@ -220,13 +220,13 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
   float* tp = Tbuf + (int64_t)b * P + ray;
   float T = 1.f;
   for (int k = 0; k < N; ++k) {
-    const float delta = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f) * r.dnorm;
+    const float delta = (k < N - 1 ? r.z(k + 1) - r.z(k) : NERF_DZ_LAST) * r.dnorm;
     const float v = sp[(int64_t)k * R];
     const float sigma = raw ? nerf_softplus(v) : nerf_sdf_density(v, beta);
-    const float alpha = 1.f - expf(-sigma * delta);
+    const float alpha = nerf_alpha(sigma, delta);
     tp[(int64_t)k * R] = T;
     wp[(int64_t)k * R] = alpha * T;
-    T *= (1.f - alpha) + 1e-10f;
+    T *= nerf_keep(alpha);
   }
   const float d0 = dthumb[((int64_t)b * 3 + 0) * R + ray], d1 = dthumb[((int64_t)b * 3 + 1) * R + ray],
               d2 = dthumb[((int64_t)b * 3 + 2) * R + ray];
@@ -241,32 +241,25 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
   float ws = 0.f, wz = 0.f;   // sum_k w_k, sum_k w_k z_k
   for (int k = N - 1; k >= 0; --k) {
     const int64_t o = (int64_t)k * R;
-    const float dz = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f);
-    const float delta = dz * r.dnorm;
-    const float sg = raw ? nerf_sigmoid(sp[o]) : nerf_sigmoid(-sp[o] / beta);
-    const float sigma = raw ? nerf_softplus(sp[o]) : sg / beta;
-    const float e = expf(-sigma * delta);
-    const float alpha = 1.f - e;
+    const float dz = k < N - 1 ? r.z(k + 1) - r.z(k) : NERF_DZ_LAST;
+    const NerfSampleAdj a = nerf_sample_adj(raw, beta, sp[o], dz * r.dnorm, cp[o], cp[P + o], cp[2 * P + o]);
     const float Tk = tp[o], wk = wp[o];
-    const float s0 = nerf_sigmoid(cp[o]), s1 = nerf_sigmoid(cp[P + o]), s2 = nerf_sigmoid(cp[2 * P + o]);
-    float Gk = g[(int64_t)b * P + ray + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
+    float Gk = a.G(g[(int64_t)b * P + ray + o], d0, d1, d2);
     if (geo) {
       const float z = r.z(k);
-      const float px = r.ox + r.dx * z, py = r.oy + r.dy * z, pz = r.oz + r.dz * z;
-      Gk += (ga.x * px + ga.y * py) + ga.z * pz;
-      if (k == N - 1) Gk += ga.m;
+      Gk = a.G_geo(Gk, ga, r.ox + r.dx * z, r.oy + r.dy * z, r.oz + r.dz * z, k == N - 1);
       ws += wk;
       wz = fmaf(wk, z, wz);
     }
-    const float dalpha = Tk * Gk - S / ((1.f - alpha) + 1e-10f);
+    const float dalpha = a.dalpha(Tk, Gk, S);
     S = fmaf(wk, Gk, S);
-    const float dsigma = dalpha * delta * e;
-    dn = fmaf(dalpha * sigma * e, dz, dn);
-    dsdf[(int64_t)b * P + ray + o] = raw ? dsigma * sg : dsigma * (-sg * (1.f - sg) / (beta * beta));
-    if (!raw) dbt = fmaf(dsigma, (sg * (1.f - sg) * sp[o] / beta - sg) / (beta * beta), dbt);
-    dcp[o] = 2.f * wk * d0 * s0 * (1.f - s0);
-    dcp[P + o] = 2.f * wk * d1 * s1 * (1.f - s1);
-    dcp[2 * P + o] = 2.f * wk * d2 * s2 * (1.f - s2);
+    const float dsigma = a.dsigma(dalpha);
+    dn = fmaf(a.ddnorm(dalpha), dz, dn);
+    dsdf[(int64_t)b * P + ray + o] = a.dsdf(dsigma);
+    if (!raw) dbt = fmaf(dsigma, a.dbeta(), dbt);
+    dcp[o] = a.drgb(wk, d0, a.s0);
+    dcp[P + o] = a.drgb(wk, d1, a.s1);
+    dcp[2 * P + o] = a.drgb(wk, d2, a.s2);
   }
   ddnorm[(int64_t)b * R + ray] = dn;
   if (dbeta_ray) dbeta_ray[(int64_t)b * R + ray] = dbt;
@@ -279,7 +272,8 @@ __global__ void __launch_bounds__(256) composite_kernel(cips3d_nerf_bwd_geom G, 
 // The same integration with one SAMPLE per thread: 32 rays x N samples per workgroup (N <= 32).  A thread per ray leaves the chip
 // to R*B / 64 waves (128 at 64^2, B = 2: 87 us for 0.4 M points); here the transcendental work and the loads of all samples run
 // side by side and only the products along the ray -- T_k, the suffix sum S_k, the per-ray sums -- are chained, each thread walking
-// the shared per-sample factors in the per-ray loop's own order (the results are the ones composite_kernel produces).
+// the shared per-sample factors (the same NerfSampleAdj) in the per-ray loop's own order: the results are the ones
+// composite_kernel produces.
 // dynamic LDS: 7 * N * 32 floats (the geometry upstreams need no eighth array: the thread that sums w_k z_k has the ray's
 // geometry and rebuilds z_k).
 __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geom G, const float* __restrict__ sdf,
@@ -312,33 +306,24 @@ __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geo
   const bool raw = sigmoid_beta == nullptr;
   const float beta = raw ? 1.f : sigmoid_beta[0];
   const int64_t o = (int64_t)k * R + ray;
-  const float dz = (k < N - 1 ? r.z(k + 1) - r.z(k) : 1e10f);
-  const float delta = dz * r.dnorm;
-  const float v = sdf[(int64_t)b * P + o];
-  const float sg = raw ? nerf_sigmoid(v) : nerf_sigmoid(-v / beta);
-  const float sigma = raw ? nerf_softplus(v) : sg / beta;
-  const float e = expf(-sigma * delta);
-  const float alpha = 1.f - e;
-  const float f = (1.f - alpha) + 1e-10f;
-  F[li] = f;
+  const float dz = k < N - 1 ? r.z(k + 1) - r.z(k) : NERF_DZ_LAST;
+  const float* cp = crgb + (int64_t)b * 3 * P + o;
+  const NerfSampleAdj a = nerf_sample_adj(raw, beta, sdf[(int64_t)b * P + o], dz * r.dnorm, cp[0], cp[P], cp[2 * P]);
+  F[li] = a.keep;
   const float d0 = dthumb[((int64_t)b * 3 + 0) * R + ray], d1 = dthumb[((int64_t)b * 3 + 1) * R + ray],
               d2 = dthumb[((int64_t)b * 3 + 2) * R + ray];
-  const float* cp = crgb + (int64_t)b * 3 * P + o;
-  const float s0 = nerf_sigmoid(cp[0]), s1 = nerf_sigmoid(cp[P]), s2 = nerf_sigmoid(cp[2 * P]);
-  float Gk = g[(int64_t)b * P + o] + 2.f * (d0 * s0 + d1 * s1 + d2 * s2);
+  float Gk = a.G(g[(int64_t)b * P + o], d0, d1, d2);
   const bool geo = d_mask != nullptr || d_xyz != nullptr;
   if (geo) {
     const GeoAdj ga = geo_adjoint(d_mask, d_xyz, xyz, G.B, R, b, ray);
     const float z = r.z(k);
-    const float px = r.ox + r.dx * z, py = r.oy + r.dy * z, pz = r.oz + r.dz * z;
-    Gk += (ga.x * px + ga.y * py) + ga.z * pz;
-    if (k == N - 1) Gk += ga.m;
+    Gk = a.G_geo(Gk, ga, r.ox + r.dx * z, r.oy + r.dy * z, r.oz + r.dz * z, k == N - 1);
   }
   Gl[li] = Gk;
   __syncthreads();
   float T = 1.f;
   for (int j = 0; j < k; ++j) T *= F[j * 32 + lr];
-  const float wk = alpha * T;
+  const float wk = a.alpha * T;
   Wl[li] = wk;
   if (live) {
     Tbuf[(int64_t)b * P + o] = T;
@@ -347,20 +332,20 @@ __global__ void __launch_bounds__(1024) composite_par_kernel(cips3d_nerf_bwd_geo
   __syncthreads();
   float S = 0.f;      // sum_{j>k} w_j G_j
   for (int j = N - 1; j > k; --j) S = fmaf(Wl[j * 32 + lr], Gl[j * 32 + lr], S);
-  const float dalpha = T * Gk - S / f;
-  const float dsigma = dalpha * delta * e;
-  Al[li] = dalpha * sigma * e;
+  const float dalpha = a.dalpha(T, Gk, S);
+  const float dsigma = a.dsigma(dalpha);
+  Al[li] = a.ddnorm(dalpha);
   Zl[li] = dz;
   if (!raw) {
     Dl[li] = dsigma;
-    Cl[li] = (sg * (1.f - sg) * v / beta - sg) / (beta * beta);
+    Cl[li] = a.dbeta();
   }
   if (live) {
-    dsdf[(int64_t)b * P + o] = raw ? dsigma * sg : dsigma * (-sg * (1.f - sg) / (beta * beta));
+    dsdf[(int64_t)b * P + o] = a.dsdf(dsigma);
     float* dcp = dcrgb + (int64_t)b * 3 * P + o;
-    dcp[0] = 2.f * wk * d0 * s0 * (1.f - s0);
-    dcp[P] = 2.f * wk * d1 * s1 * (1.f - s1);
-    dcp[2 * P] = 2.f * wk * d2 * s2 * (1.f - s2);
+    dcp[0] = a.drgb(wk, d0, a.s0);
+    dcp[P] = a.drgb(wk, d1, a.s1);
+    dcp[2 * P] = a.drgb(wk, d2, a.s2);
   }
   __syncthreads();
   if (!live) return;

@@ -16,7 +16,8 @@
 //                       order (1 KiB per wave store, fully coalesced); per point it emits sdf, the rgb logits and, where the
 //                       render composites the view layer's features, g = <d_features[:, ray], feature> (ViewGdot) -- all the
 //                       compositing backward needs.
-//   composite_kernel    (nerf_bwd.hip) volume integration forward + backward per ray -> w, d sdf, d rgb logits, d |rays_d|
+//   composite_kernel    (nerf_bwd.hip; the step: nerf_geom.h) volume integration forward + backward per ray -> w, d sdf, d rgb
+//                       logits, d |rays_d|
 //                       (d_mask / d_xyz set: d loss / d w_k gains the geometry maps' share; per-ray sum w_k, sum w_k z_k)
 //   nerf_bwd_kernel     per 16-point tile, layers in reverse.  Epilogue of layer l (VALU):
 //                           u    = upstream (accumulator of the previous MFMA layer, or the compositing gradient)

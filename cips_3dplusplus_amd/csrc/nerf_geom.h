@@ -1,12 +1,14 @@
-// The per-ray geometry of the NeRF half, stated ONCE (reference: Render.get_rays_in_world / get_z_vals / volume_integration,
-// cips3d/nerf_utils.py:18-121, 264-307): pixel -> camera direction -> world direction, the view direction, |rays_d|, the
+// The per-ray geometry of the NeRF half, stated ONCE (reference: Render.get_rays_in_world / get_z_vals and the densities of
+// volume_integration, cips3d/nerf_utils.py:18-121, 276-297): pixel -> camera direction -> world direction, the view direction, |rays_d|, the
 // torch.linspace(0, 1 - 1/N, N) constants, the un-perturbed depth of a sample and its offset-sampled form, the sigmoid and the
 // SDF density.  Every kernel that recomputes a ray instead of reading it takes these expressions from here -- the render kernel
 // (nerf.hip), both backwards (nerf_bwd.hip, nerf_bwd_fused.hip), the SDF gradient (nerf_sdf_grad.hip), the normals
 // (nerf_normals.hip) and the stand-alone Render.* ops (render_ops.hip) -- because they must agree BIT FOR BIT: the fused backward
 // refills the forward's stash, the materialised one recomposites with the forward's delta, the normals weight samples with the
-// render kernel's z, and the stand-alone ops are what the fused kernel does in registers.  fp32, contraction off, the
-// association written out: change an expression here and it changes everywhere at once.
+// render kernel's z, and the stand-alone ops are what the fused kernel does in registers.  So must what they do with a sample
+// once they have its density (nerf_utils.py:264-307; at the end of this file): the compositing step, and its per-sample adjoint
+// for the two compositing kernels of the backward.  fp32, contraction off, the association written out: change an expression
+// here and it changes everywhere at once.
 #pragma once
 #include "common.h"
 
@@ -110,6 +112,52 @@ __device__ __forceinline__ RayGeom ray_geom(const float* cam_poses, const float*
   r.N = N;
   r.t_end = t_end; r.t_step = t_step;
   return r;
+}
+
+// ---- Compositing.  dz_k = z_{k+1} - z_k, delta_k = dz_k |rays_d|, e_k = exp(-sigma_k delta_k), alpha_k = 1 - e_k,
+// f_k = (1 - alpha_k) + 1e-10, T_k = prod_{j<k} f_j, w_k = alpha_k T_k.  Helpers take loaded values and the density sigma (which
+// softplus a raw density goes through is the call site's choice); the products and sums along a ray stay with each kernel, whose
+// order they are.  dz_k of the last sample is NERF_DZ_LAST, scaled by |rays_d| like every other: a call site writes
+// k < N - 1 ? z_{k+1} - z_k : NERF_DZ_LAST  around its own loads, so that z_{k+1} is read only where there is one.
+constexpr float NERF_DZ_LAST = 1e10f;
+__device__ __forceinline__ float nerf_atten(float sigma, float delta) { return expf(-sigma * delta); }               // e_k
+__device__ __forceinline__ float nerf_alpha(float sigma, float delta) { return 1.f - nerf_atten(sigma, delta); }
+__device__ __forceinline__ float nerf_keep(float alpha) { return (1.f - alpha) + 1e-10f; }                           // f_k
+
+// Upstreams of a ray's geometry maps (nerf_utils.py:329-336): m = d loss / d mask[0], (x, y, z) = the effective adjoint of xyz
+struct GeoAdj { float x, y, z, m; };
+
+// One sample of the compositing backward (nerf_bwd.hip): what the forward made of it and every per-sample factor of the adjoint,
+// from G_k = d loss / d w_k and S_k = sum_{j>k} w_j G_j.  raw (with_sdf = False, nerf_utils.py:288-297): v is the raw density,
+// sigma = softplus(v), d sigma / d v = sg = sigmoid(v); else v is the sdf, sg = sigmoid(-v / beta), sigma = sg / beta.
+struct NerfSampleAdj {
+  bool raw;
+  float beta, v, delta, sg, sigma, e, alpha, keep, s0, s1, s2;   // s*: the rgb sigmoids
+  // g = <d feature map, feature_k>, d* = d thumbnail (rgb_map = -1 + 2 sum_k w_k s_k)
+  __device__ __forceinline__ float G(float g, float d0, float d1, float d2) const { return g + 2.f * (d0 * s0 + d1 * s1 + d2 * s2); }
+  // the geometry upstreams' share of G_k: <xbar, p_k> + [k == N-1] mbar, p_k the world point the forward composites
+  __device__ static __forceinline__ float G_geo(float Gk, const GeoAdj& ga, float px, float py, float pz, bool last) {
+    Gk += (ga.x * px + ga.y * py) + ga.z * pz;
+    return last ? Gk + ga.m : Gk;
+  }
+  __device__ __forceinline__ float dalpha(float Tk, float Gk, float Sk) const { return Tk * Gk - Sk / keep; }
+  __device__ __forceinline__ float dsigma(float dalpha) const { return dalpha * delta * e; }
+  __device__ __forceinline__ float ddnorm(float dalpha) const { return dalpha * sigma * e; }   // d |rays_d| = sum_k ddnorm_k dz_k
+  __device__ __forceinline__ float dsdf(float dsigma) const { return raw ? dsigma * sg : dsigma * (-sg * (1.f - sg) / (beta * beta)); }
+  // d sigma / d beta (with_sdf only): d sigmoid_beta = sum_k dsigma_k dbeta_k
+  __device__ __forceinline__ float dbeta() const { return (sg * (1.f - sg) * v / beta - sg) / (beta * beta); }
+  __device__ static __forceinline__ float drgb(float wk, float d, float s) { return 2.f * wk * d * s * (1.f - s); }   // d rgb logit
+};
+__device__ __forceinline__ NerfSampleAdj nerf_sample_adj(bool raw, float beta, float v, float delta, float c0, float c1, float c2) {
+  NerfSampleAdj a;
+  a.raw = raw; a.beta = beta; a.v = v; a.delta = delta;
+  a.sg = raw ? nerf_sigmoid(v) : nerf_sigmoid(-v / beta);
+  a.sigma = raw ? nerf_softplus(v) : a.sg / beta;
+  a.e = nerf_atten(a.sigma, a.delta);
+  a.alpha = 1.f - a.e;
+  a.keep = nerf_keep(a.alpha);
+  a.s0 = nerf_sigmoid(c0); a.s1 = nerf_sigmoid(c1); a.s2 = nerf_sigmoid(c2);
+  return a;
 }
 
 }  // namespace

@@ -1,10 +1,10 @@
 // Composited surface normals and the Phong-shaded geometry frame of a rendered view (cips3d_nerf_normals).
 //
 //   normal_raw[b,:,r] = sum_i w_i grad[b,r,i,:]     w = the compositing weights of nerf_utils.py:276-286 (the render
-//                                                   kernel's rays and depths: csrc/nerf_geom.h), grad = d sdf / d pts of
-//                                                   csrc/nerf_sdf_grad.hip
+//                                                   kernel's rays, depths and compositing step: csrc/nerf_geom.h),
+//                                                   grad = d sdf / d pts of csrc/nerf_sdf_grad.hip
 //   normal = normal_raw / max(|normal_raw|, 1e-12)  (F.normalize)
-//   shade  = pytorch3d's Phong for a white vertex colour at p = xyz[b,:,r], seen from `eye`, lit from `light`
+//   shade  = the mesh frames' Phong (csrc/shade.h) at p = xyz[b,:,r], seen from `eye`, lit from `light`
 //
 // sdf and grad have the sample index innermost, so lanes span SAMPLES: a ray is a segment of W = 2^k >= N lanes (64 / W rays
 // per wave), or, for N > 64, one wave walking chunks of 64 samples with the transmittance carried across.  The transmittance
@@ -14,6 +14,7 @@
 // fixed by N alone: no atomics, bit-reproducible, independent of the grid.  Accurate expf / powf throughout.
 #include "common.h"
 #include "nerf_geom.h"
+#include "shade.h"
 
 namespace {
 
@@ -25,12 +26,6 @@ struct NormalsArgs {
   int R;
   float t_end, t_step;       // nerf_linspace_consts (nerf_geom.h)
 };
-
-// F.normalize of a 3-vector (eps 1e-12)
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-  const float n = fmaxf(sqrtf((x * x + y * y) + z * z), 1e-12f);
-  x /= n; y /= n; z /= n;
-}
 
 template <int W, bool XG>
 __global__ void __launch_bounds__(NRM_WAVES * 64) nerf_normals_kernel(NormalsArgs a) {
@@ -78,10 +73,9 @@ __global__ void __launch_bounds__(NRM_WAVES * 64) nerf_normals_kernel(NormalsArg
         const float sdf = P.sdf[pt];
         const float* gp = P.grad + pt * 3;
         gx = gp[0]; gy = gp[1]; gz = gp[2];
-        const float delta = (sk < N - 1 ? zsample(sk + 1) - zsample(sk) : 1e10f) * dnorm;
-        const float sigma = nerf_sdf_density(sdf, beta);
-        alpha = 1.f - expf(-sigma * delta);
-        f = (1.f - alpha) + 1e-10f;
+        const float delta = (sk < N - 1 ? zsample(sk + 1) - zsample(sk) : NERF_DZ_LAST) * dnorm;
+        alpha = nerf_alpha(nerf_sdf_density(sdf, beta), delta);
+        f = nerf_keep(alpha);
       }
       // shifted exclusive prefix product over the segment
       float x = __shfl_up(f, 1, W);
@@ -111,16 +105,10 @@ __global__ void __launch_bounds__(NRM_WAVES * 64) nerf_normals_kernel(NormalsArg
       const float px = P.xyz[o3], py = P.xyz[o3 + R], pz = P.xyz[o3 + 2 * (int64_t)R];
       float lx = P.light[3 * b] - px, ly = P.light[3 * b + 1] - py, lz = P.light[3 * b + 2] - pz;
       float vx = P.eye[3 * b] - px, vy = P.eye[3 * b + 1] - py, vz = P.eye[3 * b + 2] - pz;
-      normalize3(lx, ly, lz);
-      normalize3(vx, vy, vz);
-      const float cs = (nx * lx + ny * ly) + nz * lz;
-      const float rx = 2.f * cs * nx - lx, ry = 2.f * cs * ny - ly, rz = 2.f * cs * nz - lz;
-      const float vr = fmaxf((vx * rx + vy * ry) + vz * rz, 0.f);
-      const float spec = cs > 0.f ? powf(vr, P.shininess) : 0.f;
-      const float sh = (P.ka + P.kd * fmaxf(cs, 0.f)) + P.ks * spec;
+      const float sh = phong_white(nx, ny, nz, lx, ly, lz, vx, vy, vz, P.ka, P.kd, P.ks, P.shininess);
       if (P.shade) P.shade[brc] = sh;
       if (P.shade_u8) {
-        const uint8_t q = (uint8_t)floorf(255.f * fminf(fmaxf(sh, 0.f), 1.f) + 0.5f);
+        const uint8_t q = unit_to_u8(sh);
         P.shade_u8[o3] = q; P.shade_u8[o3 + R] = q; P.shade_u8[o3 + 2 * (int64_t)R] = q;
       }
     }

@@ -105,11 +105,11 @@ __global__ void __launch_bounds__(256) integrate_kernel(const float* __restrict_
   const float dnorm = nerf_norm3(rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]);
   // alpha_k for this lane's samples, then the transmittance scan by lane 0 (N is small: 24 .. 128)
   for (int k = lane; k < N; k += 64) {
-    const float delta = (k < N - 1 ? z[r * N + k + 1] - z[r * N + k] : 1e10f) * dnorm;
+    const float delta = (k < N - 1 ? z[r * N + k + 1] - z[r * N + k] : NERF_DZ_LAST) * dnorm;
     const float v = sdf[r * N + k];
     // with_sdf: the SDF density; else F.softplus of the raw output (nerf_geom.h)
     const float sigma = raw_density ? nerf_softplus(v) : nerf_sdf_density(v, beta);
-    s_w[wv][k] = 1.f - expf(-sigma * delta);
+    s_w[wv][k] = nerf_alpha(sigma, delta);
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS writes are done
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(256) integrate_kernel(const float* __restrict_
       const float w = alpha * T;
       s_w[wv][k] = w;
       if (k < N - 1) wsum += w;
-      T *= (1.f - alpha) + 1e-10f;
+      T *= nerf_keep(alpha);
     }
     if (flags & CIPS3D_VI_FORCE_BACKGROUND) s_w[wv][N - 1] = 1.f - wsum;   // nerf_utils.py:309-310
   }

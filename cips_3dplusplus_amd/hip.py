@@ -1255,6 +1255,20 @@ def _geo_upstreams(d_mask, d_xyz, xyz, B, R):
     return dm, dx, None if dm is None else xyz.detach().float().reshape(B, 3, R).contiguous()
 
 
+def _nerf_bwd_geom(cam_poses, focals, near, far, perturb_u, img_size, n_samples, static_viewdirs, into=None):
+    """The NerfBwdGeom (cips3d_nerf_bwd_geom) of both NeRF backwards, a new one or `into` filled: returns (geom, the tensors it
+    points into, which the caller holds until its calls are enqueued)."""
+    geom = _lib.NerfBwdGeom() if into is None else into
+    B, R = cam_poses.shape[0], img_size * img_size
+    keep = [cam_poses.float().contiguous(), focals.float().reshape(B).contiguous(), near.float().reshape(B).contiguous(),
+            far.float().reshape(B).contiguous(),
+            None if perturb_u is None else perturb_u.float().reshape(B, R).contiguous()]
+    geom.cam_poses, geom.focals, geom.near_, geom.far_ = (dev_ptr(t) for t in keep[:4])
+    geom.perturb_u = dev_ptr(keep[4], "perturb_u", True)
+    geom.B, geom.img_size, geom.n_samples, geom.static_viewdirs = B, img_size, n_samples, int(bool(static_viewdirs))
+    return geom, keep
+
+
 def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, film, layer_bias, img_size, n_samples,
                   static_viewdirs, d_features, d_thumb, need_params=False, d_mask=None, d_xyz=None, xyz=None):
     """The materialised NeRF backward (see csrc/nerf_bwd.hip): returns (dfilm [B,L,2,H], dcam [B,3,4]) -- and, with
@@ -1275,13 +1289,7 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     R = img_size * img_size
     P = R * n_samples
     fb = L * 2 * H
-    geom = _lib.NerfBwdGeom()
-    keep = [cam_poses.float().contiguous(), focals.float().reshape(B).contiguous(), near.float().reshape(B).contiguous(),
-            far.float().reshape(B).contiguous(),
-            None if perturb_u is None else perturb_u.float().reshape(B, R).contiguous()]
-    geom.cam_poses, geom.focals, geom.near_, geom.far_ = (dev_ptr(t) for t in keep[:4])
-    geom.perturb_u = dev_ptr(keep[4], "perturb_u", True)
-    geom.B, geom.img_size, geom.n_samples, geom.static_viewdirs = B, img_size, n_samples, int(bool(static_viewdirs))
+    geom, keep = _nerf_bwd_geom(cam_poses, focals, near, far, perturb_u, img_size, n_samples, static_viewdirs)
     gp = C.byref(geom)
     new = lambda *shape: torch.empty(*shape, device=dev)
     film = film.contiguous()
@@ -1449,14 +1457,8 @@ def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb
     B, H, D = cam_poses.shape[0], net.W, net.D
     L, R = D + 1, img_size * img_size
     p = _lib.NerfBwdFusedParams()
-    keep = [cam_poses.float().contiguous(), focals.float().reshape(B).contiguous(), near.float().reshape(B).contiguous(),
-            far.float().reshape(B).contiguous(),
-            None if perturb_u is None else perturb_u.float().reshape(B, R).contiguous(),
-            film.float().contiguous(), d_features.float().contiguous(), d_thumb.float().contiguous()]
-    g = p.geom
-    g.cam_poses, g.focals, g.near_, g.far_ = (dev_ptr(t) for t in keep[:4])
-    g.perturb_u = dev_ptr(keep[4], "perturb_u", True)
-    g.B, g.img_size, g.n_samples, g.static_viewdirs = B, img_size, n_samples, int(bool(static_viewdirs))
+    _, keep = _nerf_bwd_geom(cam_poses, focals, near, far, perturb_u, img_size, n_samples, static_viewdirs, into=p.geom)
+    keep += [film.float().contiguous(), d_features.float().contiguous(), d_thumb.float().contiguous()]
     if fwd is not None:
         if stash is not None:
             raise ValueError("stash= is the recompute route's buffer: with fwd= the forward's own stash is read")
