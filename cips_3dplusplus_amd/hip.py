@@ -996,7 +996,8 @@ def modconv3x3_supported(Cin, Cout, H, W, up):
     return bool(_lib.load().cips3d_modconv3x3_supported(Cin, Cout, H, W, int(bool(up))))
 
 
-def modconv3x3(x, wm_packed, Cout, up=False, fir=None, epilogue=0, noise=None, noise_w=None, bias=None, split=False, x_amax=None):
+def modconv3x3(x, wm_packed, Cout, up=False, fir=None, epilogue=0, noise=None, noise_w=None, bias=None, split=False, x_amax=None,
+               out=None):
     """3x3 modulated conv on the LDS-tiled MFMA kernel (csrc/conv3x3.hip).  x [B,Cin,H,W]; wm_packed from
     modulate_weights(..., ksq=9, packed=True, flip=up); up: conv_transpose2d(stride 2) + Blur(fir) fused -> [B,Cout,2H,2W].
     split: fp32-equivalent split-fp16 products (wm_packed from modulate_weights(..., split=True) as well); x is split as x * 2^-e
@@ -1004,7 +1005,8 @@ def modconv3x3(x, wm_packed, Cout, up=False, fir=None, epilogue=0, noise=None, n
     lib = _lib.load()
     B, Cin, H, W = x.shape
     OH, OW = (2 * H, 2 * W) if up else (H, W)
-    out = torch.empty(B, Cout, OH, OW, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B, Cout, OH, OW, device=x.device, dtype=torch.float32)
     nb = 0
     if noise is not None:
         if noise.shape[0] not in (1, B) or tuple(noise.shape[-2:]) != (OH, OW):
