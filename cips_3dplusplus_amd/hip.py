@@ -808,32 +808,43 @@ def modconv_kxk(x, wm, Cout, k, transpose2=False):
     return out
 
 
+def _given(t, shape, dtype, device, make):
+    """the caller's output tensor `t` after a check of its shape and type, or a fresh make(shape)"""
+    if t is None:
+        return make(*shape, device=device, dtype=dtype)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device.type != torch.device(device).type:
+        raise RuntimeError(f"an output tensor must be a contiguous {dtype} tensor of shape {tuple(shape)} on the device")
+    return t
+
+
 def planes_supported(Cin, Cout, HW):
     return bool(_lib.load().cips3d_planes_supported(Cin, Cout, HW))
 
 
-def to_planes(x, ranged=True):
+def to_planes(x, ranged=True, out=None, out_exp=None, out_pmax=None):
     """fp32 [B,C,H,W] -> split-fp16 planes (torch.float16 tensor [B, C/8, 2, H*W, 8]: hi plane, lo plane) of x * 2^-e, e one
     power of two per sample that puts max|x| into [2^14, 2^15) (cips3d_range).  The exponents ([B, blocks of 128 pixels] int32:
     the format allows one per pixel block, this conversion writes the sample's everywhere) travel as an attribute of the
-    result (`.cips3d_exp`); ranged=False stores x itself (e = 0)."""
+    result (`.cips3d_exp`); ranged=False stores x itself (e = 0).  out / out_exp / out_pmax: caller-supplied tensors of those
+    shapes to write instead of fresh ones."""
     lib = _lib.load()
     B, Cc, H, W = x.shape
-    p = torch.empty(B, Cc // 8, 2, H * W, 8, device=x.device, dtype=torch.float16)
+    p = _given(out, (B, Cc // 8, 2, H * W, 8), torch.float16, x.device, torch.empty)
     amax = amax_of(x) if ranged else None
     nblk = (H * W + _lib.PLANES_EXP_BLOCK - 1) // _lib.PLANES_EXP_BLOCK
-    exps = torch.zeros(B, nblk, device=x.device, dtype=torch.int32) if ranged else None
-    pmax = torch.zeros(B, (H * W + 63) // 64, Cc // 16, device=x.device) if (ranged and Cc % 16 == 0) else None
+    exps = _given(out_exp, (B, nblk), torch.int32, x.device, torch.zeros) if ranged else None
+    pmax = _given(out_pmax, (B, (H * W + 63) // 64, Cc // 16), torch.float32, x.device, torch.zeros) \
+        if (ranged and Cc % 16 == 0) else None
     check(lib.cips3d_to_planes(dev_ptr(x, "x"), p.data_ptr(), B, Cc, H * W, dev_ptr(amax, "amax", True),
                                exps.data_ptr() if ranged else None, dev_ptr(pmax, "pmax", True), stream_ptr()), "cips3d_to_planes")
     p.cips3d_exp, p.cips3d_pmax = exps, pmax
     return p
 
 
-def from_planes(p, H, W):
+def from_planes(p, H, W, out=None):
     lib = _lib.load()
     B, C8 = p.shape[0], p.shape[1]
-    x = torch.empty(B, C8 * 8, H, W, device=p.device, dtype=torch.float32)
+    x = _given(out, (B, C8 * 8, H, W), torch.float32, p.device, torch.empty)
     exps = getattr(p, "cips3d_exp", None)
     check(lib.cips3d_from_planes(dev_ptr(p, "planes", dtype=torch.float16), dev_ptr(x), B, C8 * 8, H * W,
                                  exps.data_ptr() if exps is not None else None, stream_ptr()), "cips3d_from_planes")
@@ -841,7 +852,8 @@ def from_planes(p, H, W):
 
 
 def modconv1x1_planes(xp, wm_split, Cout, HW, out_format="planes", epilogue=0, noise=None, noise_w=None, bias=None,
-                      rgb_w=None, rgb_part=None, demodulated=True, lconst=None, ride=None, half_chip=False):
+                      rgb_w=None, rgb_part=None, demodulated=True, lconst=None, ride=None, half_chip=False, out=None, out_exp=None,
+                      out_pmax=None, out_amax=None):
     """1x1 modulated conv on split-fp16 planes (csrc/chain.hip).  xp from to_planes / a previous call (its exponents are read
     from its attribute; a planes output carries its own); wm_split from
     modulate_weights(..., packed=True, split=True).  out_format: "planes" | "fp32" | "bf16" ([B,Cout,HW]).
@@ -850,15 +862,17 @@ def modconv1x1_planes(xp, wm_split, Cout, HW, out_format="planes", epilogue=0, n
     ride: a ToRGB fold carried by this launch (cips3d_reduce_job; range-tracked inputs only) -- dict(part [n_slots, Br, 3, HWr],
     biases [list of [3]], skip [Br, 3, HWr] or None, out [Br, 3, HWr]): out = skip + sum of the slots + sum of the biases, the
     arithmetic and order of torgb_reduce.
-    half_chip: cips3d_range.half_chip (another view's launches are in flight: 128 x 128 tiles on half the CUs; same results)."""
+    half_chip: cips3d_range.half_chip (another view's launches are in flight: 128 x 128 tiles on half the CUs; same results).
+    out / out_exp / out_pmax / out_amax: caller-supplied tensors (the output; the exponents and patch maxima of a range-tracked
+    planes output; the amax array, zeroed, that a range-tracked fp32 / bf16 output raises) to write instead of fresh ones."""
     lib = _lib.load()
     B, Cin = xp.shape[0], xp.shape[1] * 8
     dev = xp.device
     fmt = {"fp32": 0, "planes": 1, "bf16": 2}[out_format]
     if fmt == 1:
-        out = torch.empty(B, Cout // 8, 2, HW, 8, device=dev, dtype=torch.float16)
+        out = _given(out, (B, Cout // 8, 2, HW, 8), torch.float16, dev, torch.empty)
     else:
-        out = torch.empty(B, Cout, HW, device=dev, dtype=torch.bfloat16 if fmt == 2 else torch.float32)
+        out = _given(out, (B, Cout, HW), torch.bfloat16 if fmt == 2 else torch.float32, dev, torch.empty)
     nb = HW if (noise is not None and noise.shape[0] == B and B > 1) else 0
     x_exp, x_pmax = getattr(xp, "cips3d_exp", None), getattr(xp, "cips3d_pmax", None)
     ranged = x_exp is not None
@@ -872,10 +886,10 @@ def modconv1x1_planes(xp, wm_split, Cout, HW, out_format="planes", epilogue=0, n
             else:
                 lconst = range_consts(B, torch.zeros(1, device=dev), None, Cin ** 0.5)
                 lconst[:, 1] /= 2.0 ** 0.5      # no activation: |out| <= sqrt(Cin) max|x|
-        out_amax = new_amax(B, dev) if fmt != 1 else None
+        out_amax = _given(out_amax, (B, amax_floats()), torch.float32, dev, torch.zeros) if fmt != 1 else None
         nblk = (HW + _lib.PLANES_EXP_BLOCK - 1) // _lib.PLANES_EXP_BLOCK
-        out_exp = torch.zeros(B, nblk, device=dev, dtype=torch.int32) if fmt == 1 else None
-        out_pmax = torch.zeros(B, (HW + 63) // 64, Cout // 16, device=dev) if fmt == 1 else None
+        out_exp = _given(out_exp, (B, nblk), torch.int32, dev, torch.zeros) if fmt == 1 else None
+        out_pmax = _given(out_pmax, (B, (HW + 63) // 64, Cout // 16), torch.float32, dev, torch.zeros) if fmt == 1 else None
         # (x_pmax None: the kernel bounds max|in| by what the input's exponent encodes -- looser, still rigorous)
         rg, _keep = _range(x_exp=x_exp, x_pmax=x_pmax if fmt == 1 else None, lconst=lconst if fmt == 1 else None,
                            out_amax=out_amax, out_exp=out_exp, out_pmax=out_pmax)
@@ -909,26 +923,26 @@ def modconv1x1_planes(xp, wm_split, Cout, HW, out_format="planes", epilogue=0, n
     return out
 
 
-def to_planes16(x):
+def to_planes16(x, out=None):
     """fp32 [B,C,H,W] -> planes16 (torch.bfloat16 tensor [B, C/8, H*W, 8]; round to nearest even)."""
     lib = _lib.load()
     B, Cc, H, W = x.shape
-    p = torch.empty(B, Cc // 8, H * W, 8, device=x.device, dtype=torch.bfloat16)
+    p = _given(out, (B, Cc // 8, H * W, 8), torch.bfloat16, x.device, torch.empty)
     check(lib.cips3d_to_planes16(dev_ptr(x, "x"), p.data_ptr(), B, Cc, H * W, stream_ptr()), "cips3d_to_planes16")
     return p
 
 
-def from_planes16(p, H, W):
+def from_planes16(p, H, W, out=None):
     lib = _lib.load()
     B, C8 = p.shape[0], p.shape[1]
-    x = torch.empty(B, C8 * 8, H, W, device=p.device, dtype=torch.float32)
+    x = _given(out, (B, C8 * 8, H, W), torch.float32, p.device, torch.empty)
     check(lib.cips3d_from_planes16(dev_ptr(p, "planes16", dtype=torch.bfloat16), dev_ptr(x), B, C8 * 8, H * W, stream_ptr()),
           "cips3d_from_planes16")
     return x
 
 
 def modconv1x1_planes16(xp, wm_bf16, Cout, HW, out_format="planes16", epilogue=0, noise=None, noise_w=None, bias=None,
-                        rgb_w=None, rgb_part=None):
+                        rgb_w=None, rgb_part=None, out=None):
     """1x1 modulated conv of the bf16 decoder mode on planes16 (csrc/chain.hip, NP = 1).  xp from to_planes16 / a previous
     call; wm_bf16 from modulate_weights(..., packed=True, bf16=True).  out_format: "planes16" | "fp32" | "bf16" ([B,Cout,HW]).
     Returns (out, number of rgb_part row-block slots written)."""
@@ -936,9 +950,9 @@ def modconv1x1_planes16(xp, wm_bf16, Cout, HW, out_format="planes16", epilogue=0
     B, Cin = xp.shape[0], xp.shape[1] * 8
     fmt = {"fp32": 0, "bf16": 2, "planes16": 3}[out_format]
     if fmt == 3:
-        out = torch.empty(B, Cout // 8, HW, 8, device=xp.device, dtype=torch.bfloat16)
+        out = _given(out, (B, Cout // 8, HW, 8), torch.bfloat16, xp.device, torch.empty)
     else:
-        out = torch.empty(B, Cout, HW, device=xp.device, dtype=torch.bfloat16 if fmt == 2 else torch.float32)
+        out = _given(out, (B, Cout, HW), torch.bfloat16 if fmt == 2 else torch.float32, xp.device, torch.empty)
     nb = HW if (noise is not None and noise.shape[0] == B and B > 1) else 0
     nblk = C.c_int(0)
     check(lib.cips3d_modconv1x1_planes16(dev_ptr(xp, "x_planes16", dtype=torch.bfloat16), dev_ptr(wm_bf16, "wm"), out.data_ptr(),
