@@ -87,17 +87,49 @@ struct ChainArgs {
   const int* x_exp; int x_exp_const; const float* x_pmax; float x_max_const; const float* lconst; float* out_amax; int* out_exp;
   float* out_pmax;
   cips3d_reduce_job ride;   // part == NULL: none.  A ToRGB fold this launch carries (cips3d_range::ride)
+  // What does not depend on the workgroup, worked out once by the launcher (chain_geometry) instead of by every wave of every
+  // launch: byte strides of one sample of x, of the weights and of the output, of one 16-row tile of packed weights, and the
+  // block counts of the side arrays.  A wave's addresses are then one 64-bit base per tensor plus 32-bit offsets.
+  int64_t x_bstride, w_bstride, out_bstride;
+  unsigned w_tile_stride;   // bytes of the (Cin / 32) * NP pieces of one 16-row tile
+  int nblk, n_half;         // ceil(HW / 128) exponent blocks, ceil(HW / 64) patch columns
 };
 
-
+// What a launch is compiled for (the FEAT template argument of chain_gemm_kernel; the table of instantiations is chain_forms
+// below).  One body with every exit, the fold, the range tracking and the riding fold as run-time branches was 169 basic blocks
+// and ~850 scalar instructions per wave around 173 MFMAs; a form carries only what its launches do.
+enum : int {
+  CF_EPI = 1,       // NoiseInjection + bias + leaky ReLU (epilogue 1); bias is there
+  CF_NOISE = 2,     // ... with a noise map and its weight (both pointers given)
+  CF_FOLD = 4,      // the ToRGB that follows is folded: rgb_w / rgb_part given
+  CF_RANGED = 8,    // the range pointers are looked at.  Planes out: lconst / out_exp are there and the exponent is tracked
+  CF_RIDE = 16,     // the grid has the extra row of workgroups of a riding ToRGB fold
+  CF_GENERIC = 128  // everything above (and the exit) decided at run time from ChainArgs, as the one body used to
+};
 
 // NP = planes per operand: 2 = split-fp16 (hi, lo; three fp16 MFMAs per tile and k-block), 1 = bf16 (one bf16 MFMA)
-template <int WM, int WGM, int WGN, int BK, int NS, int NP = 2>
+// FMT: the exit (ChainArgs.out_fmt) and FEAT: CF_* bits, both fixed at compile time -- or FMT = -1, FEAT = CF_GENERIC: read from
+// ChainArgs at run time.  The arithmetic, the loads, the stores and their order are the same in every form.
+template <int WM, int WGM, int WGN, int BK, int NS, int NP, int FMT, int FEAT>
 __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a) {
 #ifdef CIPS3D_CHAIN_STAMPS
   unsigned long long ts_[6];
   CSTAMP(0);
 #endif
+  constexpr bool GEN = (FEAT & CF_GENERIC) != 0;
+  static_assert(GEN == (FMT < 0), "a generic form reads its exit at run time too");
+  static_assert(GEN || ((NP == 2 || FMT != 1) && (NP == 1 || FMT != 3) && (NP == 2 || !(FEAT & (CF_RANGED | CF_RIDE))) &&
+                        (!(FEAT & CF_NOISE) || (FEAT & CF_EPI))), "no such form");
+  const int out_fmt = GEN ? a.out_fmt : FMT;
+  const bool epi = GEN ? a.epilogue == 1 : (FEAT & CF_EPI) != 0;
+  const bool noisy = GEN ? (a.noise && a.noise_w) : (FEAT & CF_NOISE) != 0;       // (looked at under epi only)
+  const bool fold = GEN ? a.rgb_part != nullptr : (FEAT & CF_FOLD) != 0;
+  constexpr bool RANGED = GEN || (FEAT & CF_RANGED) != 0;
+  // the range pointers of this form: constant NULLs where the form (or its exit) has no use for them
+  const int* const x_exp = (RANGED && NP == 2) ? a.x_exp : nullptr;
+  const float* const x_pmax = (RANGED && NP == 2 && (GEN || FMT == 1)) ? a.x_pmax : nullptr;
+  float* const out_pmax = (RANGED && (GEN || FMT == 1)) ? a.out_pmax : nullptr;
+  float* const out_amax = (RANGED && (GEN || FMT != 1)) ? a.out_amax : nullptr;
   constexpr int NW = WGM * WGN;
   constexpr int BM = 16 * WM * WGM, BN = 64 * WGN;
   constexpr int A_STAGE = BM * BK * NP / 2, B_STAGE = BK * BN * NP / 2, STAGE = A_STAGE + B_STAGE;   // floats (NP 2-byte planes)
@@ -119,8 +151,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   // grid of a launch that leaves CUs free (the 512 -> 256 exit of the 64^2 run: 128 tiles).  As in torgb_reduce_kernel a float4
   // position is shared by four slot groups (group g adds slots g, g + 4, ... in that order, absent ones of a batch of four as
   // zeros; then the groups 0 .. 3, the biases, the skip): here the groups are the lane quarters of a wave, 16 positions per wave.
-  if constexpr (NP == 2) {
-    if (a.ride.part && (int)blockIdx.y == a.Cout / BM) {
+  if constexpr (NP == 2 && (GEN || (FEAT & CF_RIDE) != 0)) {
+    if ((!GEN || a.ride.part) && (int)blockIdx.y == a.Cout / BM) {
       constexpr int RIDE_K = 12;                 // loads per lane: n_slots <= 4 * RIDE_K
       const int64_t wv = ((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * NW + wave;
       const int64_t ride_i = wv * 16 + col;
@@ -171,38 +203,61 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   // separate __shared__ array moved the ring off LDS offset 0 and rounded the allocation up past 96 KB: every layer of the
   // run was 2.3 us, 20 %, slower for it.)
   float* s_part = lds + (nstage % NS) * STAGE;
-  const _Float16* xb = a.x + (int64_t)b * K * HW * NP;           // (Cin/8) * NP planes * HW * 8 two-byte elements
-  const float* ab = a.wmp + (int64_t)b * a.Cout * K * NP / 2;   // 2-byte elements, NP planes
-
-  auto stage_load = [&](int st) {
-    float* dstA = lds + (st % NS) * STAGE;
-    float* dstB = dstA + A_STAGE;
-    const int k0 = st * BK;
+  // The pieces this wave moves in EVERY stage are the same ones, a stage further along K: piece j * NW + wave of the stage is a
+  // 1 KB run of packed weights (j < A_PIECES / NW) or 64 pixels of one plane row of x.  Their addresses are worked out once, here:
+  // a uniform 64-bit source per piece, advanced on the scalar unit by the stage's byte step after every issue, and two lane
+  // offsets (weights: 16 bytes per lane; x: the lane's clamped pixel).  The per-sample strides and the tile stride come from the
+  // launcher.  (Before: every piece of every stage rebuilt its address from b, Cin, HW, m0 and k0 -- 64-bit multiplies per piece.)
+  static_assert(A_PIECES % NW == 0 && NW % (BN / 64) == 0 && A_PIECES % (BN / 64) == 0, "a wave's piece j is of one kind");
+  const unsigned x_row = (unsigned)HW * 16u;                      // bytes of one plane row of x (and of a planes output)
+  const char* src[PW];
+  {
+    const char* xb = reinterpret_cast<const char*>(a.x) + (int64_t)b * a.x_bstride;
+    const char* ab = reinterpret_cast<const char*>(a.wmp) + (int64_t)b * a.w_bstride + (uint64_t)(m0 >> 4) * a.w_tile_stride;
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
       const int piece = j * NW + wave;
-      // (saddr form of the LDS-DMA: a uniform base advanced on the scalar unit + a 32-bit lane offset, both made opaque so that
-      // instruction selection sees base + zext(offset) -- with per-lane 64-bit pointers every piece first needed a
-      // v_lshl_add_u64 into the register pair the previous piece was still issuing from)
-      if (piece < A_PIECES) {
+      if (j * NW < A_PIECES) {
         const int ot_l = piece / KQ, kq_l = piece % KQ;
-        const char* ub = reinterpret_cast<const char*>(ab + ((((m0 >> 4) + ot_l) * ((K >> 5) * NP) + (k0 >> 5) * NP + kq_l) * 256));
-        unsigned vo = lane * 16;
-        asm volatile("" : "+s"(ub), "+v"(vo));
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ub + vo),
-                                         (__attribute__((address_space(3))) void*)(dstA + piece * 256), 16, 0, 0);
+        src[j] = ab + (uint64_t)ot_l * a.w_tile_stride + kq_l * 1024;
       } else {
-        const int pb = piece - A_PIECES;
-        const int row = pb / (BN / 64), chunk = pb % (BN / 64);     // row = (channel block of the stage) * NP + plane
-        int n = n0 + chunk * 64 + lane;
-        if (n > HW - 1) n = HW - 1;                                  // clamp: those columns are never stored
-        const char* ub = reinterpret_cast<const char*>(xb + ((int64_t)((k0 >> 3) * NP + row) * HW) * 8);
-        unsigned vo = (unsigned)n * 16u;
-        asm volatile("" : "+s"(ub), "+v"(vo));
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ub + vo),
-                                         (__attribute__((address_space(3))) void*)(dstB + pb * 256), 16, 0, 0);
+        const int row = (piece - A_PIECES) / (BN / 64);           // row = (channel block of the stage) * NP + plane
+        src[j] = xb + (uint64_t)row * x_row;
       }
     }
+  }
+  const unsigned vo_a = lane * 16;
+  unsigned vo_b;
+  {
+    int n = n0 + (wave % (BN / 64)) * 64 + lane;
+    if (n > HW - 1) n = HW - 1;                                    // clamp: those columns are never stored
+    vo_b = (unsigned)n * 16u;
+  }
+  // (saddr form of the LDS-DMA: a uniform base + a 32-bit lane offset, the offset made opaque at every piece so that instruction
+  // selection sees base + zext(offset) in the block of the load -- hoisted out of the loop the extension becomes a 64-bit lane
+  // value, and with per-lane 64-bit pointers every piece first needs a v_lshl_add_u64 into the register pair the previous piece
+  // is still issuing from)
+  const unsigned x_step = (unsigned)((BK >> 3) * NP) * x_row;    // bytes of x one K stage further
+  int ld_slot = 0;                                                 // ring slot of the next stage to load (stages load in order)
+  auto stage_load = [&]() {
+    float* dstA = lds + ld_slot * STAGE;
+    float* dstB = dstA + A_STAGE;
+#pragma unroll
+    for (int j = 0; j < PW; ++j) {
+      const int piece = j * NW + wave;
+      unsigned vo = j * NW < A_PIECES ? vo_a : vo_b;
+      asm volatile("" : "+v"(vo));
+      if (j * NW < A_PIECES) {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + vo),
+                                         (__attribute__((address_space(3))) void*)(dstA + piece * 256), 16, 0, 0);
+        src[j] += KQ * 1024;
+      } else {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + vo),
+                                         (__attribute__((address_space(3))) void*)(dstB + (piece - A_PIECES) * 256), 16, 0, 0);
+        src[j] += x_step;
+      }
+    }
+    ld_slot = ld_slot + 1 == NS ? 0 : ld_slot + 1;
   };
 
   // this lane's four pixels: 16 c + col of the wave's 64-pixel strip (c = MFMA column tile)
@@ -220,7 +275,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   float lc0 = 0.f, lc1 = 0.f;                // the layer's bound constants (planes output)
   float pin = 0.f;                           // this lane's entries of the input's patch maxima (planes output)
   // a planes output under range tracking: the exponent follows from max|in| of this pixel block and the layer's constants
-  const bool track = NP == 2 && a.out_fmt == 1 && a.lconst;
+  const bool track = NP == 2 && out_fmt == 1 && (GEN ? a.lconst != nullptr : RANGED);
   // The epilogue's operands are REQUESTED here (pure loads into registers, right behind the first stage's LDS-DMA) and only
   // turned into what the epilogue needs after the main loop (finish_ops).  Round 5: in the old form -- loads and their arithmetic
   // interleaved -- `a.x_exp ? a.x_exp[..] : a.x_exp_const` became ONE flat load of a selected address (array or kernarg word), a
@@ -231,25 +286,24 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   f32x4 lc_raw = {0.f, 0.f, 0.f, 0.f};
   auto issue_ops = [&]() {
     if constexpr (NP == 2) {
-      const int nblk = (HW + BN - 1) / BN;
-      if (a.x_exp) {        // (an agent-scope relaxed load: a plain global load the compiler cannot fold into a select of addresses)
+      if (x_exp) {          // (an agent-scope relaxed load: a plain global load the compiler cannot fold into a select of addresses)
         typedef const __attribute__((address_space(1))) int gi32_t;
-        e_raw = __hip_atomic_load(reinterpret_cast<gi32_t*>(reinterpret_cast<uintptr_t>(a.x_exp + b * nblk + blockIdx.x)),
+        e_raw = __hip_atomic_load(reinterpret_cast<gi32_t*>(reinterpret_cast<uintptr_t>(x_exp + b * a.nblk + blockIdx.x)),
                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (track) {
         const float* lc = a.lconst + b * 4;
         lc_raw = f32x4{lc[0], lc[1], lc[2], 0.f};
-        if (a.x_pmax) {      // the 2 x Cin/16 patch maxima of this pixel block are contiguous: one load per wave (Cin <= 512)
-          const int n_half = (HW + 63) / 64, per = K >> 4;
+        if (x_pmax) {        // the 2 x Cin/16 patch maxima of this pixel block are contiguous: one load per wave (Cin <= 512)
+          const int n_half = a.n_half, per = K >> 4;
           const int n_ent = (2 * (int)blockIdx.x + 1 < n_half ? 2 : 1) * per;
-          const float* pp = a.x_pmax + ((int64_t)b * n_half + 2 * blockIdx.x) * per;
+          const float* pp = x_pmax + ((int64_t)b * n_half + 2 * blockIdx.x) * per;
           if (lane < n_ent) pin = pp[lane];        // (entries past the first 64 -- Cin > 512 only -- follow in finish_ops)
         }
       }
     }
-    if (a.epilogue == 1) {
-      if (a.noise && a.noise_w) {
+    if (epi) {
+      if (noisy) {
         nw = a.noise_w[0];
         const float* nzp = a.noise + (int64_t)b * a.noise_bstride;
 #pragma unroll
@@ -260,7 +314,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
       for (int i = 0; i < WM; ++i)
         bias4[i] = *reinterpret_cast<const f32x4*>(a.bias + m0 + (wm_i * WM + i) * 16 + 4 * q);
     }
-    if (a.rgb_part) {
+    if (fold) {
 #pragma unroll
       for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -270,15 +324,15 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   };
   auto finish_ops = [&]() {
     if constexpr (NP == 2) {
-      const int e_in = a.x_exp ? __builtin_amdgcn_readfirstlane(e_raw) : a.x_exp_const;
+      const int e_in = x_exp ? __builtin_amdgcn_readfirstlane(e_raw) : a.x_exp_const;
       kin = cips3d_uniform(kin * cips3d_pow2(e_in));
       if (track) {
         lc0 = lc_raw[0];
         lc1 = fmaxf(lc_raw[1], 1.41421356237309515f * lc_raw[2]);
-        if (a.x_pmax) {
-          const int n_half = (HW + 63) / 64, per = K >> 4;
+        if (x_pmax) {
+          const int n_half = a.n_half, per = K >> 4;
           const int n_ent = (2 * (int)blockIdx.x + 1 < n_half ? 2 : 1) * per;
-          const float* pp = a.x_pmax + ((int64_t)b * n_half + 2 * blockIdx.x) * per;
+          const float* pp = x_pmax + ((int64_t)b * n_half + 2 * blockIdx.x) * per;
           for (int i = lane + 64; i < n_ent; i += 64) pin = fmaxf(pin, pp[i]);
         } else {
           // no patch maxima: the caller's constant, or what the input's own exponent says -- its producer put a bound of ITS
@@ -304,6 +358,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   // nothing or lose: the loop moves 48 KB per stage and CU in ~1600 cycles = 30 B/clk per CU = 18 TB/s chip-wide, which is
   // the L2 -> LDS gather rate of this part (MI355X_MICROARCH.md, "Indexed rows: gather into LDS": 66-73 GB/s per CU).  The
   // launch is bound by L2 -> CU bandwidth for its 384 KB of operand tiles per CU, not by latency and not by the matrix pipe.
+  // (With the exits compiled apart and the addresses hoisted -- FMT / FEAT above, chain_geometry below -- the same stamps read 2.5k
+  // cycles to the first landed stage, 12.4k for the 8 K stages, 1.6k epilogue + 1.0k until the stores are acknowledged: the
+  // skeleton went from 7.4k to 4.1k cycles, the loop is what it was.  DESIGN 5.3.)
   // (Round 6: the run as ONE persistent launch -- this body as the per-layer step of a multi-layer kernel, one counter per pixel-block
   // column between layers, bit-identical results -- was built and measured: a hop cost 2.2-2.4 us where a launch boundary between two
   // of these kernels costs 0.7 us (nine layers 118.2 us in one launch, 104.6 us as nine).  Commit 47e2af1 has the kernel,
@@ -316,7 +373,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   if (NS > 2) issue_ops();
 #pragma unroll
   for (int s0 = 0; s0 < NS - 1; ++s0)
-    if (s0 < nstage) stage_load(s0);
+    if (s0 < nstage) stage_load();
   if (NS == 2) issue_ops();
 
 #ifdef CIPS3D_CHAIN_STAMPS
@@ -325,6 +382,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
 #else
 #define PSTAMP(i)
 #endif
+  int rd_slot = 0;                     // ring slot of stage st
   for (int st = 0; st < nstage; ++st) {
     int younger = nstage - 1 - st;
     if (younger > NS - 2) younger = NS - 2;
@@ -341,10 +399,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
 #ifdef CIPS3D_CHAIN_STAMPS
     if (st == 0) CSTAMP(1);          // first stage landed
 #endif
-    if (st + NS - 1 < nstage) stage_load(st + NS - 1);
+    if (st + NS - 1 < nstage) stage_load();
     PSTAMP(1);                         // DMA issue
-    const float* sA = lds + (st % NS) * STAGE;
+    const float* sA = lds + rd_slot * STAGE;
     const float* sB = sA + A_STAGE;
+    rd_slot = rd_slot + 1 == NS ? 0 : rd_slot + 1;
     if constexpr (NP == 2) {
       h8 ah[KB][WM], al[KB][WM], bh[KB][4], bl[KB][4];
 #pragma unroll
@@ -403,7 +462,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
     const int e = cips3d_split_exp(fmaf(lc1, m_in * 1.000001f, lc0));
     kout = cips3d_uniform(cips3d_pow2(-e));
     kback = cips3d_uniform(cips3d_pow2(e));
-    if (blockIdx.y == 0 && tid == 0) a.out_exp[b * ((HW + BN - 1) / BN) + blockIdx.x] = e;
+    if (blockIdx.y == 0 && tid == 0) a.out_exp[b * a.nblk + blockIdx.x] = e;
   }
   // ---- epilogue.  D layout: acc[i][c][r] = out[o = obase + 4 q + r][pixel npx[c]]
   // (one accumulator set per 16-row tile: the ToRGB slots are sums of FOUR tiles in a fixed order whatever the workgroup's height --
@@ -418,8 +477,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
   // v below is the STORED value, out * kout (kout = 1 unless the output is planes): the power of two rides on the constants
   // the epilogue multiplies by anyway, the ToRGB partial sums and the recorded maximum are taken from v and scaled back once
   const float kact = 1.41421356237309515f * kout;
-  const float kpre = a.epilogue == 1 ? kin : kin * kout;      // (one uniform multiplier: no branch per value)
+  const float kpre = epi ? kin : kin * kout;      // (one uniform multiplier: no branch per value)
   float mx = 0.f;
+  char* const ob = reinterpret_cast<char*>(a.out) + (int64_t)b * a.out_bstride;      // this sample's output
+  // the lane's place inside a 16-row tile: planes (bytes): channel block q >> 1 (a row of x_row bytes per plane), elements
+  // 4 (q & 1) ..; NCHW (elements): row 4 q
+  const unsigned lane_cb = (unsigned)(q >> 1) * x_row, lane_el = 8u * (unsigned)(q & 1);
+  const unsigned lane_n = 4u * (unsigned)q * (unsigned)HW;
 #pragma unroll
   for (int i = 0; i < WM; ++i) {
     const int obase = m0 + (wm_i * WM + i) * 16;
@@ -429,11 +493,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         v[r] = acc[i][c][r] * kpre;
-        if (a.epilogue == 1) v[r] = lrelu02(fmaf(nw, nz[c], v[r]) + bias4[i][r]) * kact;
+        if (epi) v[r] = lrelu02(fmaf(nw, nz[c], v[r]) + bias4[i][r]) * kact;
       }
       // (columns past HW repeat the last pixel without its noise: a value the patch maximum may include -- it only has to bound)
       mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fmaxf(fabsf(v[2]), fabsf(v[3])), mx));
-      if (a.rgb_part) {
+      if (fold) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
@@ -443,35 +507,35 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
             asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(prgb[i][ch][c]) : "v"(wrgb[i][ch][r]), "v"(v[r]));
       }
       if (npx[c] < HW) {
-        if (a.out_fmt == 1) {
+        // (addresses: the tile's uniform base + this lane's 32-bit byte offset inside the tile's 16 rows: < 64 HW < 2^30)
+        if (out_fmt == 1) {
           // planes: channels obase + 4 q + r live in channel block (obase >> 3) + (q >> 1), elements 4 (q & 1) + r
           h4 hi, lo;
           split_frag(v[0], v[1], v[2], v[3], hi, lo);
-          _Float16* dst = reinterpret_cast<_Float16*>(a.out) +
-                          ((((int64_t)b * (a.Cout >> 3) + (obase >> 3) + (q >> 1)) * 2) * HW + npx[c]) * 8 + 4 * (q & 1);
+          char* dst = ob + (uint64_t)(obase >> 3) * (2u * x_row) + (size_t)(lane_cb * 2u + lane_el + (unsigned)npx[c] * 16u);
           cips3d_store_wt8(dst, hi);                      // (write-through: common.h)
-          cips3d_store_wt8(dst + (int64_t)HW * 8, lo);
-        } else if (a.out_fmt == 3) {
+          cips3d_store_wt8(dst + (size_t)x_row, lo);
+        } else if (out_fmt == 3) {
           // planes16: the same channel block / element positions, one bf16 plane (round to nearest even: the operand rounding
           // of the bf16 mode)
-          unsigned short* dst = reinterpret_cast<unsigned short*>(a.out) +
-                                (((int64_t)b * (a.Cout >> 3) + (obase >> 3) + (q >> 1)) * HW + npx[c]) * 8 + 4 * (q & 1);
+          char* dst = ob + (uint64_t)(obase >> 3) * x_row + (size_t)(lane_cb + lane_el + (unsigned)npx[c] * 16u);
           cips3d_store_wt8(dst, pack_bf16(v[0], v[1], v[2], v[3]));
-        } else if (a.out_fmt == 2) {
-          unsigned short* dst = reinterpret_cast<unsigned short*>(a.out) + ((int64_t)b * a.Cout + obase + 4 * q) * HW + npx[c];
+        } else if (out_fmt == 2) {
+          unsigned short* dst = reinterpret_cast<unsigned short*>(ob + (uint64_t)obase * ((unsigned)HW * 2u)) +
+                                (size_t)(lane_n + (unsigned)npx[c]);
           typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
           typedef float f32x2_t __attribute__((ext_vector_type(2)));
 #pragma unroll
           for (int r = 0; r < 4; r += 2) {
             const bf16x2_t p = __builtin_convertvector(f32x2_t{v[r], v[r + 1]}, bf16x2_t);
             const unsigned bits = __builtin_bit_cast(unsigned, p);
-            dst[(int64_t)r * HW] = (unsigned short)(bits & 0xffffu);
-            dst[(int64_t)(r + 1) * HW] = (unsigned short)(bits >> 16);
+            dst[(size_t)((unsigned)r * (unsigned)HW)] = (unsigned short)(bits & 0xffffu);
+            dst[(size_t)((unsigned)(r + 1) * (unsigned)HW)] = (unsigned short)(bits >> 16);
           }
         } else {
-          float* dst = reinterpret_cast<float*>(a.out) + ((int64_t)b * a.Cout + obase + 4 * q) * HW + npx[c];
+          float* dst = reinterpret_cast<float*>(ob + (uint64_t)obase * ((unsigned)HW * 4u)) + (size_t)(lane_n + (unsigned)npx[c]);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) cips3d_store_wt(dst + (int64_t)r * HW, v[r]);
+          for (int r = 0; r < 4; ++r) cips3d_store_wt(dst + (size_t)((unsigned)r * (unsigned)HW), v[r]);
         }
       }
     }
@@ -488,18 +552,18 @@ __global__ void __launch_bounds__(64 * WGM * WGN) chain_gemm_kernel(ChainArgs a)
     atomicAdd(&g_chain_stamps[6], ph_[2]);
   }
 #endif
-  if (a.out_pmax && n0 + wn_i * 64 < HW) {
+  if (out_pmax && n0 + wn_i * 64 < HW) {
     // this wave's patch (16 WM channels x 64 pixels): its largest |out|, one plain store per 16 channels
     static_assert(BN == 64 * WGN, "a wave column = one 64-pixel half block");
     const float m = cips3d_wave_max_uniform(mx * kback);
     if (lane < WM)
-      a.out_pmax[((int64_t)b * ((HW + 63) / 64) + (n0 >> 6) + wn_i) * (a.Cout >> 4) + (m0 >> 4) + wm_i * WM + lane] = m;
+      out_pmax[((int64_t)b * a.n_half + (n0 >> 6) + wn_i) * (a.Cout >> 4) + (m0 >> 4) + wm_i * WM + lane] = m;
   }
-  if (a.out_amax) {        // fp32 / bf16 exit: the workgroup's largest |out| raises one slot of the sample's amax array
+  if (out_amax) {          // fp32 / bf16 exit: the workgroup's largest |out| raises one slot of the sample's amax array
     const float m = cips3d_workgroup_max(mx * kback, s_part, wave, lane, NW);
-    if (tid == 0) cips3d_amax_raise_if(a.out_amax + b * CIPS3D_AMAX_FLOATS, m, blockIdx.y * gridDim.x + blockIdx.x);
+    if (tid == 0) cips3d_amax_raise_if(out_amax + b * CIPS3D_AMAX_FLOATS, m, blockIdx.y * gridDim.x + blockIdx.x);
   }
-  if (!a.rgb_part) return;
+  if (!fold) return;
   // ---- folded ToRGB partial of this workgroup's BM rows: over the 4 lane quarters by shuffles, over the WGM wave rows
   // through LDS (every wave passed the last stage's lgkmcnt(0) and meets at the barrier below)
 #pragma unroll
@@ -641,6 +705,70 @@ extern "C" int cips3d_planes_supported(int Cin, int Cout, int64_t HW) {
 // row blocks of the ToRGB partial sums of a planes launch (one rgb_part slot each): 64-row slots, whatever the tile
 extern "C" int cips3d_planes_torgb_blocks(int Cout) { return Cout > 0 ? Cout / 64 : 0; }
 
+namespace {
+
+// ---- the instantiations of chain_gemm_kernel.  Tiles: NP = 2 (split-fp16 planes) 64 x 128 (WM = 1) or, on the half-chip hint,
+// 128 x 128 (WM = 2), 2-slot ring; NP = 1 (planes16) 64 x 128, 3-slot ring.  Forms: what cips3d_decoder_steps can produce (its
+// CIPS3D_STEP_PLANES_GEMM launches run epilogue 1 with the layer's noise, into planes with or without the folded ToRGB, or into
+// fp32 where the run ends; its CIPS3D_STEP_LOWRES_GEMM launches run no epilogue into fp32, with or without a riding fold), each
+// compiled apart; everything else the entry points accept (no noise map, planes out without the range workspace, the bf16 NCHW
+// exit, an amax array behind planes16, ...) runs on the one generic form per tile.  chain_form() looks a launch up; a launch
+// that no row takes is CIPS3D_E_UNSUPP and nothing is enqueued.
+typedef void (*chain_kernel_t)(ChainArgs);
+struct ChainForm { int np, wm, fmt, feat; chain_kernel_t kernel; };
+#define CHAIN_FORM(WM, NS, NP, FMT, FEAT) {NP, WM, FMT, FEAT, chain_gemm_kernel<WM, 4, 2, 64, NS, NP, FMT, FEAT>}
+#define CHAIN_FORMS_SPLIT(WM)                                                                                      \
+  CHAIN_FORM(WM, 2, 2, 1, CF_EPI | CF_NOISE | CF_RANGED),             /* a layer of the run                     */ \
+  CHAIN_FORM(WM, 2, 2, 1, CF_EPI | CF_NOISE | CF_FOLD | CF_RANGED),   /* ... with the ToRGB behind it folded    */ \
+  CHAIN_FORM(WM, 2, 2, 0, CF_EPI | CF_NOISE | CF_RANGED),             /* the run ends in fp32                   */ \
+  CHAIN_FORM(WM, 2, 2, 0, CF_EPI | CF_NOISE | CF_FOLD | CF_RANGED),                                                \
+  CHAIN_FORM(WM, 2, 2, 0, CF_RANGED),                                 /* the low-resolution GEMM of a stage     */ \
+  CHAIN_FORM(WM, 2, 2, 0, CF_RANGED | CF_RIDE),                       /* ... carrying the pending ToRGB sum     */ \
+  CHAIN_FORM(WM, 2, 2, -1, CF_GENERIC)
+const ChainForm chain_forms[] = {
+    CHAIN_FORMS_SPLIT(1),
+    CHAIN_FORMS_SPLIT(2),
+    CHAIN_FORM(1, 3, 1, 3, CF_EPI | CF_NOISE),
+    CHAIN_FORM(1, 3, 1, 3, CF_EPI | CF_NOISE | CF_FOLD),
+    CHAIN_FORM(1, 3, 1, 0, CF_EPI | CF_NOISE),
+    CHAIN_FORM(1, 3, 1, 0, CF_EPI | CF_NOISE | CF_FOLD),
+    CHAIN_FORM(1, 3, 1, 0, 0),
+    CHAIN_FORM(1, 3, 1, 2, 0),
+    CHAIN_FORM(1, 3, 1, -1, CF_GENERIC),
+};
+#undef CHAIN_FORMS_SPLIT
+#undef CHAIN_FORM
+
+// The form of a launch: the row compiled for exactly what it does, else the generic row of its tile, else NULL.  `ranged`: the
+// caller handed a range workspace.  An NCHW exit looks at its range pointers one by one (each may be NULL), so its CF_RANGED rows
+// take the launch without a workspace too; a planes exit's row tracks the exponent unconditionally and needs the workspace.
+const ChainForm* chain_form(int np, int wm, const ChainArgs& a, bool ranged) {
+  int feat = (a.epilogue == 1 ? CF_EPI : 0) | ((a.epilogue == 1 && a.noise && a.noise_w) ? CF_NOISE : 0) | (a.rgb_part ? CF_FOLD : 0) |
+             (a.ride.part ? CF_RIDE : 0);
+  if (np == 2 && (ranged || a.out_fmt != 1)) feat |= CF_RANGED;
+  const bool exact_ok = np == 2 || !a.out_amax;       // (planes16 rows carry no range pointers at all)
+  const ChainForm* generic = nullptr;
+  for (const ChainForm& f : chain_forms) {
+    if (f.np != np || f.wm != wm) continue;
+    if (f.feat & CF_GENERIC) generic = &f;
+    else if (exact_ok && f.fmt == a.out_fmt && f.feat == feat) return &f;
+  }
+  return generic;
+}
+
+// the launch-invariant part of ChainArgs (see there); BN = 128 pixels per workgroup in every form
+void chain_geometry(ChainArgs& a, int np) {
+  const int64_t hw = a.HW;
+  a.x_bstride = (int64_t)a.Cin * hw * np * 2;
+  a.w_bstride = (int64_t)a.Cout * a.Cin * np * 2;
+  a.out_bstride = (int64_t)a.Cout * hw * ((a.out_fmt == 2 || a.out_fmt == 3) ? 2 : 4);
+  a.w_tile_stride = (unsigned)(a.Cin >> 5) * (unsigned)np * 1024u;
+  a.nblk = (int)((hw + 127) / 128);
+  a.n_half = (int)((hw + 63) / 64);
+}
+
+}  // namespace
+
 extern "C" int cips3d_to_planes(const float* x, void* planes, int B, int C, int64_t HW, const float* x_amax, int32_t* exp_out,
                                 float* pmax_out, void* stream) {
   if (!x || !planes || B < 0 || C <= 0 || HW <= 0 || ((x_amax == nullptr) != (exp_out == nullptr)) || (pmax_out && !x_amax))
@@ -703,11 +831,14 @@ extern "C" int cips3d_modconv1x1_planes16(const void* x_planes16, const float* w
               noise_bstride, noise_w, bias, rgb_w, rgb_part, nullptr, 0, nullptr, 0.f, nullptr, rg ? rg->out_amax : nullptr, nullptr,
               nullptr, cips3d_reduce_job{}};
   if (rg && rg->ride) return CIPS3D_E_UNSUPP;       // the riding fold exists in the split-planes kernel only
+  chain_geometry(a, 1);
+  const ChainForm* form = chain_form(1, 1, a, false);
+  if (!form) return CIPS3D_E_UNSUPP;
   // 64 x 128 tiles, 64-deep stages of 24 KB in a 3-slot ring (72 KB: two workgroups per CU).  Same-box sweep (rocprofv3, 512 -> 512
   // at 64^2): batch 1 7.45 us / batch 4 17.4 us; a 2-slot ring 8.0 / 17.5; 128-deep stages 7.4 / 24.2 (one workgroup per CU);
   // 128 x 128 tiles (2/3 of the operand bytes per flop) 9.6 / 19.8; 64 x 64 tiles 7.5 / 19.9.
   dim3 grid((unsigned)ceil_div<int64_t>(HW, 128), (unsigned)(Cout / 64), (unsigned)B);
-  hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 3, 1>), grid, dim3(512), 0, as_stream(stream), a);
+  hipLaunchKernelGGL(form->kernel, grid, dim3(512), 0, as_stream(stream), a);
   return cips3d_launch_status();
 }
 
@@ -744,9 +875,13 @@ extern "C" int cips3d_modconv1x1_planes(const void* x_planes, const float* wm, v
   // against 0.303-0.308 ms per view, same box x3; alone on the device such a launch is SLOWER, 16.3 against 11.1 us: only on the hint).
   // The ToRGB slots stay 64-row slots (same bits).
   const int64_t tiles64 = (int64_t)B * (Cout / 64) * ceil_div<int64_t>(HW, 128);
-  if (rg && rg->half_chip && Cout % 128 == 0 && tiles64 > 192 && tiles64 <= 256) {
+  const bool half_chip = rg && rg->half_chip && Cout % 128 == 0 && tiles64 > 192 && tiles64 <= 256;
+  chain_geometry(a, 2);
+  const ChainForm* form = chain_form(2, half_chip ? 2 : 1, a, rg != nullptr);
+  if (!form) return CIPS3D_E_UNSUPP;
+  if (half_chip) {
     dim3 grid2((unsigned)ceil_div<int64_t>(HW, 128), (unsigned)(Cout / 128) + (a.ride.part ? 1u : 0u), (unsigned)B);
-    hipLaunchKernelGGL((chain_gemm_kernel<2, 4, 2, 64, 2>), grid2, dim3(512), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(form->kernel, grid2, dim3(512), 0, as_stream(stream), a);
     return cips3d_launch_status();
   }
   dim3 grid((unsigned)ceil_div<int64_t>(HW, 128), (unsigned)(Cout / 64) + (a.ride.part ? 1u : 0u), (unsigned)B);
@@ -754,6 +889,6 @@ extern "C" int cips3d_modconv1x1_planes(const void* x_planes, const float* wm, v
   // workgroups -- 16.3 us per 512 -> 512 layer against 12.2: twice the MFMAs and fragment reads per wave at the same one
   // workgroup per CU; 32 x 128 tiles / four waves for the 512 -> 256 exit, whose 64 x 128 grid covers half the CUs: 10.4 against
   // 10.0 us.)
-  hipLaunchKernelGGL((chain_gemm_kernel<1, 4, 2, 64, 2>), grid, dim3(512), 0, as_stream(stream), a);
+  hipLaunchKernelGGL(form->kernel, grid, dim3(512), 0, as_stream(stream), a);
   return cips3d_launch_status();
 }

@@ -13,7 +13,7 @@ for i in $(seq $R); do
     cp cips_3dplusplus_amd/_ab/hash_$v cips_3dplusplus_amd/libcips3d_hip.so.srchash
     echo -n "$v: "
     CIPS3D_HIPCC_FLAGS="$(cat cips_3dplusplus_amd/_ab/flags_$v)" python3 bench.py --full --no-also --no-cpu-baseline --steps 200 --repeats 5 --detail "" ${BENCH_ARGS} 2>/dev/null | tail -1 | \
-      python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['ms_per_step_repeats'], 'render', d['roofline']['avg_launch_ms'])"
+      python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['ms_per_step_repeats'], 'single_stream', (d.get('single_stream') or {}).get('ms_per_step'), 'render', d['roofline']['avg_launch_ms'])"
   done
 done
 cp cips_3dplusplus_amd/_ab/lib_default.so cips_3dplusplus_amd/libcips3d_hip.so; cp cips_3dplusplus_amd/_ab/hash_default cips_3dplusplus_amd/libcips3d_hip.so.srchash
