@@ -48,6 +48,13 @@ class ReduceJob(C.Structure):
                 ("n4", C.c_int64), ("HW4", C.c_int64), ("slot_stride", C.c_int64), ("n_slots", C.c_int32), ("n_bias", C.c_int32)]
 
 
+class StageGeom(C.Structure):
+    """cips3d_stage_geom: what a fused-stage launch hands its kernel (cips3d_fused_stage_geometry, include/cips3d_hip.h)."""
+    _fields_ = [("tile_h", C.c_int32), ("tile_w", C.c_int32), ("threads", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("tx_shift", C.c_int32), ("tx_rcp", C.c_uint32), ("HWlo", C.c_int32), ("HWo", C.c_int32), ("pad_", C.c_int32),
+                ("ylo_bs", C.c_int64), ("out2_bs", C.c_int64), ("ynext_bs", C.c_int64), ("rgb_bs", C.c_int64), ("skip_bs", C.c_int64)]
+
+
 # cips3d_dec_layer.flags (CIPS3D_DEC_*)
 DEC_CHAINED, DEC_SPLIT, DEC_PLANES_IN, DEC_PLANES_OUT, DEC_SPLIT16, DEC_P16, DEC_DEMOD, DEC_FLAT_HEAD = 1, 2, 4, 8, 16, 32, 64, 128
 # cips3d_dec_step.kind (CIPS3D_STEP_*), in this order from 0, and .form
@@ -246,6 +253,7 @@ _SIGS = {
                                      c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_int, c_int, c_int, c_int,
                                      C.c_void_p, C.c_void_p]),
     "cips3d_fused_up_conv_chains": (c_int, [c_int]),
+    "cips3d_fused_stage_geometry": (c_int, [c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
     "cips3d_fused_up_conv_next": (c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_f32p, c_f32p,
                                           c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int,
                                           c_int, C.c_void_p, C.c_void_p]),
@@ -410,7 +418,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 45          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 46          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
@@ -420,7 +428,7 @@ def _struct_table():
     return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
             6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
             11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO, 17: DecRouteOpts,
-            18: DecStep, 19: MeshColorParams, 20: MeshTextureParams}
+            18: DecStep, 19: MeshColorParams, 20: MeshTextureParams, 21: StageGeom}
 
 
 def load(build_if_missing=True):

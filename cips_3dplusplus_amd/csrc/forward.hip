@@ -38,6 +38,7 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 18: return (int64_t)sizeof(cips3d_dec_step);
     case 19: return (int64_t)sizeof(cips3d_mesh_color_params);
     case 20: return (int64_t)sizeof(cips3d_mesh_texture_params);
+    case 21: return (int64_t)sizeof(cips3d_stage_geom);
     default: return -1;
   }
 }

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 45 /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 46 /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -520,6 +520,23 @@ int cips3d_fused_flat_conv_supported(int C, int H, int W);
  * CIPS3D_MOD_PACKED | CIPS3D_MOD_CHAINED order, y_next [B,C/2,2H,2W].  wm_next == y_next == NULL: plain cips3d_fused_up_conv.
  * cips3d_fused_up_conv_chains(C): 1 for the widths that have the chained form. */
 int cips3d_fused_up_conv_chains(int C);
+/* What a launch of cips3d_fused_up_conv[_next] hands its kernel instead of having every wave compute it (host only: no GPU call;
+ * cips3d_sizeof_struct(21)).  Workgroup `bid` of a sample (after the kernel's permutation of the linear id) owns the tile at row
+ * bid / tiles_x, column bid % tiles_x; the kernel takes the quotient as bid >> tx_shift when tiles_x is a power of two
+ * (tx_shift >= 0), else as q = (bid * tx_rcp) >> 32 (tx_rcp = 2^32 / tiles_x + 1: the quotient or one more for every
+ * bid < 2^32), minus one when q * tiles_x > bid.  *_bs: BYTES from one sample to the next, for the element types `skip_up`
+ * selects (CIPS3D_Y_BF16: y_lo / y_next are bf16; CIPS3D_RGB_U8: rgb is uint8; bit 0: the skip image has the input's size).
+ * `chained`: the launch has a wm_next / y_next.  Returns CIPS3D_E_UNSUPP for a shape the stage does not take. */
+typedef struct cips3d_stage_geom {
+  int32_t tile_h, tile_w, threads;   /* output pixels of a workgroup's tile, threads of a workgroup */
+  int32_t tiles_x, tiles_y;          /* grid = (tiles_x * tiles_y, 1, B) */
+  int32_t tx_shift;                  /* log2(tiles_x), or -1 */
+  uint32_t tx_rcp;
+  int32_t HWlo, HWo;                 /* elements of one channel plane of y_lo; of the outputs */
+  int32_t pad_;
+  int64_t ylo_bs, out2_bs, ynext_bs, rgb_bs, skip_bs;
+} cips3d_stage_geom;
+int cips3d_fused_stage_geometry(int C, int chained, int H, int W, int skip_up, cips3d_stage_geom* geom);
 int cips3d_fused_up_conv_next(const float* y_lo, const float* fir, const float* noise1, int64_t noise1_bstride,
                               const float* noise_w1, const float* bias1, const float* wm2, const float* noise2,
                               int64_t noise2_bstride, const float* noise_w2, const float* bias2, float* out2,
