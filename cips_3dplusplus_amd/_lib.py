@@ -325,11 +325,18 @@ _SIGS = {
     "cips3d_nerf_bwd_camera_geo": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
                                            c_f32p, C.c_void_p]),
     "cips3d_camera_params_bwd": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_f32p, C.c_void_p]),
+    "cips3d_camera_axis_angle": (c_int, [c_f32p, c_f32p, c_f32p, c_f32, c_f32, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p,
+                                         C.c_void_p]),
+    "cips3d_camera_axis_angle_bwd": (c_int, [c_f32p, c_f32p, c_f32p, c_f32, c_int, c_f32p, c_f32p, c_int, c_f32p, c_f32p, c_f32p,
+                                             C.c_void_p]),
+    "cips3d_nerf_bwd_camera_intr": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
+                                            c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_fused_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "cips3d_nerf_bwd_fused_stash_floats": (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "cips3d_nerf_bwd_fused_scratch_floats": (c_i64, [c_int, c_int, c_int, c_int, c_int]),
     "cips3d_nerf_pack_weights_t": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, C.c_void_p]),
     "cips3d_nerf_bwd_fused": (c_int, [C.c_void_p, C.c_void_p]),
+    "cips3d_nerf_bwd_fused_intr": (c_int, [C.c_void_p, c_f32p, C.c_void_p]),
     "cips3d_generator_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_style_phase": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     "cips3d_decoder_route_flags": (c_int, [C.c_void_p, c_int, C.POINTER(DecRouteOpts), C.POINTER(c_i64)]),
@@ -418,7 +425,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 46          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 47          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

@@ -524,6 +524,37 @@ class CameraFn(Function):
         return hip.camera_params_bwd(locations, dextr, up).to(locations.dtype), None, None, None, None
 
 
+class CameraAxisAngleFn(Function):
+    """The free camera (hip.camera_axis_angle): pose = [exp([rot]x) | normalize(trans)], differentiable w.r.t. rot, trans and --
+    when it is a tensor -- fov_ang (through the focal length, whose gradient NerfRenderFn returns).  One launch each way."""
+
+    @staticmethod
+    def forward(ctx, rot, trans, img_size, fov_ang, dist_radius):
+        extr, focal, near, far = hip.camera_axis_angle(rot, trans, img_size, fov_ang, dist_radius)
+        fov_t = fov_ang.detach() if torch.is_tensor(fov_ang) else None
+        ctx.save_for_backward(rot.detach(), trans.detach(), fov_t)
+        ctx.fov_s, ctx.img_size = None if fov_t is not None else float(fov_ang), img_size
+        # (focal carries a graph only for a field of view that asks for a gradient: NerfRenderFn launches its focal
+        # instantiation exactly then)
+        ctx.mark_non_differentiable(*((near, far) if fov_t is not None and ctx.needs_input_grad[3] else (focal, near, far)))
+        ctx.set_materialize_grads(False)        # (else the engine fills a zero gradient for each absent upstream)
+        return extr, focal, near, far
+
+    @staticmethod
+    def backward(ctx, dextr, dfocal, dnear, dfar):
+        rot, trans, fov_t = ctx.saved_tensors
+        need_fov = fov_t is not None and ctx.needs_input_grad[3]
+        if not need_fov:
+            dfocal = None
+        if dextr is None and dfocal is None:
+            return None, None, None, None, None
+        drot, dtrans, dfov = hip.camera_axis_angle_bwd(rot, trans, ctx.img_size, fov_t if fov_t is not None else ctx.fov_s,
+                                                       dextr, dfocal, need_dfov=need_fov)
+        return (drot.to(rot.dtype) if ctx.needs_input_grad[0] else None,
+                dtrans.to(trans.dtype) if ctx.needs_input_grad[1] else None, None,
+                dfov.reshape(fov_t.shape).to(fov_t.dtype) if need_fov else None, None)
+
+
 class FilmTableFn(Function):
     """gamma / beta of every FiLM layer in one launch (the renderer's own table, cips3d_linear_table) with the table backward."""
 
@@ -624,7 +655,9 @@ class NerfRenderFn(Function):
     fused kernel;
     backward = the fused recompute + backward kernels of csrc/nerf_bwd_fused.hip (the materialised sequence of
     csrc/nerf_bwd.hip for shapes they do not cover, or with CIPS3D_FUSED_NERF_BACKWARD=0).  The renderer's own weights are treated as constants
-    (`optim_render_params: false` in the released inversion recipes, train_cips3d_compcars_v10.yaml:585)."""
+    (`optim_render_params: false` in the released inversion recipes, train_cips3d_compcars_v10.yaml:585).
+    `focals` that require grad (the free camera's field of view) get d loss / d focals from the camera chain's second
+    instantiation (hip.nerf_backward*(d_focal=True)); otherwise it is not launched and the gradient is None."""
 
     @staticmethod
     def forward(ctx, renderer, cam_poses, focals, near, far, film, perturb_u, img_size, n_samples, static_viewdirs, *params):
@@ -665,21 +698,26 @@ class NerfRenderFn(Function):
             dfeat = torch.zeros(B, H, img_size, img_size, device=cam_poses.device)
         if dthumb is None:
             dthumb = torch.zeros(B, 3, img_size, img_size, device=cam_poses.device)
+        if ctx.needs_input_grad[2]:
+            geo["d_focal"] = True               # (the returned tuple then ends in d focals [B])
+        dfoc = lambda t: t[-1].reshape(focals.shape).to(focals.dtype) if ctx.needs_input_grad[2] else None
         if ctx.want_params:
-            dfilm, dcam, pg = hip.nerf_backward(r.network, sig_beta, cam_poses, focals, near, far, perturb_u, film,
-                                                layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(),
-                                                need_params=True, **geo)
+            out = hip.nerf_backward(r.network, sig_beta, cam_poses, focals, near, far, perturb_u, film,
+                                    layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(),
+                                    need_params=True, **geo)
+            dfilm, dcam, pg = out[:3]
             names = [n for n, _ in nerf_named_parameters(r)]
             grads = tuple(pg[n].reshape(p.shape) if ctx.needs_input_grad[10 + i] else None
                           for i, (n, (_, p)) in enumerate(zip(names, nerf_named_parameters(r))))
-            return (None, dcam, None, None, None, dfilm, None, None, None, None) + grads
+            return (None, dcam, dfoc(out), None, None, dfilm, None, None, None, None) + grads
         if hip.FUSED_NERF_BACKWARD and hip.nerf_backward_fused_supported(H, r.N_layers_renderer, img_size, n_samples):
             packed, _ = r._derived_buffers()
-            dfilm, dcam = hip.nerf_backward_fused(r.network, sig_beta, cam_poses, focals, near, far, perturb_u,
-                                                  film, layer_bias, packed, r._packed_transposed(), img_size, n_samples,
-                                                  static, dfeat, dthumb, fwd=ctx.fwd, **geo)
+            out = hip.nerf_backward_fused(r.network, sig_beta, cam_poses, focals, near, far, perturb_u,
+                                          film, layer_bias, packed, r._packed_transposed(), img_size, n_samples,
+                                          static, dfeat, dthumb, fwd=ctx.fwd, **geo)
             ctx.fwd = None
         else:
-            dfilm, dcam = hip.nerf_backward(r.network, sig_beta, cam_poses, focals, near, far, perturb_u, film,
-                                            layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(), **geo)
-        return (None, dcam, None, None, None, dfilm, None, None, None, None) + (None,) * ctx.n_params
+            out = hip.nerf_backward(r.network, sig_beta, cam_poses, focals, near, far, perturb_u, film,
+                                    layer_bias, img_size, n_samples, static, dfeat.float(), dthumb.float(), **geo)
+        dfilm, dcam = out[:2]
+        return (None, dcam, dfoc(out), None, None, dfilm, None, None, None, None) + (None,) * ctx.n_params

@@ -66,6 +66,46 @@ class Camera(object):
         return Camera.generate_camera_params_v1(img_size, device, batch, locations, sweep, uniform, azim_range,
                                                 elev_range, fov_ang, dist_radius, up=None)
 
+    @staticmethod
+    def get_camera2world(cam2world, trans, homo=False):
+        """cips3d/nerf_utils.py:439-463: cam2world [..., 3] axis-angle, trans [..., 3] -> [..., 3, 4] = [exp([r]x) | trans]
+        (or [..., 4, 4] with the row (0, 0, 0, 1)).  Nothing is normalised here -- the reference's projector normalises `trans`
+        before the call.  The rotation is Rodrigues' formula as a torch expression (what pytorch3d's axis_angle_to_matrix
+        computes), on any device and differentiable; the loop's one-launch form is `free_camera_params`."""
+        assert cam2world.shape[:-1] == trans.shape[:-1]
+        prefix = cam2world.shape[:-1]
+        r = cam2world.reshape(-1, 3)
+        s = (r * r).sum(-1)
+        small = s < 1e-4                          # (the series there: the quotients' rounding would be divided by s)
+        s_ = torch.where(small, torch.ones_like(s), s)
+        t = torch.sqrt(s_)
+        a = torch.where(small, 1 - s / 6 + s * s / 120, torch.sin(t) / t)
+        b = torch.where(small, 0.5 - s / 24 + s * s / 720, (1 - torch.cos(t)) / s_)
+        z = torch.zeros_like(s)
+        K = torch.stack([z, -r[:, 2], r[:, 1], r[:, 2], z, -r[:, 0], -r[:, 1], r[:, 0], z], -1).reshape(-1, 3, 3)
+        rot_m = torch.eye(3, dtype=r.dtype, device=r.device) + a.view(-1, 1, 1) * K + b.view(-1, 1, 1) * (K @ K)
+        extr = torch.cat((rot_m.view(*prefix, 3, 3), trans.view(*prefix, 3, 1)), dim=-1)
+        if homo:
+            extend = torch.zeros(*prefix, 1, 4, dtype=extr.dtype, device=extr.device)
+            extend[..., 0, 3] = 1.
+            extr = torch.cat((extr, extend), dim=-2)
+        return extr
+
+    @staticmethod
+    def free_camera_params(img_size, device, rot, trans, fov_ang=6, dist_radius=0.12):
+        """The free camera of the axis-angle projector in ONE launch (hip.camera_axis_angle): rot [B,3] axis-angle, trans [B,3]
+        (normalised onto the unit sphere inside, F.normalize) -> (extrinsics [B,3,4], focal, near, far [B,1,1]).  Differentiable
+        w.r.t. rot, trans and a tensor fov_ang when one of them requires grad (autograd.CameraAxisAngleFn)."""
+        rot, trans = rot.to(device), trans.to(device)
+        if torch.is_tensor(fov_ang):
+            if fov_ang.numel() not in (1, rot.shape[0]):
+                raise RuntimeError("fov_ang tensor must have 1 or B elements")
+            fov_ang = fov_ang.to(device)
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (rot, trans, fov_ang)):
+            from .autograd import CameraAxisAngleFn
+            return CameraAxisAngleFn.apply(rot, trans, img_size, fov_ang, dist_radius)
+        return hip.camera_axis_angle(rot, trans, img_size, fov_ang, dist_radius)
+
 
 # ---------------------------------------------------------------------------------------- trajectories
 def yaw_trajectory(n_frames, azim_range=(-0.77, 0.77), elev=0.0, fov=6.0):
@@ -102,6 +142,28 @@ def cameras_from_trajectory(traj, img_size, device, dist_radius=0.12, up=None):
                                                       fov_ang=traj[:, 2].contiguous(), dist_radius=dist_radius,
                                                       up=None if up is None else up.to(device))
     return e, f, n, fa
+
+
+def cameras_around_pose(base_extr, traj, img_size, device, dist_radius=0.12):
+    """Rows (d azim, d elev, fov) of `traj` as offsets around a given pose base_extr [3,4] (an inverted subject's camera): row i
+    gives Ry(d azim) Rx(-d elev) base -- a WORLD rotation of the whole camera, applied to its axes and to its origin -- with the
+    row's field of view.  For the frontal base (identity, origin (0,0,1)) this is the pose cameras_from_trajectory makes.
+    -> (extrinsics [n,3,4], focal, near, far [n,1,1]) on `device`; a torch expression of a dozen small ops per call (a
+    sequence calls it once), the intrinsics as everywhere else."""
+    traj = traj.to(device=device, dtype=torch.float32)
+    base = base_extr.detach().to(device=device, dtype=torch.float32).reshape(3, 4)
+    n = traj.shape[0]
+    az, el = traj[:, 0], traj[:, 1]
+    ca, sa, ce, se = torch.cos(az), torch.sin(az), torch.cos(el), torch.sin(el)
+    z, o = torch.zeros_like(az), torch.ones_like(az)
+    ry = torch.stack([ca, z, sa, z, o, z, -sa, z, ca], -1).reshape(n, 3, 3)
+    rx = torch.stack([o, z, z, z, ce, se, z, -se, ce], -1).reshape(n, 3, 3)       # Rx(-d elev)
+    extr = (ry @ rx) @ base.unsqueeze(0)
+    fov = traj[:, 2].double() * math.pi / 180
+    focal = (0.5 * img_size / torch.tan(fov)).float().reshape(n, 1, 1)
+    near = torch.full((n, 1, 1), 1.0 - dist_radius, device=traj.device)
+    far = torch.full((n, 1, 1), 1.0 + dist_radius, device=traj.device)
+    return extr.contiguous(), focal, near, far
 
 
 def translate_rotate_cameras(n_frames, trans_max, img_size, device, fov_ang=6.0, dist_radius=0.12):

@@ -78,9 +78,12 @@ INVERSION_KEYS = ("azim", "elev", "w_render_opt", "w_decoder_opt", "render_state
                   "noise_bufs", "padding")
 
 
-def save_inversion(path, azim, elev, w_render_opt, w_decoder_opt, G, noise_bufs=None, padding=None):
-    """projector_v10.py:1044-1055 + :1262-1263."""
-    cpu = lambda t: t.detach().cpu()
+def save_inversion(path, azim, elev, w_render_opt, w_decoder_opt, G, noise_bufs=None, padding=None, rot=None, trans=None,
+                   fov=None):
+    """projector_v10.py:1044-1055 + :1262-1263.  rot / trans [bs,3] and fov [bs] (degrees): the free camera of
+    project_wplus(camera="axis_angle"), whose azim / elev are None; each key is written only when given, so a look-at
+    inversion's file holds exactly INVERSION_KEYS."""
+    cpu = lambda t: None if t is None else t.detach().cpu()
     obj = {
         "azim": cpu(azim), "elev": cpu(elev), "w_render_opt": cpu(w_render_opt), "w_decoder_opt": cpu(w_decoder_opt),
         "render_state_dict": {k: cpu(v) for k, v in G.renderer.state_dict().items()},
@@ -88,6 +91,9 @@ def save_inversion(path, azim, elev, w_render_opt, w_decoder_opt, G, noise_bufs=
         "noise_bufs": None if noise_bufs is None else [cpu(b) for b in noise_bufs],
         "padding": padding,
     }
+    for k, v in (("rot", rot), ("trans", trans), ("fov", fov)):
+        if v is not None:
+            obj[k] = cpu(v)
     torch.save(obj, path)
     return path
 
@@ -106,6 +112,25 @@ def load_inversion(path, w_idx=0):
     if noise is not None:
         noise = [b.detach().requires_grad_(False) for b in noise]
     return azim, elev, w_render, w_decoder, kw["decoder_state_dict"], noise, kw.get("render_state_dict")
+
+
+def load_inversion_camera(path, w_idx=0):
+    """The camera an inversion ended at, as (cam_pose [1,3,4] float32 on the CPU, fov in degrees | None): of a free-camera
+    file [exp([rot]x) | normalize(trans)] of view `w_idx` and its "fov" (None when the file has none); of a look-at file the
+    look-at pose of (azim, elev)[w_idx], and None -- its field of view was the caller's cam_cfg.  This is what
+    multiview.sample_multi_view takes as base_pose / base_fov."""
+    import torch.nn.functional as F
+    from .camera import Camera, cameras_around_pose
+    kw = _torch_load(path)
+    if kw.get("rot") is not None and kw.get("trans") is not None:
+        rot, trans = kw["rot"].detach().double()[[w_idx]], kw["trans"].detach().double()[[w_idx]]
+        pose = Camera.get_camera2world(rot, F.normalize(trans, p=2, dim=1)).float()
+        fov = kw.get("fov")
+        return pose, None if fov is None else float(fov.reshape(-1)[w_idx])
+    frontal = torch.eye(3, 4)
+    frontal[2, 3] = 1.0
+    row = torch.tensor([[float(kw["azim"][w_idx]), float(kw["elev"][w_idx]), 6.0]])
+    return cameras_around_pose(frontal, row, 64, "cpu")[0], None
 
 
 def apply_inversion(G, decoder_state_dict=None, render_state_dict=None):

@@ -467,13 +467,19 @@ __global__ void __launch_bounds__(256) film_grad_kernel(float* __restrict__ buf,
 // linear in the per-sample sums) -- a thread per ray alone is R*B/64 waves on the whole chip; 12 atomics per workgroup.
 // d_mask / d_xyz (either set): xyz = sum_k w_k (o + z_k d) also reaches the pose directly, d o += wsum xbar, d d += wzsum xbar
 // (world units: not scaled by 2 / span), in slice 0 beside ddnorm.
+// FOCAL (a second instantiation; the first is the kernel without it, instruction for instruction): also d loss / d focals [B]
+// (atomics; zeroed by the caller).  d_cam = (dcx, dcy, -1) with dcx, dcy ~ 1 / focal, so with g_cam = Rm^T dD -- plus, with
+// static_viewdirs, the view direction's own (dV - v <v, dV>) / |d_cam|, which does not pass through the pose --
+// d focal = -(g_cam[0] dcx + g_cam[1] dcy) / focal: a thirteenth sum, reduced like the twelve pose entries.
+template <bool FOCAL>
 __global__ void __launch_bounds__(1024) camera_chain_kernel(cips3d_nerf_bwd_geom G, const float* __restrict__ dptsn,
                                                             const float* __restrict__ dvd_pt,
                                                             const float* __restrict__ ddnorm, float* __restrict__ dcam,
                                                             const float* __restrict__ d_mask, const float* __restrict__ d_xyz,
                                                             const float* __restrict__ xyz, const float* __restrict__ wsum,
-                                                            const float* __restrict__ wzsum) {
-  __shared__ float sh[12][16];
+                                                            const float* __restrict__ wzsum, float* __restrict__ dfocal) {
+  __shared__ float sh[FOCAL ? 13 : 12][16];
+  float vf = 0.f;
   const int b = blockIdx.y;
   const int R = G.img_size * G.img_size;
   const int ray = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -524,13 +530,36 @@ __global__ void __launch_bounds__(1024) camera_chain_kernel(cips3d_nerf_bwd_geom
       for (int j = 0; j < 3; ++j) v[i * 4 + j] = dD[i] * dc[j];
       v[i * 4 + 3] = dO[i];
     }
+    if constexpr (FOCAL) {
+      const float* cw = G.cam_poses + 12 * b;
+      float g0 = (dD[0] * cw[0] + dD[1] * cw[4]) + dD[2] * cw[8];
+      float g1 = (dD[0] * cw[1] + dD[1] * cw[5]) + dD[2] * cw[9];
+      if (G.static_viewdirs) {
+        const float dotv = (r.vx * dV[0] + r.vy * dV[1]) + r.vz * dV[2];
+        g0 += (dV[0] - r.vx * dotv) / r.vnorm;
+        g1 += (dV[1] - r.vy * dotv) / r.vnorm;
+      }
+      vf = -(g0 * r.dcx + g1 * r.dcy) / G.focals[b];
+    }
   }
 #pragma unroll
   for (int i = 0; i < 12; ++i) {
     const float s = wave_sum(v[i]);
     if ((threadIdx.x & 63) == 0) sh[i][slice] = s;
   }
+  if constexpr (FOCAL) {
+    const float s = wave_sum(vf);
+    if ((threadIdx.x & 63) == 0) sh[12][slice] = s;
+  }
   __syncthreads();
+  if constexpr (FOCAL) {
+    if (threadIdx.x == 64) {      // (the second wave: the first one's lanes 0 .. 11 own the pose entries)
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) s += sh[12][j];
+      unsafeAtomicAdd(dfocal + b, s);
+    }
+  }
   if (threadIdx.x < 12) {
     float s = 0.f;
 #pragma unroll
@@ -689,10 +718,12 @@ extern "C" int cips3d_nerf_bwd_film_grad(float* buf, const float* pre, const flo
   return cips3d_launch_status();
 }
 
-// accumulate != 0: added to a dcam the caller has zeroed; d_mask / d_xyz NULL: no direct path from the geometry maps
-extern "C" int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
-                                          const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
-                                          const float* wsum, const float* wzsum, int accumulate, float* dcam, void* stream) {
+// accumulate != 0: added to a dcam the caller has zeroed; d_mask / d_xyz NULL: no direct path from the geometry maps;
+// dfocal NULL: the kernel without the focal sum, else the second instantiation, added to a dfocal [B] the caller has zeroed
+extern "C" int cips3d_nerf_bwd_camera_intr(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
+                                           const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
+                                           const float* wsum, const float* wzsum, int accumulate, float* dcam, float* dfocal,
+                                           void* stream) {
   if (!geom_ok(G) || !dptsn || !dvd_pt || !ddnorm || !dcam) return CIPS3D_E_BADARG;
   if ((d_mask && !xyz) || ((d_mask || d_xyz) && (!wsum || !wzsum))) return CIPS3D_E_BADARG;
   if (G->B == 0) return 0;
@@ -702,9 +733,21 @@ extern "C" int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* G, const f
     if (e != hipSuccess) return (int)e;
   }
   const int R = G->img_size * G->img_size;
-  hipLaunchKernelGGL(camera_chain_kernel, dim3((unsigned)ceil_div(R, 64), (unsigned)G->B), dim3(1024), 0, st, *G, dptsn, dvd_pt,
-                     ddnorm, dcam, d_mask, d_xyz, xyz, wsum, wzsum);
+  const dim3 grid((unsigned)ceil_div(R, 64), (unsigned)G->B);
+  if (dfocal != nullptr)
+    hipLaunchKernelGGL(camera_chain_kernel<true>, grid, dim3(1024), 0, st, *G, dptsn, dvd_pt, ddnorm, dcam, d_mask, d_xyz, xyz,
+                       wsum, wzsum, dfocal);
+  else
+    hipLaunchKernelGGL(camera_chain_kernel<false>, grid, dim3(1024), 0, st, *G, dptsn, dvd_pt, ddnorm, dcam, d_mask, d_xyz, xyz,
+                       wsum, wzsum, dfocal);
   return cips3d_launch_status();
+}
+
+extern "C" int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
+                                          const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
+                                          const float* wsum, const float* wzsum, int accumulate, float* dcam, void* stream) {
+  return cips3d_nerf_bwd_camera_intr(G, dptsn, dvd_pt, ddnorm, d_mask, d_xyz, xyz, wsum, wzsum, accumulate, dcam, nullptr,
+                                     stream);
 }
 
 extern "C" int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,

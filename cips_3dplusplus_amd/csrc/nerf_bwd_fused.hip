@@ -802,7 +802,7 @@ extern "C" int cips3d_nerf_pack_weights_t(const float* w_hidden, const float* w_
   return cips3d_launch_status();
 }
 
-extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, void* stream) {
+extern "C" int cips3d_nerf_bwd_fused_intr(const cips3d_nerf_bwd_fused_params* pp, float* dfocal, void* stream) {
   if (!pp) return CIPS3D_E_BADARG;
   const cips3d_nerf_bwd_fused_params& P = *pp;
   const cips3d_nerf_bwd_geom& G = P.geom;
@@ -865,6 +865,14 @@ extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, voi
   hipLaunchKernelGGL(finalize_film_kernel, dim3(ceil_div(B * L * H, 256)), dim3(256), 0, st, a.sums, P.layer_bias, P.packed, B,
                      L, H, P.dfilm);
   if ((rc = cips3d_launch_status())) return rc;
-  return cips3d_nerf_bwd_camera_geo(&G, a.dptsn, a.dvd, a.ddnorm, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, 1, P.dcam,
-                                    st);                                            // (dcam: zeroed by the preparation launch)
+  if (dfocal) {                  // (opt-in: the preparation launch stays the one it is without it)
+    hipError_t e = hipMemsetAsync(dfocal, 0, sizeof(float) * B, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  return cips3d_nerf_bwd_camera_intr(&G, a.dptsn, a.dvd, a.ddnorm, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, 1, P.dcam,
+                                     dfocal, st);                                   // (dcam: zeroed by the preparation launch)
+}
+
+extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, void* stream) {
+  return cips3d_nerf_bwd_fused_intr(pp, nullptr, stream);
 }

@@ -394,7 +394,7 @@ class Generator(nn.Module):
         if differentiable is None:
             differentiable = False
             if torch.is_grad_enabled():
-                ins = [cam_poses, style_render, style_decoder] + list(noise_bufs or [])
+                ins = [cam_poses, focals, style_render, style_decoder] + list(noise_bufs or [])
                 differentiable = (any(torch.is_tensor(t) and t.requires_grad for t in ins)
                                   or any(p.requires_grad for p in self.decoder.parameters())
                                   or any(p.requires_grad for p in self.renderer.parameters()))
@@ -458,8 +458,11 @@ class Generator(nn.Module):
         rparams = [p for _, p in AG.nerf_named_parameters(self.renderer)]
         if not any(p.requires_grad for p in rparams):
             rparams = []
+        # (a focal length that asks for a gradient -- the free camera's field of view -- stays attached: NerfRenderFn returns its
+        # gradient; every other intrinsic is a constant)
+        focals_in = focals.float() if torch.is_tensor(focals) and focals.requires_grad else per_view(focals)
         features, thumb, xyz, mask = AG.NerfRenderFn.apply(
-            self.renderer, cam_poses.float(), per_view(focals), per_view(near), per_view(far), film,
+            self.renderer, cam_poses.float(), focals_in, per_view(near), per_view(far), film,
             None if perturb_u is None else perturb_u.detach(), img_size, N, static, *rparams)
         if self.renderer_detach if renderer_detach is None else renderer_detach:
             features = features.detach()                                    # model_v3.py:1016-1017

@@ -326,6 +326,53 @@ def camera_params(locations, img_size, fov_ang=6.0, dist_radius=0.12, up=None):
     return extr, focal, near, far
 
 
+def _fov_arg(fov_ang, B):
+    """fov_ang as the camera entry points take it: (a [B] float32 tensor | None, the scalar used when it is None)."""
+    if not torch.is_tensor(fov_ang):
+        return None, float(fov_ang)
+    fov_t = fov_ang.detach().float().reshape(-1).contiguous()
+    if fov_t.numel() == 1 and B != 1:
+        fov_t = fov_t.expand(B).contiguous()
+    if fov_t.numel() != B:
+        raise ValueError(f"fov_ang tensor must have 1 or {B} elements, got {fov_t.numel()}")
+    return fov_t, 0.0
+
+
+def camera_axis_angle(rot, trans, img_size, fov_ang=6.0, dist_radius=0.12):
+    """The free camera (cips3d_camera_axis_angle, csrc/camera_free.hip): rot [B,3] axis-angle, trans [B,3] -> extrinsics
+    [B,3,4] = [exp([rot]x) | normalize(trans)], focal/near/far [B,1,1] (the shapes of camera_params).  One launch."""
+    lib = _lib.load()
+    B, dev = rot.shape[0], rot.device
+    if tuple(rot.shape) != (B, 3) or tuple(trans.shape) != (B, 3):
+        raise ValueError(f"camera_axis_angle: rot and trans must be [B,3], got {list(rot.shape)} and {list(trans.shape)}")
+    r, t = rot.detach().float().contiguous(), trans.detach().float().contiguous()
+    fov_t, fov_s = _fov_arg(fov_ang, B)
+    extr = torch.empty(B, 3, 4, device=dev)
+    focal, near, far = (torch.empty(B, 1, 1, device=dev) for _ in range(3))
+    check(lib.cips3d_camera_axis_angle(dev_ptr(r, "rot"), dev_ptr(t, "trans"), dev_ptr(fov_t, "fov", True), fov_s,
+                                       float(dist_radius), int(img_size), B, dev_ptr(extr), dev_ptr(focal), dev_ptr(near),
+                                       dev_ptr(far), stream_ptr()), "cips3d_camera_axis_angle")
+    return extr, focal, near, far
+
+
+def camera_axis_angle_bwd(rot, trans, img_size, fov_ang, dextr=None, dfocal=None, need_dfov=None):
+    """Backward of camera_axis_angle: dextr [B,3,4] and dfocal [B] (each may be None = zero) -> (drot [B,3], dtrans [B,3],
+    dfov [B] | None).  need_dfov: None = when dfocal is given."""
+    lib = _lib.load()
+    B, dev = rot.shape[0], rot.device
+    r, t = rot.detach().float().contiguous(), trans.detach().float().contiguous()
+    fov_t, fov_s = _fov_arg(fov_ang, B)
+    de = None if dextr is None else dextr.float().reshape(B, 3, 4).contiguous()
+    df = None if dfocal is None else dfocal.float().reshape(B).contiguous()
+    drot, dtrans = torch.empty(B, 3, device=dev), torch.empty(B, 3, device=dev)
+    dfov = torch.empty(B, device=dev) if (df is not None if need_dfov is None else need_dfov) else None
+    check(lib.cips3d_camera_axis_angle_bwd(dev_ptr(r, "rot"), dev_ptr(t, "trans"), dev_ptr(fov_t, "fov", True), fov_s,
+                                           int(img_size), dev_ptr(de, "dextr", True), dev_ptr(df, "dfocal", True), B,
+                                           dev_ptr(drot), dev_ptr(dtrans), dev_ptr(dfov, "dfov", True), stream_ptr()),
+          "cips3d_camera_axis_angle_bwd")
+    return drot, dtrans, dfov
+
+
 def nerf_pack_weights(w_hidden, w_view, hidden, depth):
     lib = _lib.load()
     packed = torch.empty(int(lib.cips3d_nerf_packed_floats(hidden, depth)), device=w_view.device, dtype=torch.float32)
@@ -1286,7 +1333,7 @@ def _nerf_bwd_geom(cam_poses, focals, near, far, perturb_u, img_size, n_samples,
 
 
 def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, film, layer_bias, img_size, n_samples,
-                  static_viewdirs, d_features, d_thumb, need_params=False, d_mask=None, d_xyz=None, xyz=None):
+                  static_viewdirs, d_features, d_thumb, need_params=False, d_mask=None, d_xyz=None, xyz=None, d_focal=False):
     """The materialised NeRF backward (see csrc/nerf_bwd.hip): returns (dfilm [B,L,2,H], dcam [B,3,4]) -- and, with
     need_params (`optim_render_params`, models/projector_v10.py:848-872), a dict of the gradients of the renderer's own
     weights: pts_linears.{l}.weight / .bias, views_linears.weight / .bias, rgb_linear.*, sigma_linear.*, sigmoid_beta
@@ -1294,7 +1341,9 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
 
     net = SirenGenerator (weights), film [B,L,2,H], layer_bias [L,H]; d_features [B,H,S,S], d_thumb [B,3,S,S].
     d_mask [2,B,S,S] (d mask[0], d depth) and d_xyz [B,3,S,S]: the upstreams of the geometry maps, None = absent; d_mask needs
-    `xyz`, the forward's [B,3,S,S] map.  They enter the compositing backward and the camera chain -- no further launch."""
+    `xyz`, the forward's [B,3,S,S] map.  They enter the compositing backward and the camera chain -- no further launch.
+    d_focal=True (opt-in): d loss / d focals [B] is appended to the returned tuple -- the camera chain's second instantiation
+    (cips3d_nerf_bwd_camera_intr) and one [B] memset; False launches exactly what it did without the argument."""
     lib = _lib.load()
     st = stream_ptr()
     dev = cam_poses.device
@@ -1424,6 +1473,11 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     check(lib.cips3d_nerf_bwd_heads(dev_ptr(dpre), dev_ptr(w_first), 1, 3, None, 3, B, H, P, dev_ptr(dptsn), st),
           "cips3d_nerf_bwd_heads")
     dcam = new(B, 3, 4)
+    if d_focal:
+        dfoc = torch.zeros(B, device=dev)
+        check(lib.cips3d_nerf_bwd_camera_intr(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), *geo_ptrs, 0, dev_ptr(dcam),
+                                              dev_ptr(dfoc), st), "cips3d_nerf_bwd_camera_intr")
+        return (dfilm, dcam, pg, dfoc) if need_params else (dfilm, dcam, dfoc)
     check(lib.cips3d_nerf_bwd_camera_geo(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), *geo_ptrs, 0, dev_ptr(dcam), st),
           "cips3d_nerf_bwd_camera_geo")
     if need_params:
@@ -1462,9 +1516,9 @@ def nerf_forward_stash(B, img_size, n_samples, hidden, depth, device, n_chunks=N
 
 def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, film, layer_bias, packed, packed_t, img_size,
                         n_samples, static_viewdirs, d_features, d_thumb, fwd=None, d_mask=None, d_xyz=None, xyz=None, n_chunks=None,
-                        stash=None):
+                        stash=None, d_focal=False):
     """The fused NeRF backward (csrc/nerf_bwd_fused.hip): returns (dfilm [B,L,2,H], dcam [B,3,4]); same contract as
-    nerf_backward (d_mask / d_xyz / xyz included).  `fwd` = the nerf_forward_stash buffers a differentiable forward filled: the
+    nerf_backward (d_mask / d_xyz / xyz and the opt-in d_focal, which appends d loss / d focals [B], included).  `fwd` = the nerf_forward_stash buffers a differentiable forward filled: the
     forward is then not recomputed.  `n_chunks` (without `fwd`, which carries its own): chunks a ray's samples are split into,
     1 .. n_samples; None = nerf_suggest_chunks.  `stash` (without `fwd`): a float32 buffer of cips3d_nerf_bwd_fused_stash_floats
     floats that the forward recompute fills instead of a private allocation."""
@@ -1505,6 +1559,10 @@ def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb
     p.hidden, p.depth, p.n_chunks = H, D, n_chunks
     geo = _geo_upstreams(d_mask, d_xyz, xyz, B, R)          # (held until the call is enqueued)
     p.d_mask, p.d_xyz, p.xyz = (dev_ptr(t, "geometry upstream", True) for t in geo)
+    if d_focal:
+        dfoc = torch.empty(B, device=dev)                   # (cleared by the call)
+        check(lib.cips3d_nerf_bwd_fused_intr(C.byref(p), dev_ptr(dfoc), stream_ptr()), "cips3d_nerf_bwd_fused_intr")
+        return dfilm, dcam, dfoc
     check(lib.cips3d_nerf_bwd_fused(C.byref(p), stream_ptr()), "cips3d_nerf_bwd_fused")
     return dfilm, dcam
 

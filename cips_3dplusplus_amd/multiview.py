@@ -126,7 +126,7 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
                       zero_noise_bufs=False, noise_bufs=None, azim_range=(-0.77, 0.77), elev=0.0, circle=None,
                       trans_max=0.04, only_rotate=False, chunk=1, gather=("rgb", "thumb_rgb", "xyz"), to_uint8=True,
                       group=None, hoist=True, uint8_in_kernel=True, lanes=2, project_noise=None,
-                      panel=("rgb", "thumb_rgb", "shaded"), panel_resample="lanczos"):
+                      panel=("rgb", "thumb_rgb", "shaded"), panel_resample="lanczos", base_pose=None, base_fov=None):
     """The frame loop of `_sample_multi_view_web` (render_video_web_v10.py:1651-1899) without the web page: one z pair,
     one set of noise buffers, `perturb=False`, a camera trajectory (`yaw` / `circle` / `translate_rotate`), one
     `G(...)` call per `chunk` frames with `truncation=truncation_ratio, return_xyz=True`.  With torch.distributed
@@ -162,19 +162,40 @@ def sample_multi_view(G, cam_cfg, nerf_cfg, zs, view_mode="yaw", N_frames=8, tru
     uint8 (n, 3, R, len(panel) R).  Each call's panes are composed on the call's own lane straight into the rank's panel block
     (frames.compose_panels, csrc/frame_resample.hip; fp32 panes are quantised on load), which travels to rank 0 as uint8 like
     `rgb`.  Panes the panel needs are produced even when they are not gathered themselves; everything else the call returns
-    is what it returns without "panel"."""
+    is what it returns without "panel".
+    `base_pose` ([3,4] or [1,3,4]; `yaw` and `circle` only): the camera an inversion ended at (checkpoint.load_inversion_camera,
+    or project_wplus's "cam_poses" row).  The trajectory's (azim, elev) rows then are OFFSETS around it -- row i renders from
+    Ry(azim_i) Rx(-elev_i) base_pose (camera.cameras_around_pose) -- which is how an inverted subject is shown from new views.
+    `base_fov` (degrees, with base_pose): the inverted field of view; it replaces cam_cfg's in `yaw` and is where `circle`'s
+    fov_range starts.  None (default): the trajectory's own look-at cameras, as ever."""
     from . import hip
-    from .camera import yaw_trajectory, circle_trajectory, cameras_from_trajectory, translate_rotate_cameras
+    from .camera import (yaw_trajectory, circle_trajectory, cameras_from_trajectory, translate_rotate_cameras,
+                         cameras_around_pose)
     dev = next(G.parameters()).device
     img_size = cam_cfg["img_size"]
     fov, dist_radius = cam_cfg.get("fov_ang", 6), cam_cfg.get("dist_radius", 0.12)
+    if base_pose is None and base_fov is not None:
+        raise ValueError("sample_multi_view: base_fov belongs to base_pose")
+    if base_pose is not None:
+        if view_mode not in ("yaw", "circle"):
+            raise ValueError(f"sample_multi_view: base_pose applies to the 'yaw' and 'circle' modes, not {view_mode!r}")
+        if base_pose.numel() != 12:
+            raise ValueError(f"sample_multi_view: base_pose must be one [3,4] pose, got {list(base_pose.shape)}")
+        if base_fov is not None:
+            fov = float(base_fov)
+        around = lambda traj: cameras_around_pose(base_pose.reshape(3, 4), traj, img_size, dev, dist_radius)
+    else:
+        around = lambda traj: cameras_from_trajectory(traj, img_size, dev, dist_radius)
     if view_mode == "yaw":
         traj = yaw_trajectory(N_frames, azim_range, elev, fov)
-        ext, foc, near, far = cameras_from_trajectory(traj, img_size, dev, dist_radius)
+        ext, foc, near, far = around(traj)
     elif view_mode == "circle":
         c = circle or {}
-        traj = circle_trajectory(N_frames, c.get("azim_range", 0.5), c.get("elev_range", 0.0), c.get("fov_range", (6.0, 8.0)))
-        ext, foc, near, far = cameras_from_trajectory(traj, img_size, dev, dist_radius)
+        fr = c.get("fov_range", (6.0, 8.0))
+        if base_fov is not None:
+            fr = (fov, fov + (fr[1] - fr[0]))
+        traj = circle_trajectory(N_frames, c.get("azim_range", 0.5), c.get("elev_range", 0.0), fr)
+        ext, foc, near, far = around(traj)
     elif view_mode == "translate_rotate":
         ext, traj, foc, near, far = translate_rotate_cameras(N_frames, trans_max, img_size, dev, fov, dist_radius)
         if only_rotate:

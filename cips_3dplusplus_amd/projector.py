@@ -210,6 +210,26 @@ class FlipProjector:
             groups.append({"params": [loc], "lr": lr_cam, "initial_lr": lr_cam, "betas": (0.9, 0.999)})
         return loc, _adam(groups) if groups else None
 
+    def _free_cam_optimizer(self, optim_cam, lr_cam, bs, rot_init, trans_init, optim_fov, lr_fov, fov_init):
+        """-> (pose [bs, 6] = (rot | trans) per view, fov [bs] | None, optimiser).  The reference keeps rot and trans as two [bs, 3]
+        parameters of one Adam group (projector_axis_angle.py:260-278); as for (azim, elev) above, ONE [bs, 6] parameter takes
+        the same element-wise steps.  Starts at rot = 0, trans = (0, 0, 1): the frontal look-at camera.  `fov` (optim_fov: a
+        parameter in its own group at lr_fov) is the field of view in degrees per view."""
+        pose = torch.zeros(bs, 6, device=self.device)
+        pose[:, 5] = 1
+        if rot_init is not None:
+            pose[:, :3] = torch.as_tensor(rot_init, dtype=torch.float32).reshape(-1, 3).to(self.device)
+        if trans_init is not None:
+            pose[:, 3:] = torch.as_tensor(trans_init, dtype=torch.float32).reshape(-1, 3).to(self.device)
+        groups, fov = [], None
+        if optim_cam:
+            pose = nn.Parameter(pose)
+            groups.append({"params": [pose], "lr": lr_cam, "initial_lr": lr_cam, "betas": (0.9, 0.999)})
+        if optim_fov:
+            fov = nn.Parameter(torch.full((bs,), float(fov_init), device=self.device))
+            groups.append({"params": [fov], "lr": lr_fov, "initial_lr": lr_fov, "betas": (0.9, 0.999)})
+        return pose, fov, _adam(groups) if groups else None
+
     def _render_optimizer(self, G, mean_r, optim_render_w, lr_render_w, bs, optim_render_params=False):
         w = mean_r.detach().reshape(1, 1, -1).repeat(bs, G.N_layers_renderer + 1, 1).contiguous()
         groups = []
@@ -239,14 +259,24 @@ class FlipProjector:
         return w, noise_bufs, _adam(groups) if groups else None
 
     # ---- one generator call of the loop (projector_v10.py:211-277)
-    def g_forward(self, G, style_render, style_decoder, noise_bufs, cam_cfg, nerf_cfg, rot, trans=None, flip_w_decoder=False):
-        """rot, trans: azimuth and elevation [B, 1] each -- or rot = the [B, 2] locations and trans = None."""
+    def g_forward(self, G, style_render, style_decoder, noise_bufs, cam_cfg, nerf_cfg, rot, trans=None, flip_w_decoder=False,
+                  camera="look_at", fov=None):
+        """rot, trans: azimuth and elevation [B, 1] each -- or rot = the [B, 2] locations and trans = None.
+        camera="axis_angle" (projector_axis_angle.py:190-203): rot [B, 3] an axis-angle vector, trans [B, 3] a position that is
+        normalised onto the unit sphere, fov None (cam_cfg's) or the [B] field of view in degrees."""
         cam_cfg = dict(cam_cfg)
         img_size = cam_cfg.pop("img_size")
         cam_cfg = {k: v for k, v in cam_cfg.items() if k in ("fov_ang", "dist_radius")}
-        extr, focal, near, far, _ = Camera.generate_camera_params(img_size, self.device,
-                                                                  locations=rot if trans is None else torch.cat([rot, trans], 1),
-                                                                  **cam_cfg)
+        if camera == "axis_angle":
+            if fov is not None:
+                cam_cfg["fov_ang"] = fov
+            extr, focal, near, far = Camera.free_camera_params(img_size, self.device, rot, trans, **cam_cfg)
+        elif camera == "look_at":
+            extr, focal, near, far, _ = Camera.generate_camera_params(img_size, self.device,
+                                                                      locations=rot if trans is None else torch.cat([rot, trans], 1),
+                                                                      **cam_cfg)
+        else:
+            raise ValueError(f"g_forward: camera must be 'look_at' or 'axis_angle', got {camera!r}")
         if flip_w_decoder:
             style_decoder = style_decoder.detach().flip(dims=(0,))      # only the decoder parameters are updated
         r = G(zs=[None, None], style_render=style_render, style_decoder=style_decoder, cam_poses=extr, focals=focal,
@@ -259,8 +289,16 @@ class FlipProjector:
                       lr_decoder_params=0.005, lr_noise=0.001, truncation_psi=1.0, flip_w_decoder_every=10,
                       azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
                       mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0, lpips_metric=None,
-                      ssim_weight=0.0, silhouette_weight=0.0, target_masks=None):
+                      ssim_weight=0.0, silhouette_weight=0.0, target_masks=None, camera="look_at", optim_fov=False, lr_fov=0.05,
+                      rot_init=None, trans_init=None):
         """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
+        `camera`: "look_at" (the default: (azim, elev) of a look-at camera with a fixed up vector and field of view) or
+        "axis_angle", the free camera of the reference's projector_axis_angle.py: per view an axis-angle rotation `rot` (start
+        0, or rot_init [bs_cam, 3]) and a position `trans` (start (0, 0, 1), or trans_init; normalised onto the unit sphere in
+        every forward, never in place), one Adam group at lr_cam -- it can follow an in-plane roll, which the look-at camera
+        cannot.  `optim_fov` (free camera only) also optimises the field of view in degrees per view, in its own group at
+        lr_fov, through the render's focal gradient.  In that mode the dict gains "rot", "trans" [bs_cam, 3], "fov" [bs_cam] and
+        "cam_poses" [bs_cam, 3, 4] (the final poses), "azim" / "elev" are None, and `on_step` receives (step, loss, rot, trans).
         `mask_background`: from the appearance phase on, the image's gradient only flows where the render's foreground mask says
         so (mask_blend; the thumbnail is not blended, as in the reference).  `mse_weight` > 0 adds mse_weight x
         F.mse_loss(image, target_images) (projector_v10.py:1176-1181).  `ssim_weight` > 0 (needs `target_images`) adds
@@ -281,6 +319,11 @@ class FlipProjector:
         final re-render's LPIPS of view 0 against target_images[0] becomes "lpips" (a float); with `metrics_every` > 0 the logged
         steps' values go to metrics_history["lpips"], enqueued beside the PSNR / SSIM launches (perceptual.LPIPSLog) and read
         once.  None: no network is built (the reference's default downloads one) and nothing changes."""
+        if camera not in ("look_at", "axis_angle"):
+            raise ValueError(f"project_wplus: camera must be 'look_at' or 'axis_angle', got {camera!r}")
+        if optim_fov and camera != "axis_angle":
+            raise ValueError("project_wplus: optim_fov needs camera='axis_angle' (the look-at camera's field of view is fixed)")
+        free = camera == "axis_angle"
         if mse_weight > 0 and target_images is None:
             raise ValueError("project_wplus: mse_weight > 0 needs target_images")
         if ssim_weight > 0 and target_images is None:
@@ -321,8 +364,15 @@ class FlipProjector:
         G.decoder.requires_grad_(True)
         with torch.no_grad():
             mean_r, mean_d = G.get_mean_latent(w_avg_samples, self.device)
-        loc, opt_cam = self._cam_optimizer(optim_cam, lr_cam, list(azim_init), bs_cam)
-        azim, elev = loc.detach()[:, 0:1], loc.detach()[:, 1:2]          # (views: they follow the optimiser's in-place updates)
+        if free:
+            loc, fov, opt_cam = self._free_cam_optimizer(optim_cam, lr_cam, bs_cam, rot_init, trans_init, optim_fov, lr_fov,
+                                                         cam_cfg.get("fov_ang", 6))
+            azim, elev = loc.detach()[:, :3], loc.detach()[:, 3:]        # (rot, trans: what on_step receives in this mode)
+            cam_kw = lambda: dict(rot=loc[:, :3], trans=loc[:, 3:], camera="axis_angle", fov=fov)
+        else:
+            loc, opt_cam = self._cam_optimizer(optim_cam, lr_cam, list(azim_init), bs_cam)
+            azim, elev = loc.detach()[:, 0:1], loc.detach()[:, 1:2]      # (views: they follow the optimiser's in-place updates)
+            cam_kw = lambda: dict(rot=loc)
         one = torch.ones((), device=self.device)                         # d loss / d loss, allocated once (backward() would fill one per step)
         w_render, opt_render = self._render_optimizer(G, mean_r, optim_render_w, lr_render_w, bs_render, optim_render_params)
         w_decoder, noise_bufs, opt_dec = self._decoder_optimizer(
@@ -351,7 +401,7 @@ class FlipProjector:
             # (one NeRF latent for both views, bs_render = 1: the generator broadcasts it inside the FiLM table's launch)
             rgb, thumb, mask = self.g_forward(
                 G, w_render, w_decoder if w_decoder.shape[0] == 2 else w_decoder.repeat(2, 1, 1), noise_bufs, cam_cfg, nerf_cfg,
-                rot=loc, flip_w_decoder=flip_w_decoder)
+                flip_w_decoder=flip_w_decoder, **cam_kw())
             if metrics_log is not None and (step % metrics_every == 0 or step == N_steps - 1):
                 metrics_log.update(step, rgb[0:1])
                 if lpips_log is not None:
@@ -384,11 +434,20 @@ class FlipProjector:
                "w_decoder_opt": w_decoder.detach(), "render_state_dict": G.renderer.state_dict(),
                "decoder_state_dict": G.decoder.state_dict(), "noise_bufs": [b.detach() for b in noise_bufs], "padding": 0,
                "loss_history": torch.stack(history).cpu() if history else None, "G": G}
+        if free:
+            with torch.no_grad():
+                cs = int(cam_cfg["img_size"])
+                fov_out = fov.detach().clone() if fov is not None else torch.full((bs_cam,), float(cam_cfg.get("fov_ang", 6)),
+                                                                                  device=self.device)
+                poses = Camera.free_camera_params(cs, self.device, loc.detach()[:, :3], loc.detach()[:, 3:], fov_ang=fov_out,
+                                                  dist_radius=cam_cfg.get("dist_radius", 0.12))[0]
+            out.update({"azim": None, "elev": None, "rot": azim.clone(), "trans": elev.clone(), "fov": fov_out,
+                        "cam_poses": poses})
         if metrics_log is not None or lpips_log is not None:
             with torch.no_grad():                        # projector_v10.py:1229-1242: the clean re-render at the optimised state
                 proj_rgb, _, _ = self.g_forward(
                     G, w_render, w_decoder if w_decoder.shape[0] == 2 else w_decoder.repeat(2, 1, 1), noise_bufs, cam_cfg, nerf_cfg,
-                    rot=loc)
+                    **cam_kw())
                 if metrics_log is not None:
                     metrics_log.update(N_steps, proj_rgb[0:1])
                 if lpips_log is not None:

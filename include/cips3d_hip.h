@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 46 /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 47 /* bumped with every change of an entry point or of a struct layout below */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -139,6 +139,23 @@ int cips3d_linear_table_bwd(const cips3d_linear_desc* table_dev, int n_desc, int
 int cips3d_camera_params(const float* locations, const float* fov_deg, float fov_deg_scalar,
                          const float* up, float dist_radius, int img_size, int B,
                          float* extrinsics, float* focal, float* near_, float* far_, void* stream);
+
+/* The free camera of the axis-angle projector (models/projector_axis_angle.py; Camera.get_camera2world,
+ * cips3d/nerf_utils.py:439-463): rot [B,3] an axis-angle vector, trans [B,3] a position; fov_deg [B] or NULL (then
+ * fov_deg_scalar).  extrinsics [B,3,4] = [exp([rot]x) | trans / max(|trans|, 1e-12)] (pytorch3d's axis_angle_to_matrix and
+ * F.normalize), evaluated in fp64 and rounded once; focal / near / far [B] exactly as cips3d_camera_params writes them
+ * (focal = 0.5 img_size / tan(fov pi / 180), 1 -+ dist_radius).  At rot = 0, trans = (0,0,1) the pose is that of
+ * cips3d_camera_params at azim = elev = 0, bit for bit.  One launch, one thread per view. */
+int cips3d_camera_axis_angle(const float* rot, const float* trans, const float* fov_deg, float fov_deg_scalar,
+                             float dist_radius, int img_size, int B, float* extrinsics, float* focal, float* near_,
+                             float* far_, void* stream);
+/* Its backward: dextrinsics [B,3,4] and dfocal [B], either may be NULL (= zero), -> drot [B,3], dtrans [B,3] and dfov [B]
+ * (dfov may be NULL: not written; it is d loss / d fov in degrees).  fp64 inside; finite at rot = 0, where d R / d rot_i is
+ * the generator [e_i]x; below the clamp of F.normalize dtrans = d column / 1e-12 (the denominator is a constant there), above
+ * it dtrans is orthogonal to trans.  One launch. */
+int cips3d_camera_axis_angle_bwd(const float* rot, const float* trans, const float* fov_deg, float fov_deg_scalar,
+                                 int img_size, const float* dextrinsics, const float* dfocal, int B, float* drot,
+                                 float* dtrans, float* dfov, void* stream);
 
 /* ------------------------------------------------------------------ NeRF renderer */
 
@@ -1194,6 +1211,14 @@ int cips3d_nerf_bwd_camera_acc(const cips3d_nerf_bwd_geom* geom, const float* dp
 int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
                                const float* d_mask, const float* d_xyz, const float* xyz, const float* wsum, const float* wzsum,
                                int accumulate, float* dcam, void* stream);
+/* cips3d_nerf_bwd_camera_geo with the gradient of the intrinsics: dfocal [B] (zeroed by the caller; NULL: exactly
+ * cips3d_nerf_bwd_camera_geo, the same kernel) += d loss / d focals.  The ray's camera-frame direction is (dcx, dcy, -1) with
+ * dcx, dcy ~ 1 / focal, so d focal = -sum_rays (g_cam[0] dcx + g_cam[1] dcy) / focal with g_cam = R^T d rays_d, plus -- with
+ * static_viewdirs, where the view direction is normalize(d_cam) and does not pass through the pose -- the view direction's
+ * own adjoint.  A second instantiation of the same kernel; near / far / perturb_u stay constants. */
+int cips3d_nerf_bwd_camera_intr(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
+                                const float* d_mask, const float* d_xyz, const float* xyz, const float* wsum, const float* wzsum,
+                                int accumulate, float* dcam, float* dfocal, void* stream);
 /* ---- NeRF half, fused backward (csrc/nerf_bwd_fused.hip): the same gradients as the sequence above -- d loss / d film
  * [B,L,2,H] and d loss / d cam_poses [B,3,4] from d_features [B,H,R] and d_thumb [B,3,R] -- with the point MLP kept in the
  * register file in both directions (the reference gets them from autograd through cips3d/volume_renderer.py:39-160 and
@@ -1251,6 +1276,10 @@ int64_t cips3d_nerf_bwd_fused_scratch_floats(int B, int img_size, int n_samples,
 int cips3d_nerf_pack_weights_t(const float* w_hidden, const float* w_view, const float* packed, float* packed_t, int hidden,
                                int depth, void* stream);
 int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* p, void* stream);
+/* The same with the gradient of the intrinsics: dfocal [B] (out; cleared by the call) = d loss / d focals, from
+ * cips3d_nerf_bwd_camera_intr at the end of the call.  NULL: exactly cips3d_nerf_bwd_fused -- the same launches.  (An argument,
+ * not a field: cips3d_nerf_bwd_fused_params keeps its layout.) */
+int cips3d_nerf_bwd_fused_intr(const cips3d_nerf_bwd_fused_params* p, float* dfocal, void* stream);
 
 /* Backward of cips3d_camera_params w.r.t. locations (azim, elev): dextrinsics [B,3,4] -> dlocations [B,2]
  * (cips3d/nerf_utils.py:344-436,466-564; focal / near / far do not depend on the angles). */

@@ -4,6 +4,7 @@
                                      [--vgg-precision fp32_exact|split_fp16]
                                      [--optim-noise-bufs] [--mask-background] [--mse-weight W] [--metrics-every K]
                                      [--lpips random] [--ssim-weight W] [--silhouette-weight W]
+                                     [--camera look_at|axis_angle] [--optim-fov]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
@@ -23,7 +24,11 @@ expressions of the first two instead of the HIP nodes (A/B).  With none of the t
 SSIM node of csrc/ssim_loss.hip; CIPS3D_FUSED_SSIM=0 runs its torch expression instead, A/B).  0: the run is what it was.
 --silhouette-weight W: W x mean (mask - (1 - target_masks))^2 of the render's mask map is added (project_wplus's
 `silhouette_weight`); the target is the same generator's foreground (1 - mask) rendered once at another pose (azimuth +-0.35,
-mean latent).  Its gradient goes through the mask map into the NeRF backward.  0: the run is what it was."""
+mean latent).  Its gradient goes through the mask map into the NeRF backward.  0: the run is what it was.
+--camera axis_angle: the free camera (project_wplus's `camera`: an axis-angle rotation and a position on the unit sphere per
+view, csrc/camera_free.hip, instead of (azim, elev)); --optim-fov also optimises the field of view through the render's focal
+gradient (the camera chain's second instantiation).  The JSON line's config gains "camera" (and "optim_fov") in that mode;
+look_at (default): the run is what it was."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -46,6 +51,8 @@ ap.add_argument("--metrics-every", type=int, default=0)
 ap.add_argument("--lpips", choices=("random",), default=None)
 ap.add_argument("--ssim-weight", type=float, default=0.0)
 ap.add_argument("--silhouette-weight", type=float, default=0.0)
+ap.add_argument("--camera", choices=("look_at", "axis_angle"), default="look_at")
+ap.add_argument("--optim-fov", action="store_true")
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -101,12 +108,17 @@ if a.lpips:
     extra.update(lpips_metric=LPIPS("vgg_random", generator=torch.Generator().manual_seed(3), precision=a.vgg_precision),
                  target_images=t_rgb)
     knobs["lpips"] = a.lpips
+if a.camera != "look_at" or a.optim_fov:
+    extra.update(camera=a.camera, optim_fov=a.optim_fov)
+    knobs["camera"] = a.camera
+    if a.optim_fov:
+        knobs["optim_fov"] = True
 n_pose, n_app = a.steps, a.app_steps
 if a.mask_background:                   # the blend runs from the appearance phase on: time appearance steps
     extra.update(mask_background=True)
     knobs["mask_background"] = True
     n_pose, n_app = 0, a.steps + a.app_steps
-if set(knobs) - {"metrics_every", "lpips", "ssim_weight", "fused_ssim", "silhouette_weight"}:
+if set(knobs) - {"metrics_every", "lpips", "ssim_weight", "fused_ssim", "silhouette_weight", "camera", "optim_fov"}:
     from cips_3dplusplus_amd import projector as _P
     knobs["fused_noise_reg"], knobs["fused_mask_blend"] = _P.FUSED_NOISE_REG, _P.FUSED_MASK_BLEND
 out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=n_pose, N_steps_app=n_app,
