@@ -299,8 +299,6 @@ _SIGS = {
     "cips3d_modulate_table_bwd": (c_int, [C.c_void_p, c_int, c_int, c_int, C.c_void_p]),
     "cips3d_decoder_grad_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_decoder_grad_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cips3d_sizeof_grad_plan": (c_int, []),
-    "cips3d_sizeof_grad_io": (c_int, []),
     "cips3d_adam_step": (c_int, [C.c_void_p, c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_int, C.c_void_p]),
     "cips3d_adam_step_groups": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p, c_int, C.c_void_p]),
     "cips3d_gemm_wgrad_split": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_i64, c_f32p, c_f32p, c_int, C.c_void_p]),
@@ -314,29 +312,22 @@ _SIGS = {
     "cips3d_nerf_bwd_heads": (c_int, [c_f32p, c_f32p, c_int, c_int, c_f32p, c_int, c_int, c_int, c_i64, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_dot": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_i64, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_composite": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                          c_f32p, c_f32p, C.c_void_p]),
-    "cips3d_nerf_bwd_composite_geo": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                              c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+                                          c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_row_dots": (c_int, [c_f32p, c_f32p, c_int, c_i64, c_f32p, c_int, c_int, c_i64, C.c_void_p]),
     "cips3d_nerf_bwd_film_grad": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                           c_f32p, c_f32p, c_int, c_int, c_int, c_i64, C.c_void_p]),
-    "cips3d_nerf_bwd_camera": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "cips3d_nerf_bwd_camera_acc": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "cips3d_nerf_bwd_camera_geo": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
-                                           c_f32p, C.c_void_p]),
+    "cips3d_nerf_bwd_camera": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
+                                       c_f32p, c_f32p, C.c_void_p]),
     "cips3d_camera_params_bwd": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_f32p, C.c_void_p]),
     "cips3d_camera_axis_angle": (c_int, [c_f32p, c_f32p, c_f32p, c_f32, c_f32, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p,
                                          C.c_void_p]),
     "cips3d_camera_axis_angle_bwd": (c_int, [c_f32p, c_f32p, c_f32p, c_f32, c_int, c_f32p, c_f32p, c_int, c_f32p, c_f32p, c_f32p,
                                              C.c_void_p]),
-    "cips3d_nerf_bwd_camera_intr": (c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_int,
-                                            c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_bwd_fused_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "cips3d_nerf_bwd_fused_stash_floats": (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "cips3d_nerf_bwd_fused_scratch_floats": (c_i64, [c_int, c_int, c_int, c_int, c_int]),
     "cips3d_nerf_pack_weights_t": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, C.c_void_p]),
-    "cips3d_nerf_bwd_fused": (c_int, [C.c_void_p, C.c_void_p]),
-    "cips3d_nerf_bwd_fused_intr": (c_int, [C.c_void_p, c_f32p, C.c_void_p]),
+    "cips3d_nerf_bwd_fused": (c_int, [C.c_void_p, c_f32p, C.c_void_p]),
     "cips3d_generator_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_style_phase": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     "cips3d_decoder_route_flags": (c_int, [C.c_void_p, c_int, C.POINTER(DecRouteOpts), C.POINTER(c_i64)]),
@@ -355,8 +346,6 @@ _SIGS = {
     "cips3d_noise_reg_bwd": (c_int, [C.c_void_p, c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_mask_blend": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
     "cips3d_mask_blend_bwd": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_void_p]),
-    "cips3d_sizeof_plan": (c_i64, []),
-    "cips3d_sizeof_io": (c_i64, []),
     "cips3d_sizeof_struct": (c_i64, [c_int]),
     "cips3d_align_volume": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, C.c_double, C.c_double, C.c_void_p]),
     "cips3d_marching_cubes_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
@@ -389,16 +378,12 @@ _SIGS = {
     "cips3d_vgg_features": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_vgg_loss_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_vgg_loss_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cips3d_sizeof_vgg_ctx": (c_int, []),
-    "cips3d_sizeof_vgg_io": (c_int, []),
     "cips3d_vgg_split_supported": (c_int, [c_int, c_int, c_int]),
     "cips3d_vgg_split_range_bytes": (c_i64, [c_int]),
     "cips3d_vgg_split_pack": (c_int, [C.c_void_p, C.c_void_p, c_int, C.c_void_p]),
     "cips3d_vgg_split_features": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_vgg_split_loss_forward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_vgg_split_loss_backward": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cips3d_sizeof_vgg_split_ctx": (c_int, []),
-    "cips3d_sizeof_vgg_split_io": (c_int, []),
     "cips3d_image_metrics": (c_int, [C.c_void_p, c_int, C.c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_void_p, C.c_void_p,
                                      c_i64, C.c_void_p]),
     "cips3d_image_metrics_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
@@ -409,7 +394,6 @@ _SIGS = {
                                   C.c_void_p, C.c_void_p]),
     "cips3d_lpips": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cips3d_lpips_split": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cips3d_sizeof_lpips_io": (c_int, []),
     "cips3d_ssim_loss_tile": (c_int, [C.POINTER(c_int), C.POINTER(c_int)]),
     "cips3d_ssim_loss_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int, c_int]),
     "cips3d_ssim_loss": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int, c_int, C.c_float, C.c_float, C.c_void_p, c_int,
@@ -425,17 +409,30 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 47          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 48          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 
+def _struct_rows():
+    """Row k: (C name, ctypes mirror) of the struct whose size cips3d_sizeof_struct(k) returns -- every struct the header
+    declares (plan.py and decoder_grad.py hold the mirrors of their own structs)."""
+    from . import decoder_grad as dg, plan
+    return [("cips3d_generator_plan", plan.GeneratorPlan), ("cips3d_forward_io", plan.ForwardIO), ("cips3d_nerf_params", NerfParams),
+            ("cips3d_linear_desc", LinearDesc), ("cips3d_modulate_desc", ModulateDesc), ("cips3d_dec_layer", plan.DecLayer),
+            ("cips3d_nerf_bwd_geom", NerfBwdGeom), ("cips3d_nerf_bwd_fused_params", NerfBwdFusedParams), ("cips3d_range", Range),
+            ("cips3d_reduce_job", ReduceJob), ("cips3d_normals_params", NormalsParams),
+            ("cips3d_mesh_resolve_params", MeshResolveParams), ("cips3d_vgg_ctx", VggCtx), ("cips3d_vgg_io", VggIO),
+            ("cips3d_vgg_split_ctx", VggSplitCtx), ("cips3d_vgg_split_io", VggSplitIO), ("cips3d_lpips_io", LpipsIO),
+            ("cips3d_dec_route_opts", DecRouteOpts), ("cips3d_dec_step", DecStep), ("cips3d_mesh_color_params", MeshColorParams),
+            ("cips3d_mesh_texture_params", MeshTextureParams), ("cips3d_stage_geom", StageGeom), ("cips3d_actbwd", ActBwd),
+            ("cips3d_slot_job", dg.SlotJob), ("cips3d_modbwd_desc", dg.ModBwdDesc), ("cips3d_adam_entry", AdamEntry),
+            ("cips3d_adam_hyper", AdamHyper), ("cips3d_noise_buf", NoiseBuf), ("cips3d_grad_layer", dg.GradLayer),
+            ("cips3d_decoder_grad_plan", dg.DecoderGradPlan), ("cips3d_decoder_grad_io", dg.DecoderGradIO)]
+
+
 def _struct_table():
-    """index of cips3d_sizeof_struct -> the ctypes mirror of that struct (plan.py holds the two big ones)."""
-    from . import plan
-    return {0: plan.GeneratorPlan, 1: plan.ForwardIO, 2: NerfParams, 3: LinearDesc, 4: ModulateDesc, 5: plan.DecLayer,
-            6: NerfBwdGeom, 7: NerfBwdFusedParams, 8: Range, 9: ReduceJob, 10: NormalsParams,
-            11: MeshResolveParams, 12: VggCtx, 13: VggIO, 14: VggSplitCtx, 15: VggSplitIO, 16: LpipsIO, 17: DecRouteOpts,
-            18: DecStep, 19: MeshColorParams, 20: MeshTextureParams, 21: StageGeom}
+    """index of cips3d_sizeof_struct -> the ctypes mirror of that struct."""
+    return {k: st for k, (_, st) in enumerate(_struct_rows())}
 
 
 def load(build_if_missing=True):

@@ -364,9 +364,6 @@ extern "C" int cips3d_up2_fir_bwd(const float* g_hi, const float* fir, float* g_
 }
 
 // ------------------------------------------------------------------------------------------------ the two calls
-extern "C" int cips3d_sizeof_grad_plan(void) { return (int)sizeof(cips3d_decoder_grad_plan); }
-extern "C" int cips3d_sizeof_grad_io(void) { return (int)sizeof(cips3d_decoder_grad_io); }
-
 #define TRY(x) do { const int rc_ = (x); if (rc_ != 0) return rc_; } while (0)
 
 static bool grad_layer_ok(const cips3d_grad_layer& L) {

@@ -13,8 +13,7 @@
     if (rc_ != 0) return rc_; \
   } while (0)
 
-extern "C" int64_t cips3d_sizeof_plan(void) { return (int64_t)sizeof(cips3d_generator_plan); }
-extern "C" int64_t cips3d_sizeof_io(void) { return (int64_t)sizeof(cips3d_forward_io); }
+// one row per struct of the public header; the binding's table (_lib._struct_table) mirrors it and is checked at load
 extern "C" int64_t cips3d_sizeof_struct(int which) {
   switch (which) {
     case 0: return (int64_t)sizeof(cips3d_generator_plan);
@@ -39,6 +38,15 @@ extern "C" int64_t cips3d_sizeof_struct(int which) {
     case 19: return (int64_t)sizeof(cips3d_mesh_color_params);
     case 20: return (int64_t)sizeof(cips3d_mesh_texture_params);
     case 21: return (int64_t)sizeof(cips3d_stage_geom);
+    case 22: return (int64_t)sizeof(cips3d_actbwd);
+    case 23: return (int64_t)sizeof(cips3d_slot_job);
+    case 24: return (int64_t)sizeof(cips3d_modbwd_desc);
+    case 25: return (int64_t)sizeof(cips3d_adam_entry);
+    case 26: return (int64_t)sizeof(cips3d_adam_hyper);
+    case 27: return (int64_t)sizeof(cips3d_noise_buf);
+    case 28: return (int64_t)sizeof(cips3d_grad_layer);
+    case 29: return (int64_t)sizeof(cips3d_decoder_grad_plan);
+    case 30: return (int64_t)sizeof(cips3d_decoder_grad_io);
     default: return -1;
   }
 }

@@ -210,5 +210,3 @@ extern "C" int cips3d_lpips_split(const cips3d_vgg_split_ctx* ctx, const cips3d_
   }
   return run_heads(io, &t->io, as_stream(stream));
 }
-
-extern "C" int cips3d_sizeof_lpips_io(void) { return (int)sizeof(cips3d_lpips_io); }

@@ -13,7 +13,7 @@
 //   cips3d_nerf_bwd_heads      rows of a [nr,H] matrix applied over the channels (sigma / rgb heads; W0^T, Wd^T in backward)
 //   cips3d_nerf_bwd_dot        g[p] = <dF[:, ray], f[:, p]>
 //   cips3d_nerf_bwd_composite  volume integration forward + backward per ray -> w, d(sdf), d(rgb logits)
-//                              (_geo: also from the gradients of the mask, depth and xyz maps)
+//                              (also from the gradients of the mask, depth and xyz maps, where given)
 //   cips3d_nerf_bwd_film_grad  d(pre) = upstream * cos(gamma pre + beta) * gamma, sums for d(gamma), d(beta)
 //   cips3d_nerf_bwd_camera     d(points), d(viewdirs) -> d(cam_poses)
 //   cips3d_camera_params_bwd   d(cam_poses) -> d(azim, elev)     (nerf_utils.py:344-436, forward-mode duals)
@@ -666,10 +666,10 @@ extern "C" int cips3d_nerf_bwd_dot(const float* dF, const float* f, int B, int H
 }
 
 // d_mask / d_xyz NULL: the compositing backward of the features and the thumbnail alone
-extern "C" int cips3d_nerf_bwd_composite_geo(const cips3d_nerf_bwd_geom* G, const float* sdf, const float* crgb, const float* g,
-                                             const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch,
-                                             float* dsdf, float* dcrgb, float* ddnorm, float* dbeta_ray, const float* d_mask,
-                                             const float* d_xyz, const float* xyz, float* wsum, float* wzsum, void* stream) {
+extern "C" int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* G, const float* sdf, const float* crgb, const float* g,
+                                         const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch,
+                                         float* dsdf, float* dcrgb, float* ddnorm, float* dbeta_ray, const float* d_mask,
+                                         const float* d_xyz, const float* xyz, float* wsum, float* wzsum, void* stream) {
   if (!geom_ok(G) || !sdf || !crgb || !g || !dthumb || !w || !T_scratch || !dsdf || !dcrgb || !ddnorm)
     return CIPS3D_E_BADARG;
   if ((d_mask && !xyz) || ((d_mask || d_xyz) && (!wsum || !wzsum))) return CIPS3D_E_BADARG;
@@ -683,13 +683,6 @@ extern "C" int cips3d_nerf_bwd_composite_geo(const cips3d_nerf_bwd_geom* G, cons
     hipLaunchKernelGGL(composite_kernel, dim3((unsigned)ceil_div(R, 256), (unsigned)G->B), dim3(256), 0, as_stream(stream), *G, sdf,
                        crgb, g, dthumb, sigmoid_beta, w, T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray, d_mask, d_xyz, xyz, wsum, wzsum);
   return cips3d_launch_status();
-}
-
-extern "C" int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* G, const float* sdf, const float* crgb, const float* g,
-                                         const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch,
-                                         float* dsdf, float* dcrgb, float* ddnorm, float* dbeta_ray, void* stream) {
-  return cips3d_nerf_bwd_composite_geo(G, sdf, crgb, g, dthumb, sigmoid_beta, w, T_scratch, dsdf, dcrgb, ddnorm, dbeta_ray,
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int cips3d_nerf_bwd_row_dots(const float* a, const float* x, int nx, int64_t Px, float* out, int B, int rows,
@@ -720,10 +713,10 @@ extern "C" int cips3d_nerf_bwd_film_grad(float* buf, const float* pre, const flo
 
 // accumulate != 0: added to a dcam the caller has zeroed; d_mask / d_xyz NULL: no direct path from the geometry maps;
 // dfocal NULL: the kernel without the focal sum, else the second instantiation, added to a dfocal [B] the caller has zeroed
-extern "C" int cips3d_nerf_bwd_camera_intr(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
-                                           const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
-                                           const float* wsum, const float* wzsum, int accumulate, float* dcam, float* dfocal,
-                                           void* stream) {
+extern "C" int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
+                                      const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
+                                      const float* wsum, const float* wzsum, int accumulate, float* dcam, float* dfocal,
+                                      void* stream) {
   if (!geom_ok(G) || !dptsn || !dvd_pt || !ddnorm || !dcam) return CIPS3D_E_BADARG;
   if ((d_mask && !xyz) || ((d_mask || d_xyz) && (!wsum || !wzsum))) return CIPS3D_E_BADARG;
   if (G->B == 0) return 0;
@@ -741,23 +734,6 @@ extern "C" int cips3d_nerf_bwd_camera_intr(const cips3d_nerf_bwd_geom* G, const 
     hipLaunchKernelGGL(camera_chain_kernel<false>, grid, dim3(1024), 0, st, *G, dptsn, dvd_pt, ddnorm, dcam, d_mask, d_xyz, xyz,
                        wsum, wzsum, dfocal);
   return cips3d_launch_status();
-}
-
-extern "C" int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
-                                          const float* ddnorm, const float* d_mask, const float* d_xyz, const float* xyz,
-                                          const float* wsum, const float* wzsum, int accumulate, float* dcam, void* stream) {
-  return cips3d_nerf_bwd_camera_intr(G, dptsn, dvd_pt, ddnorm, d_mask, d_xyz, xyz, wsum, wzsum, accumulate, dcam, nullptr,
-                                     stream);
-}
-
-extern "C" int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
-                                      const float* ddnorm, float* dcam, void* stream) {
-  return cips3d_nerf_bwd_camera_geo(G, dptsn, dvd_pt, ddnorm, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dcam, stream);
-}
-
-extern "C" int cips3d_nerf_bwd_camera_acc(const cips3d_nerf_bwd_geom* G, const float* dptsn, const float* dvd_pt,
-                                          const float* ddnorm, float* dcam, void* stream) {
-  return cips3d_nerf_bwd_camera_geo(G, dptsn, dvd_pt, ddnorm, nullptr, nullptr, nullptr, nullptr, nullptr, 1, dcam, stream);
 }
 
 extern "C" int cips3d_camera_params_bwd(const float* locations, const float* up, const float* dextrinsics, int B,

@@ -757,8 +757,8 @@ int launch_fused(const FusedArgs& a, hipStream_t st) {
   if (P.fwd_sdf) hipLaunchKernelGGL((nerf_g_kernel<NT>), dim3(wgs), dim3(WAVES * 64), 0, st, a);
   else hipLaunchKernelGGL((nerf_stash_kernel<NT, TPS>), dim3(wgs), dim3(WAVES * 64), lds_a, st, a);
   if (int rc = cips3d_launch_status()) return rc;
-  if (int rc = cips3d_nerf_bwd_composite_geo(&G, a.sdf, a.crgb, a.g, P.d_thumb, P.sigmoid_beta, a.wts, a.Tb, a.dsdf, a.dcrgb,
-                                             a.ddnorm, nullptr, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, st))
+  if (int rc = cips3d_nerf_bwd_composite(&G, a.sdf, a.crgb, a.g, P.d_thumb, P.sigmoid_beta, a.wts, a.Tb, a.dsdf, a.dcrgb,
+                                         a.ddnorm, nullptr, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, st))
     return rc;
   hipLaunchKernelGGL((nerf_bwd_kernel<NT, TPS>), dim3(wgs), dim3(WAVES * 64), lds_b, st, a);
   return cips3d_launch_status();
@@ -802,7 +802,8 @@ extern "C" int cips3d_nerf_pack_weights_t(const float* w_hidden, const float* w_
   return cips3d_launch_status();
 }
 
-extern "C" int cips3d_nerf_bwd_fused_intr(const cips3d_nerf_bwd_fused_params* pp, float* dfocal, void* stream) {
+// dfocal NULL: no focal gradient (an argument, not a field: the params struct is embedded in the kernels' FusedArgs)
+extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, float* dfocal, void* stream) {
   if (!pp) return CIPS3D_E_BADARG;
   const cips3d_nerf_bwd_fused_params& P = *pp;
   const cips3d_nerf_bwd_geom& G = P.geom;
@@ -869,10 +870,6 @@ extern "C" int cips3d_nerf_bwd_fused_intr(const cips3d_nerf_bwd_fused_params* pp
     hipError_t e = hipMemsetAsync(dfocal, 0, sizeof(float) * B, st);
     if (e != hipSuccess) return (int)e;
   }
-  return cips3d_nerf_bwd_camera_intr(&G, a.dptsn, a.dvd, a.ddnorm, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, 1, P.dcam,
-                                     dfocal, st);                                   // (dcam: zeroed by the preparation launch)
-}
-
-extern "C" int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* pp, void* stream) {
-  return cips3d_nerf_bwd_fused_intr(pp, nullptr, stream);
+  return cips3d_nerf_bwd_camera(&G, a.dptsn, a.dvd, a.ddnorm, P.d_mask, P.d_xyz, P.xyz, a.wsum, a.wzsum, 1, P.dcam, dfocal,
+                                st);                                                // (dcam: zeroed by the preparation launch)
 }

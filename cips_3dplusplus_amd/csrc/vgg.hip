@@ -360,6 +360,3 @@ extern "C" int cips3d_vgg_loss_backward(const cips3d_vgg_ctx* ctx, const cips3d_
                      B, io->H, io->W, io->normalize);
   return cips3d_launch_status();
 }
-
-extern "C" int cips3d_sizeof_vgg_ctx(void) { return (int)sizeof(cips3d_vgg_ctx); }
-extern "C" int cips3d_sizeof_vgg_io(void) { return (int)sizeof(cips3d_vgg_io); }

@@ -487,6 +487,3 @@ extern "C" int cips3d_vgg_split_loss_backward(const cips3d_vgg_split_ctx* ctx, c
                      static_cast<const float*>(ctx->w_fwd[0]), io->dx, B, io->H, io->W, io->normalize);
   return cips3d_launch_status();
 }
-
-extern "C" int cips3d_sizeof_vgg_split_ctx(void) { return (int)sizeof(cips3d_vgg_split_ctx); }
-extern "C" int cips3d_sizeof_vgg_split_io(void) { return (int)sizeof(cips3d_vgg_split_io); }

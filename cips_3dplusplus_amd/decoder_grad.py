@@ -81,9 +81,6 @@ def parameters_of(dec):
 class GradPlan:
     def __init__(self, dec, B, H0, W0, device):
         from .decoder import StyledConv
-        lib = _lib.load()
-        if lib.cips3d_sizeof_grad_plan() != C.sizeof(DecoderGradPlan) or lib.cips3d_sizeof_grad_io() != C.sizeof(DecoderGradIO):
-            raise RuntimeError("cips3d_decoder_grad_plan / _io layout mismatch between python and the library")
         seq = dec._mod_layers()
         if dec.kernel_size != 1 or len(seq) > MAX_LAYERS or B > 4 or dec.style_dim % 4:
             raise Unsupported("kernel_size != 1, too many layers, batch > 4 or style_dim % 4")

@@ -120,10 +120,9 @@ def linear(x, W, bias=None, out=None, w_scale=1.0, b_scale=1.0, pixelnorm=False,
     return out
 
 
-# Bumped by everything that rewrites a module's style tables (FiLM table, modulation table: LinearTable.run, a full
-# ForwardPlan.run).  A forward with styles_resident=True (plan.py) is only valid while nothing did since its plan's last full run.
-# Bumped by everything that rewrites a module's style tables (FiLM table, decoder modulations): a forward plan's resident frame
-# (plan.run, styles_resident) checks that nothing has since its last full run.  One counter per LANE: the tables of lane k > 0 are
+# Bumped by everything that rewrites a module's style tables (FiLM table, decoder modulations: LinearTable.run, a full
+# ForwardPlan.run): a forward plan's resident frame (plan.run, styles_resident) is only valid while nothing has since the plan's
+# last full run, and checks that.  One counter per LANE: the tables of lane k > 0 are
 # private to the forward plans of that lane (Generator.forward on another stream, pipeline.ViewPipeline).
 import collections
 STYLE_EPOCHS = collections.defaultdict(int)
@@ -1343,7 +1342,7 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     d_mask [2,B,S,S] (d mask[0], d depth) and d_xyz [B,3,S,S]: the upstreams of the geometry maps, None = absent; d_mask needs
     `xyz`, the forward's [B,3,S,S] map.  They enter the compositing backward and the camera chain -- no further launch.
     d_focal=True (opt-in): d loss / d focals [B] is appended to the returned tuple -- the camera chain's second instantiation
-    (cips3d_nerf_bwd_camera_intr) and one [B] memset; False launches exactly what it did without the argument."""
+    (cips3d_nerf_bwd_camera with dfocal) and one [B] memset; False launches exactly what it did without the argument."""
     lib = _lib.load()
     st = stream_ptr()
     dev = cam_poses.device
@@ -1406,10 +1405,10 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     wsum, wzsum = (new(B, R), new(B, R)) if geo else (None, None)
     geo_ptrs = (dev_ptr(dm, "d_mask", True), dev_ptr(dx, "d_xyz", True), dev_ptr(xm, "xyz", True),
                 dev_ptr(wsum, "wsum", True), dev_ptr(wzsum, "wzsum", True))
-    check(lib.cips3d_nerf_bwd_composite_geo(gp, dev_ptr(sdf), dev_ptr(crgb), dev_ptr(g), dev_ptr(dth),
-                                            dev_ptr(sigmoid_beta, "sigmoid_beta", True),      # None: with_sdf = False
-                                            dev_ptr(wts), dev_ptr(Tb), dev_ptr(dsdf), dev_ptr(dcrgb), dev_ptr(ddnorm),
-                                            dev_ptr(dbeta_ray, "dbeta_ray", True), *geo_ptrs, st), "cips3d_nerf_bwd_composite_geo")
+    check(lib.cips3d_nerf_bwd_composite(gp, dev_ptr(sdf), dev_ptr(crgb), dev_ptr(g), dev_ptr(dth),
+                                        dev_ptr(sigmoid_beta, "sigmoid_beta", True),      # None: with_sdf = False
+                                        dev_ptr(wts), dev_ptr(Tb), dev_ptr(dsdf), dev_ptr(dcrgb), dev_ptr(ddnorm),
+                                        dev_ptr(dbeta_ray, "dbeta_ray", True), *geo_ptrs, st), "cips3d_nerf_bwd_composite")
 
     # ---- gradients of the renderer's own weights (optional): the wide blocks W_l [H,H] on the split-fp16 weight-gradient
     # GEMM (contraction over the points), everything narrow -- biases, the first layer, the view-direction columns, the heads
@@ -1473,16 +1472,11 @@ def nerf_backward(net, sigmoid_beta, cam_poses, focals, near, far, perturb_u, fi
     check(lib.cips3d_nerf_bwd_heads(dev_ptr(dpre), dev_ptr(w_first), 1, 3, None, 3, B, H, P, dev_ptr(dptsn), st),
           "cips3d_nerf_bwd_heads")
     dcam = new(B, 3, 4)
-    if d_focal:
-        dfoc = torch.zeros(B, device=dev)
-        check(lib.cips3d_nerf_bwd_camera_intr(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), *geo_ptrs, 0, dev_ptr(dcam),
-                                              dev_ptr(dfoc), st), "cips3d_nerf_bwd_camera_intr")
-        return (dfilm, dcam, pg, dfoc) if need_params else (dfilm, dcam, dfoc)
-    check(lib.cips3d_nerf_bwd_camera_geo(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), *geo_ptrs, 0, dev_ptr(dcam), st),
-          "cips3d_nerf_bwd_camera_geo")
-    if need_params:
-        return dfilm, dcam, pg
-    return dfilm, dcam
+    dfoc = torch.zeros(B, device=dev) if d_focal else None
+    check(lib.cips3d_nerf_bwd_camera(gp, dev_ptr(dptsn), dev_ptr(dvd_pt), dev_ptr(ddnorm), *geo_ptrs, 0, dev_ptr(dcam),
+                                     dev_ptr(dfoc, "dfocal", True), st), "cips3d_nerf_bwd_camera")
+    out = (dfilm, dcam, pg) if need_params else (dfilm, dcam)
+    return out + (dfoc,) if d_focal else out
 
 
 def nerf_pack_weights_t(w_hidden, w_view, packed, hidden, depth):
@@ -1559,12 +1553,9 @@ def nerf_backward_fused(net, sigmoid_beta, cam_poses, focals, near, far, perturb
     p.hidden, p.depth, p.n_chunks = H, D, n_chunks
     geo = _geo_upstreams(d_mask, d_xyz, xyz, B, R)          # (held until the call is enqueued)
     p.d_mask, p.d_xyz, p.xyz = (dev_ptr(t, "geometry upstream", True) for t in geo)
-    if d_focal:
-        dfoc = torch.empty(B, device=dev)                   # (cleared by the call)
-        check(lib.cips3d_nerf_bwd_fused_intr(C.byref(p), dev_ptr(dfoc), stream_ptr()), "cips3d_nerf_bwd_fused_intr")
-        return dfilm, dcam, dfoc
-    check(lib.cips3d_nerf_bwd_fused(C.byref(p), stream_ptr()), "cips3d_nerf_bwd_fused")
-    return dfilm, dcam
+    dfoc = torch.empty(B, device=dev) if d_focal else None  # (cleared by the call)
+    check(lib.cips3d_nerf_bwd_fused(C.byref(p), dev_ptr(dfoc, "dfocal", True), stream_ptr()), "cips3d_nerf_bwd_fused")
+    return (dfilm, dcam, dfoc) if d_focal else (dfilm, dcam)
 
 
 def inversion_roofline(renderer, B, n_samples, img_size=64, iters=10):

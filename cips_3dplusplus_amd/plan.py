@@ -92,8 +92,6 @@ class ForwardPlan:
         forwards issued on different streams (Generator.forward keys its plans by the current stream) can be in flight together."""
         lib = _lib.load()
         self.lane = lane
-        if lib.cips3d_sizeof_plan() != C.sizeof(GeneratorPlan) or lib.cips3d_sizeof_io() != C.sizeof(ForwardIO):
-            raise RuntimeError("cips3d_generator_plan / cips3d_forward_io layout mismatch between python and the library")
         dev = G.renderer.sigmoid_beta.device
         ren, dec = G.renderer, G.decoder
         D, H = ren.N_layers_renderer, ren.hidden_dim

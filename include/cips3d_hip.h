@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 47 /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 48 /* bumped with every change of an entry point or of a struct layout below */
+/* 48: cips3d_nerf_bwd_composite, cips3d_nerf_bwd_camera and cips3d_nerf_bwd_fused CHANGED SIGNATURE (each took the argument list
+ * of its former superset, whose name is gone); the per-struct cips3d_sizeof_* functions are gone, cips3d_sizeof_struct covers
+ * every struct.  A binding written against 47 must be updated: check cips3d_abi_version() before the first call. */
 
 #define CIPS3D_E_BADARG   (-1)   /* null pointer / non-positive size */
 #define CIPS3D_E_UNSUPP   (-2)   /* configuration outside what the kernels implement */
@@ -848,13 +851,14 @@ int cips3d_planes_torgb_blocks(int Cout);
  * CIPS3D_STYLE_PHASE=1: the one launch measured slower on MI355X.  Both modes give bit-identical
  * results. */
 int cips3d_style_phase(const cips3d_generator_plan* plan, const cips3d_forward_io* io, int mode, void* stream);
-/* sizeof() of the two structs as the library sees them (layout check for foreign-language bindings) */
-int64_t cips3d_sizeof_plan(void);
-int64_t cips3d_sizeof_io(void);
-/* sizeof() of every struct that crosses the boundary (a binding checks its own layout against these at load time):
+/* sizeof() of every struct this header declares (a binding checks its own layout against these at load time):
  * which = 0 cips3d_generator_plan, 1 cips3d_forward_io, 2 cips3d_nerf_params, 3 cips3d_linear_desc,
- * 4 cips3d_modulate_desc, 5 cips3d_dec_layer, 6 cips3d_nerf_bwd_geom, 7 cips3d_nerf_bwd_fused_params;
- * -1 for an unknown index */
+ * 4 cips3d_modulate_desc, 5 cips3d_dec_layer, 6 cips3d_nerf_bwd_geom, 7 cips3d_nerf_bwd_fused_params, 8 cips3d_range,
+ * 9 cips3d_reduce_job, 10 cips3d_normals_params, 11 cips3d_mesh_resolve_params, 12 cips3d_vgg_ctx, 13 cips3d_vgg_io,
+ * 14 cips3d_vgg_split_ctx, 15 cips3d_vgg_split_io, 16 cips3d_lpips_io, 17 cips3d_dec_route_opts, 18 cips3d_dec_step,
+ * 19 cips3d_mesh_color_params, 20 cips3d_mesh_texture_params, 21 cips3d_stage_geom, 22 cips3d_actbwd, 23 cips3d_slot_job,
+ * 24 cips3d_modbwd_desc, 25 cips3d_adam_entry, 26 cips3d_adam_hyper, 27 cips3d_noise_buf, 28 cips3d_grad_layer,
+ * 29 cips3d_decoder_grad_plan, 30 cips3d_decoder_grad_io; -1 for an unknown index */
 int64_t cips3d_sizeof_struct(int which);
 
 /* ------------------------------------------------------------------ stand-alone renderer steps
@@ -1121,8 +1125,6 @@ typedef struct cips3d_decoder_grad_io {
 } cips3d_decoder_grad_io;
 int cips3d_decoder_grad_forward(const cips3d_decoder_grad_plan* plan, const cips3d_decoder_grad_io* io, void* stream);
 int cips3d_decoder_grad_backward(const cips3d_decoder_grad_plan* plan, const cips3d_decoder_grad_io* io, void* stream);
-int cips3d_sizeof_grad_plan(void);
-int cips3d_sizeof_grad_io(void);
 
 /* The same contraction on split-fp16 products (three fp16 MFMA products per fp32 product).  dy_amax / x_amax: the measured
  * per-sample maxima of the operands ([B][CIPS3D_AMAX_FLOATS] slot arrays as cips3d_range uses them, or NULL: unscaled split,
@@ -1173,21 +1175,19 @@ int cips3d_nerf_bwd_dot(const float* dF, const float* f, int B, int H, int R, in
 /* volume integration forward + backward per ray: sdf [B,P], crgb [B,3,P] (rgb logits), g [B,P], dthumb [B,3,R]
  * -> w [B,P] (compositing weights), dsdf [B,P], dcrgb [B,3,P], ddnorm [B,R] (d loss / d |rays_d|, which scales the
  * sample spacing); T_scratch [B,P].  sigmoid_beta == NULL: with_sdf = False -- `sdf` is the raw density, sigma = softplus(sdf)
- * (cips3d/nerf_utils.py:288-297); no dbeta_ray then. */
-int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* geom, const float* sdf, const float* crgb, const float* g,
-                              const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch, float* dsdf,
-                              float* dcrgb, float* ddnorm, float* dbeta_ray, void* stream);
-/* (dbeta_ray [B,R] or NULL: per-ray d loss / d sigmoid_beta, for `optim_render_params`, models/projector_v10.py:848-872)
- * The same with the upstreams of the geometry maps of Render.volume_integration (cips3d/nerf_utils.py:329-336: xyz = sum_k w_k p_k,
+ * (cips3d/nerf_utils.py:288-297); no dbeta_ray then.  dbeta_ray [B,R] or NULL: per-ray d loss / d sigmoid_beta, for
+ * `optim_render_params`, models/projector_v10.py:848-872.
+ * The upstreams of the geometry maps of Render.volume_integration (cips3d/nerf_utils.py:329-336: xyz = sum_k w_k p_k,
  * mask[0] = w_{N-1}, mask[1] = depth = -|xyz|): d_mask [2,B,R] (planar: d mask[0], then d depth) and d_xyz [B,3,R], each may be
  * NULL; xyz [B,3,R] is the forward's map (needed with d_mask: d depth acts as -d_depth * xyz / |xyz| on xyz, 0 where |xyz| == 0).
  * With xbar the effective adjoint of xyz, d loss / d w_k gains <xbar, p_k> + [k == N-1] d mask[0], p_k = o + z_k d in world
- * units; the per-ray sums wsum = sum_k w_k and wzsum = sum_k w_k z_k [B,R] (written when d_mask or d_xyz is set) carry the direct
- * path through the points to cips3d_nerf_bwd_camera_geo.  Both NULL: exactly cips3d_nerf_bwd_composite. */
-int cips3d_nerf_bwd_composite_geo(const cips3d_nerf_bwd_geom* geom, const float* sdf, const float* crgb, const float* g,
-                                  const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch, float* dsdf,
-                                  float* dcrgb, float* ddnorm, float* dbeta_ray, const float* d_mask, const float* d_xyz,
-                                  const float* xyz, float* wsum, float* wzsum, void* stream);
+ * units; the per-ray sums wsum = sum_k w_k and wzsum = sum_k w_k z_k [B,R] (needed and written when d_mask or d_xyz is set, else
+ * NULL) carry the direct path through the points to cips3d_nerf_bwd_camera.  d_mask and d_xyz both NULL: the compositing
+ * backward of the features and the thumbnail alone. */
+int cips3d_nerf_bwd_composite(const cips3d_nerf_bwd_geom* geom, const float* sdf, const float* crgb, const float* g,
+                              const float* dthumb, const float* sigmoid_beta, float* w, float* T_scratch, float* dsdf,
+                              float* dcrgb, float* ddnorm, float* dbeta_ray, const float* d_mask, const float* d_xyz,
+                              const float* xyz, float* wsum, float* wzsum, void* stream);
 /* out[row][c] += sum_{b,p} a[b][row][p] * x[b][c][p mod Px] (c < nx <= 3), out[row][3] += sum_{b,p} a[b][row][p]; a [B,rows,P],
  * x [B,nx,Px], out [rows,4] zeroed by the caller: the narrow weight gradients and the biases of the point MLP. */
 int cips3d_nerf_bwd_row_dots(const float* a, const float* x, int nx, int64_t Px, float* out, int B, int rows, int64_t P,
@@ -1200,25 +1200,18 @@ int cips3d_nerf_bwd_film_grad(float* buf, const float* pre, const float* film, i
                               const float* w_sigma, const float* dsdf, const float* weights, const float* dF,
                               const float* w_rgb, const float* dcrgb, float* dfilm, int B, int H, int R, int64_t P,
                               void* stream);
-/* dptsn [B,3,P], dvd_pt [B,3,P] (d loss / d viewdir per point), ddnorm [B,R] -> dcam [B,3,4] */
+/* dptsn [B,3,P], dvd_pt [B,3,P] (d loss / d viewdir per point), ddnorm [B,R] -> dcam [B,3,4].  accumulate == 0: dcam is
+ * cleared by the call; != 0: ADDED to a dcam the caller has zeroed (cips3d_nerf_bwd_fused clears it in its preparation launch).
+ * The direct path of the geometry maps: d o += wsum xbar, d d += wzsum xbar per ray (d_mask, d_xyz, xyz, wsum, wzsum as in
+ * cips3d_nerf_bwd_composite; d_mask and d_xyz both NULL: none).
+ * The gradient of the intrinsics: dfocal [B] (zeroed by the caller; NULL: none, the kernel's instantiation without the focal
+ * sum) += d loss / d focals.  The ray's camera-frame direction is (dcx, dcy, -1) with dcx, dcy ~ 1 / focal, so d focal =
+ * -sum_rays (g_cam[0] dcx + g_cam[1] dcy) / focal with g_cam = R^T d rays_d, plus -- with static_viewdirs, where the view
+ * direction is normalize(d_cam) and does not pass through the pose -- the view direction's own adjoint.  near / far /
+ * perturb_u stay constants. */
 int cips3d_nerf_bwd_camera(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
-                           float* dcam, void* stream);
-/* the same, ADDED to a dcam the caller has zeroed (cips3d_nerf_bwd_fused clears it in its preparation launch) */
-int cips3d_nerf_bwd_camera_acc(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
-                               float* dcam, void* stream);
-/* the two above with the direct path of the geometry maps: d o += wsum xbar, d d += wzsum xbar per ray (d_mask, d_xyz, xyz, wsum,
- * wzsum as in cips3d_nerf_bwd_composite_geo; d_mask and d_xyz both NULL: none).  accumulate != 0: dcam is added to. */
-int cips3d_nerf_bwd_camera_geo(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
-                               const float* d_mask, const float* d_xyz, const float* xyz, const float* wsum, const float* wzsum,
-                               int accumulate, float* dcam, void* stream);
-/* cips3d_nerf_bwd_camera_geo with the gradient of the intrinsics: dfocal [B] (zeroed by the caller; NULL: exactly
- * cips3d_nerf_bwd_camera_geo, the same kernel) += d loss / d focals.  The ray's camera-frame direction is (dcx, dcy, -1) with
- * dcx, dcy ~ 1 / focal, so d focal = -sum_rays (g_cam[0] dcx + g_cam[1] dcy) / focal with g_cam = R^T d rays_d, plus -- with
- * static_viewdirs, where the view direction is normalize(d_cam) and does not pass through the pose -- the view direction's
- * own adjoint.  A second instantiation of the same kernel; near / far / perturb_u stay constants. */
-int cips3d_nerf_bwd_camera_intr(const cips3d_nerf_bwd_geom* geom, const float* dptsn, const float* dvd_pt, const float* ddnorm,
-                                const float* d_mask, const float* d_xyz, const float* xyz, const float* wsum, const float* wzsum,
-                                int accumulate, float* dcam, float* dfocal, void* stream);
+                           const float* d_mask, const float* d_xyz, const float* xyz, const float* wsum, const float* wzsum,
+                           int accumulate, float* dcam, float* dfocal, void* stream);
 /* ---- NeRF half, fused backward (csrc/nerf_bwd_fused.hip): the same gradients as the sequence above -- d loss / d film
  * [B,L,2,H] and d loss / d cam_poses [B,3,4] from d_features [B,H,R] and d_thumb [B,3,R] -- with the point MLP kept in the
  * register file in both directions (the reference gets them from autograd through cips3d/volume_renderer.py:39-160 and
@@ -1260,7 +1253,7 @@ typedef struct cips3d_nerf_bwd_fused_params {
    * only g = <d_features, feature> is then rebuilt, from the view layer's stash. */
   const float* fwd_sdf;      /* [B,P] */
   const float* fwd_crgb;     /* [B,3,P] */
-  /* upstreams of the mask / depth and xyz maps (cips3d_nerf_bwd_composite_geo); each may be NULL, xyz is needed with d_mask */
+  /* upstreams of the mask / depth and xyz maps (cips3d_nerf_bwd_composite); each may be NULL, xyz is needed with d_mask */
   const float* d_mask;       /* [2,B,R] */
   const float* d_xyz;        /* [B,3,R] */
   const float* xyz;          /* [B,3,R]: the forward's map */
@@ -1275,11 +1268,10 @@ int64_t cips3d_nerf_bwd_fused_scratch_floats(int B, int img_size, int n_samples,
  * `packed`); packed_t holds cips3d_nerf_packed_floats(hidden, depth) floats */
 int cips3d_nerf_pack_weights_t(const float* w_hidden, const float* w_view, const float* packed, float* packed_t, int hidden,
                                int depth, void* stream);
-int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* p, void* stream);
-/* The same with the gradient of the intrinsics: dfocal [B] (out; cleared by the call) = d loss / d focals, from
- * cips3d_nerf_bwd_camera_intr at the end of the call.  NULL: exactly cips3d_nerf_bwd_fused -- the same launches.  (An argument,
- * not a field: cips3d_nerf_bwd_fused_params keeps its layout.) */
-int cips3d_nerf_bwd_fused_intr(const cips3d_nerf_bwd_fused_params* p, float* dfocal, void* stream);
+/* The fused backward.  dfocal [B] (out; cleared by the call) = d loss / d focals, from cips3d_nerf_bwd_camera at the end of the
+ * call; NULL: none, and no launch or memset on its behalf.  (An argument, not a field: cips3d_nerf_bwd_fused_params is embedded
+ * in the kernels' arguments and keeps its layout.) */
+int cips3d_nerf_bwd_fused(const cips3d_nerf_bwd_fused_params* p, float* dfocal, void* stream);
 
 /* Backward of cips3d_camera_params w.r.t. locations (azim, elev): dextrinsics [B,3,4] -> dlocations [B,2]
  * (cips3d/nerf_utils.py:344-436,466-564; focal / near / far do not depend on the angles). */
@@ -1551,8 +1543,6 @@ int cips3d_vgg_pack(const cips3d_vgg_ctx* ctx, const float* const* weights, int 
 int cips3d_vgg_features(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
 int cips3d_vgg_loss_forward(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
 int cips3d_vgg_loss_backward(const cips3d_vgg_ctx* ctx, const cips3d_vgg_io* io, void* stream);
-int cips3d_sizeof_vgg_ctx(void);
-int cips3d_sizeof_vgg_io(void);
 
 /* The same loss with convs 1 .. 12 and their data gradients on split-fp16 products (csrc/vgg_split.hip): w x = w_lo x_hi +
  * w_hi x_lo + w_hi x_hi on v_mfma_f32_16x16x32_f16 with fp32 accumulation -- fp32-accurate, not bit-equal to the exact form
@@ -1584,8 +1574,6 @@ int cips3d_vgg_split_pack(const cips3d_vgg_split_ctx* ctx, const float* const* w
 int cips3d_vgg_split_features(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
 int cips3d_vgg_split_loss_forward(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
 int cips3d_vgg_split_loss_backward(const cips3d_vgg_split_ctx* ctx, const cips3d_vgg_split_io* io, void* stream);
-int cips3d_sizeof_vgg_split_ctx(void);
-int cips3d_sizeof_vgg_split_io(void);
 
 /* PSNR and SSIM of image pairs on the device (csrc/metrics.hip): scikit-image's peak_signal_noise_ratio and
  * structural_similarity at their defaults on 8-bit images (data range 255; win_size 7, uniform window, K1 = 0.01, K2 = 0.03,
@@ -1647,7 +1635,6 @@ int cips3d_lpips_head(const float* za, const float* zb, const float* lin, int B,
                       double* mean, void* stream);
 int cips3d_lpips(const cips3d_vgg_ctx* ctx, const cips3d_lpips_io* io, void* stream);
 int cips3d_lpips_split(const cips3d_vgg_split_ctx* ctx, const cips3d_lpips_io* io, void* stream);
-int cips3d_sizeof_lpips_io(void);
 
 /* Gaussian-window SSIM of fp32 image pairs as a differentiable loss (csrc/ssim_loss.hip): Wang et al. 2004, which is scikit-image's
  * structural_similarity(gaussian_weights = True, sigma = 1.5, use_sample_covariance = False, data_range = R).  a, b [B,C,H,W]

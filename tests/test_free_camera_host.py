@@ -17,8 +17,8 @@ from oracle import path as O
 import _free_camera_cases as FC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY_POINTS = ("cips3d_camera_axis_angle", "cips3d_camera_axis_angle_bwd", "cips3d_nerf_bwd_camera_intr",
-                "cips3d_nerf_bwd_fused_intr")
+ENTRY_POINTS = ("cips3d_camera_axis_angle", "cips3d_camera_axis_angle_bwd", "cips3d_nerf_bwd_camera",
+                "cips3d_nerf_bwd_fused")
 
 
 def test_abi_exports_and_version():
@@ -29,8 +29,8 @@ def test_abi_exports_and_version():
         assert s in _lib.EXPORTED and s in _lib._SIGS and hasattr(raw, s), s
         assert re.search(r"\b%s\(" % s, header), s
     m = re.search(r"#define\s+CIPS3D_ABI_VERSION\s+(\d+)", header)
-    assert lib.cips3d_abi_version() == int(m.group(1)) == _lib.ABI_VERSION >= 47
-    # the focal gradient of the fused route is an argument of a new entry point: the params struct keeps its layout
+    assert lib.cips3d_abi_version() == int(m.group(1)) == _lib.ABI_VERSION >= 48
+    # the focal gradient of the fused route is an argument of the entry point: the params struct keeps its layout
     assert lib.cips3d_sizeof_struct(7) == ctypes.sizeof(_lib.NerfBwdFusedParams)
     assert "camera_free.hip" in build.SOURCES
 
@@ -58,7 +58,7 @@ def test_library_refuses_bad_arguments_without_a_device():
     geom.cam_poses = geom.focals = geom.near_ = geom.far_ = one
     geom.B, geom.img_size, geom.n_samples, geom.static_viewdirs = 1, 2, 4, 0
     gp = ctypes.byref(geom)
-    cam = lib.cips3d_nerf_bwd_camera_intr
+    cam = lib.cips3d_nerf_bwd_camera                                                    # (dfocal non-null throughout)
     assert cam(None, one, one, one, None, None, None, None, None, 0, one, one, None) == -1
     assert cam(gp, one, one, one, None, None, None, None, None, 0, None, one, None) == -1      # no dcam
     assert cam(gp, one, one, one, one, None, None, one, one, 0, one, one, None) == -1          # d_mask without xyz
@@ -66,8 +66,8 @@ def test_library_refuses_bad_arguments_without_a_device():
     assert cam(gp, one, one, one, None, None, None, None, None, 0, one, one, None) == -1
     geom.B = 0
     assert cam(gp, one, one, one, None, None, None, None, None, 1, one, one, None) == 0
-    assert lib.cips3d_nerf_bwd_fused_intr(None, one, None) == -1
-    assert lib.cips3d_nerf_bwd_fused_intr(ctypes.byref(_lib.NerfBwdFusedParams()), one, None) == -1
+    assert lib.cips3d_nerf_bwd_fused(None, one, None) == -1
+    assert lib.cips3d_nerf_bwd_fused(ctypes.byref(_lib.NerfBwdFusedParams()), one, None) == -1
 
 
 def test_default_surfaces_are_unchanged():

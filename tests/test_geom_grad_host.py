@@ -1,5 +1,5 @@
-"""Host checks of the gradient through the render's mask / depth / xyz maps and of the silhouette term (csrc/nerf_bwd.hip's
-`_geo` entry points, projector.silhouette_loss, project_wplus's `silhouette_weight` / `target_masks`): the C ABI's declarations
+"""Host checks of the gradient through the render's mask / depth / xyz maps and of the silhouette term (the geometry
+arguments of csrc/nerf_bwd.hip's compositing and camera entry points, projector.silhouette_loss, project_wplus's `silhouette_weight` / `target_masks`): the C ABI's declarations
 and argument checks, the knobs' defaults and errors, and the CPU route of the loss.  Nothing here launches a kernel."""
 import ctypes
 import inspect
@@ -13,7 +13,7 @@ import torch.nn.functional as F
 from cips_3dplusplus_amd import _lib, projector as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY_POINTS = ("cips3d_nerf_bwd_composite_geo", "cips3d_nerf_bwd_camera_geo")
+ENTRY_POINTS = ("cips3d_nerf_bwd_composite", "cips3d_nerf_bwd_camera")
 
 
 def test_abi_exports_and_version():
@@ -43,18 +43,18 @@ def test_library_refuses_incomplete_geometry_arguments():
     geom.B, geom.img_size, geom.n_samples, geom.static_viewdirs = 1, 2, 4, 0
     gp = ctypes.byref(geom)
     req = [one] * 10                                                                    # sdf .. ddnorm
-    comp = lib.cips3d_nerf_bwd_composite_geo
+    comp = lib.cips3d_nerf_bwd_composite
     assert comp(None, *req, None, None, None, None, None, None, None) != 0
     assert comp(gp, *req, None, one, None, None, one, one, None) != 0                   # d_mask without xyz
     assert comp(gp, *req, None, None, one, None, None, None, None) != 0                 # d_xyz without wsum / wzsum
     assert comp(gp, *req, None, one, one, one, one, None, None) != 0                    # ... without wzsum
-    cam = lib.cips3d_nerf_bwd_camera_geo
-    assert cam(gp, one, one, one, one, None, None, one, one, 0, one, None) != 0         # d_mask without xyz
-    assert cam(gp, one, one, one, None, one, None, None, None, 1, one, None) != 0       # d_xyz without the sums
-    assert cam(gp, one, one, one, None, None, None, None, None, 0, None, None) != 0     # no dcam
+    cam = lib.cips3d_nerf_bwd_camera                                                    # (dfocal = None throughout)
+    assert cam(gp, one, one, one, one, None, None, one, one, 0, one, None, None) != 0   # d_mask without xyz
+    assert cam(gp, one, one, one, None, one, None, None, None, 1, one, None, None) != 0 # d_xyz without the sums
+    assert cam(gp, one, one, one, None, None, None, None, None, 0, None, None, None) != 0  # no dcam
     geom.B = 0                                                                          # an empty batch is a no-op
     assert comp(gp, *req, None, one, one, one, one, one, None) == 0
-    assert cam(gp, one, one, one, one, one, one, one, one, 1, one, None) == 0
+    assert cam(gp, one, one, one, one, one, one, one, one, 1, one, None, None) == 0
 
 
 def test_project_wplus_has_the_silhouette_keywords():

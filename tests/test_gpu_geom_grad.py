@@ -1,5 +1,5 @@
-"""The gradient through the render's mask / depth / xyz maps (autograd.NerfRenderFn; cips3d_nerf_bwd_composite_geo and
-cips3d_nerf_bwd_camera_geo of csrc/nerf_bwd.hip, reached by the fused and by the materialised backward) and the silhouette term
+"""The gradient through the render's mask / depth / xyz maps (autograd.NerfRenderFn; cips3d_nerf_bwd_composite and
+cips3d_nerf_bwd_camera of csrc/nerf_bwd.hip, reached by the fused and by the materialised backward) and the silhouette term
 of the inversion loop, against torch autograd through the CPU oracle's volume_integration (oracle/path.py:150-171:
 xyz = sum_k w_k p_k, mask = [w_last, -|xyz|]).  The harness is that of test_gpu_backward.py::test_nerf_render_bwd_vs_oracle."""
 import ctypes
@@ -206,10 +206,10 @@ def test_depth_gradient_of_a_ray_composited_to_the_origin(N):
               ("wzsum", (B, R)))}
         geo = (d_mask.data_ptr(), None, xyz.data_ptr(), o["wsum"].data_ptr(), o["wzsum"].data_ptr()) if with_depth \
             else (None,) * 5
-        _lib.check(lib.cips3d_nerf_bwd_composite_geo(
+        _lib.check(lib.cips3d_nerf_bwd_composite(
             ctypes.byref(geom), sdf.data_ptr(), crgb.data_ptr(), g.data_ptr(), dth.data_ptr(),
             beta.data_ptr(), o["w"].data_ptr(), o["T"].data_ptr(), o["dsdf"].data_ptr(), o["dcrgb"].data_ptr(),
-            o["ddnorm"].data_ptr(), None, *geo, hip.stream_ptr()), "cips3d_nerf_bwd_composite_geo")
+            o["ddnorm"].data_ptr(), None, *geo, hip.stream_ptr()), "cips3d_nerf_bwd_composite")
         torch.cuda.synchronize()
         return o
 

@@ -37,6 +37,51 @@ def test_library_builds_and_exports_header_symbols():
     assert b"bad argument" in lib.cips3d_strerror(-1)
 
 
+def test_every_struct_of_the_header_has_a_row_in_the_layout_table():
+    """A struct added to the header without a row of cips3d_sizeof_struct / _lib._struct_rows() would cross the boundary
+    unchecked: the table's C names are exactly the header's typedefs, one row each, and each row's size is the library's."""
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "cips3d_hip.h")).read()
+    declared = re.findall(r"^typedef struct (cips3d_\w+)", header, flags=re.M)
+    rows = _lib._struct_rows()
+    names = [n for n, _ in rows]
+    assert len(declared) == len(set(declared)) >= 31 and len(names) == len(set(names))
+    assert set(names) == set(declared)
+    for name in declared:                                   # the closing name of each typedef is its opening one
+        assert re.search(r"\}\s*%s;" % name, header), name
+    assert list(_lib._struct_table().items()) == [(k, st) for k, (_, st) in enumerate(rows)]
+    for k, (name, st) in enumerate(rows):
+        assert lib.cips3d_sizeof_struct(k) == ctypes.sizeof(st) > 0, name
+    assert lib.cips3d_sizeof_struct(len(rows)) == -1        # no row of the library without one here
+    # rows that tests and INTEGRATION.md cite by index keep it
+    assert names[:8] == ["cips3d_generator_plan", "cips3d_forward_io", "cips3d_nerf_params", "cips3d_linear_desc",
+                         "cips3d_modulate_desc", "cips3d_dec_layer", "cips3d_nerf_bwd_geom", "cips3d_nerf_bwd_fused_params"]
+    assert names[12:17] == ["cips3d_vgg_ctx", "cips3d_vgg_io", "cips3d_vgg_split_ctx", "cips3d_vgg_split_io", "cips3d_lpips_io"]
+    assert names[21] == "cips3d_stage_geom" and names[29:] == ["cips3d_decoder_grad_plan", "cips3d_decoder_grad_io"]
+
+
+RETIRED = ("cips3d_nerf_bwd_composite_geo", "cips3d_nerf_bwd_camera_acc", "cips3d_nerf_bwd_camera_geo",
+           "cips3d_nerf_bwd_camera_intr", "cips3d_nerf_bwd_fused_intr", "cips3d_sizeof_plan", "cips3d_sizeof_io",
+           "cips3d_sizeof_grad_plan", "cips3d_sizeof_grad_io", "cips3d_sizeof_vgg_ctx", "cips3d_sizeof_vgg_io",
+           "cips3d_sizeof_vgg_split_ctx", "cips3d_sizeof_vgg_split_io", "cips3d_sizeof_lpips_io")
+
+
+def test_retired_entry_points_are_gone_everywhere():
+    """ABI 48 folded each wrapper into its superset and the per-struct sizeof functions into cips3d_sizeof_struct: none of
+    the 14 names is exported by the library, declared in the header or bound."""
+    _lib.load()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    header = open(os.path.join(ROOT, "include", "cips3d_hip.h")).read()
+    assert len(set(RETIRED)) == 14
+    for name in RETIRED:
+        assert not hasattr(raw, name), name
+        assert not re.search(r"\b%s\b" % name, header), name
+        assert name not in _lib._SIGS and name not in _lib.EXPORTED, name
+    # the survivors carry the full argument lists
+    assert len(_lib._SIGS["cips3d_nerf_bwd_composite"][1]) == 18 and len(_lib._SIGS["cips3d_nerf_bwd_camera"][1]) == 13
+    assert len(_lib._SIGS["cips3d_nerf_bwd_fused"][1]) == 3
+
+
 def test_argument_errors_do_not_launch():
     lib = _lib.load()
     assert lib.cips3d_fused_bias_act(None, None, None, None, 16, 1, 1, 3, 0, 0.2, 1.0, None) == -1
@@ -148,7 +193,9 @@ def test_decoder_grad_plan_layout(res, D, B, S0, monkeypatch):
     # (layout only, nothing is launched: the binding's CUDA-tensor guard is lifted for the table builder)
     monkeypatch.setattr(hip, "dev_ptr", lambda t, name="", optional=False, **kw: None if t is None else t.data_ptr())
     lib = _lib.load()
-    assert lib.cips3d_sizeof_grad_plan() == C.sizeof(dg.DecoderGradPlan) and lib.cips3d_sizeof_grad_io() == C.sizeof(dg.DecoderGradIO)
+    table = _lib._struct_table()
+    assert table[29] is dg.DecoderGradPlan and table[30] is dg.DecoderGradIO
+    assert lib.cips3d_sizeof_struct(29) == C.sizeof(dg.DecoderGradPlan) and lib.cips3d_sizeof_struct(30) == C.sizeof(dg.DecoderGradIO)
     cfg = configs.ffhq_G_cfg(res, D)
     dec = Decoder(style_dim=cfg["mapping_decoder_cfg"]["style_dim"], **cfg["decoder_cfg"])
     plan = dg.GradPlan(dec, B, S0, S0, "cpu")

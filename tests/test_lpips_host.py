@@ -15,7 +15,7 @@ from cips_3dplusplus_amd import _lib, perceptual as PP, projector as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("cips3d_lpips_head", "cips3d_lpips", "cips3d_lpips_split", "cips3d_lpips_supported",
-                "cips3d_lpips_partial_bytes", "cips3d_sizeof_lpips_io")
+                "cips3d_lpips_partial_bytes")
 
 
 def test_entry_points_are_declared_and_exported():
@@ -33,7 +33,7 @@ def test_entry_points_are_declared_and_exported():
 
 def test_struct_sizes_agree():
     lib = _lib.load()
-    assert lib.cips3d_sizeof_lpips_io() == ctypes.sizeof(_lib.LpipsIO) == lib.cips3d_sizeof_struct(16)
+    assert ctypes.sizeof(_lib.LpipsIO) == lib.cips3d_sizeof_struct(16)
     assert _lib._struct_table()[16] is _lib.LpipsIO
     assert int(re.search(r"#define\s+CIPS3D_LPIPS_LAYERS\s+(\d+)",
                          open(os.path.join(ROOT, "include", "cips3d_hip.h")).read()).group(1)) == _lib.LPIPS_LAYERS == 5

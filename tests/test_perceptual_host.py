@@ -13,7 +13,7 @@ from cips_3dplusplus_amd.perceptual import VGG16ConvLoss
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("cips3d_vgg_supported", "cips3d_vgg_channels", "cips3d_vgg_stride", "cips3d_vgg_partial_bytes", "cips3d_vgg_pack",
-       "cips3d_vgg_features", "cips3d_vgg_loss_forward", "cips3d_vgg_loss_backward", "cips3d_sizeof_vgg_ctx", "cips3d_sizeof_vgg_io")
+       "cips3d_vgg_features", "cips3d_vgg_loss_forward", "cips3d_vgg_loss_backward")
 
 
 def test_new_symbols_and_abi_version():
@@ -25,8 +25,8 @@ def test_new_symbols_and_abi_version():
         assert s in _lib.EXPORTED and hasattr(raw, s), s
     m = re.search(r"#define\s+CIPS3D_ABI_VERSION\s+(\d+)", header)
     assert lib.cips3d_abi_version() == int(m.group(1)) == _lib.ABI_VERSION >= 35
-    assert lib.cips3d_sizeof_vgg_ctx() == ctypes.sizeof(_lib.VggCtx) == lib.cips3d_sizeof_struct(12)
-    assert lib.cips3d_sizeof_vgg_io() == ctypes.sizeof(_lib.VggIO) == lib.cips3d_sizeof_struct(13)
+    assert ctypes.sizeof(_lib.VggCtx) == lib.cips3d_sizeof_struct(12)
+    assert ctypes.sizeof(_lib.VggIO) == lib.cips3d_sizeof_struct(13)
     assert int(re.search(r"#define\s+CIPS3D_VGG_CONVS\s+(\d+)", header).group(1)) == _lib.VGG_CONVS == 13
     assert [lib.cips3d_vgg_channels(l) for l in range(13)] == list(perceptual.CHANNELS) == list(PC.CHANNELS)
     assert [lib.cips3d_vgg_stride(l) for l in range(13)] == [1, 1, 2, 2, 4, 4, 4, 8, 8, 8, 16, 16, 16]

@@ -16,8 +16,7 @@ from cips_3dplusplus_amd.perceptual import VGG16ConvLoss
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("cips3d_vgg_split_supported", "cips3d_vgg_split_range_bytes", "cips3d_vgg_split_pack", "cips3d_vgg_split_features",
-       "cips3d_vgg_split_loss_forward", "cips3d_vgg_split_loss_backward", "cips3d_sizeof_vgg_split_ctx",
-       "cips3d_sizeof_vgg_split_io")
+       "cips3d_vgg_split_loss_forward", "cips3d_vgg_split_loss_backward")
 
 
 def test_new_symbols_sizes_and_abi_version():
@@ -29,11 +28,11 @@ def test_new_symbols_sizes_and_abi_version():
         assert s in _lib.EXPORTED and hasattr(raw, s), s
     m = re.search(r"#define\s+CIPS3D_ABI_VERSION\s+(\d+)", header)
     assert lib.cips3d_abi_version() == int(m.group(1)) == _lib.ABI_VERSION >= 36
-    assert lib.cips3d_sizeof_vgg_split_ctx() == ctypes.sizeof(_lib.VggSplitCtx) == lib.cips3d_sizeof_struct(14)
-    assert lib.cips3d_sizeof_vgg_split_io() == ctypes.sizeof(_lib.VggSplitIO) == lib.cips3d_sizeof_struct(15)
+    assert ctypes.sizeof(_lib.VggSplitCtx) == lib.cips3d_sizeof_struct(14)
+    assert ctypes.sizeof(_lib.VggSplitIO) == lib.cips3d_sizeof_struct(15)
     # the existing structs keep their sizes and ids
-    assert lib.cips3d_sizeof_vgg_ctx() == ctypes.sizeof(_lib.VggCtx) == lib.cips3d_sizeof_struct(12)
-    assert lib.cips3d_sizeof_vgg_io() == ctypes.sizeof(_lib.VggIO) == lib.cips3d_sizeof_struct(13)
+    assert ctypes.sizeof(_lib.VggCtx) == lib.cips3d_sizeof_struct(12)
+    assert ctypes.sizeof(_lib.VggIO) == lib.cips3d_sizeof_struct(13)
     # one word per (tensor, sample), activations and gradients
     assert lib.cips3d_vgg_split_range_bytes(1) == 2 * 13 * 4 and lib.cips3d_vgg_split_range_bytes(3) == 2 * 13 * 3 * 4
     assert lib.cips3d_vgg_split_range_bytes(0) == -1
