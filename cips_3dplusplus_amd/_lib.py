@@ -227,6 +227,10 @@ _SIGS = {
     "cips3d_nerf_fuses_finish": (c_int, [C.POINTER(NerfParams)]),
     "cips3d_nerf_sdf_grad": (c_int, [C.POINTER(NerfParams), c_f32p, C.c_void_p]),
     "cips3d_nerf_sdf_grad_supported": (c_int, [c_int, c_int]),
+    "cips3d_nerf_eikonal_loss": (c_int, [C.POINTER(NerfParams), c_f32p, c_f32, c_f32, c_f32, c_int, C.c_void_p, c_i64, C.c_void_p,
+                                         c_f32p, C.c_void_p]),
+    "cips3d_nerf_eikonal_supported": (c_int, [c_int, c_int]),
+    "cips3d_nerf_eikonal_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "cips3d_nerf_normals": (c_int, [C.POINTER(NormalsParams), C.c_void_p]),
     "cips3d_nerf_finish": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "cips3d_nerf_finish_rays": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
@@ -409,7 +413,7 @@ _SIGS = {
 }
 
 EXPORTED = tuple(_SIGS)
-ABI_VERSION = 48          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
+ABI_VERSION = 49          # == CIPS3D_ABI_VERSION of include/cips3d_hip.h
 _lib = None
 
 

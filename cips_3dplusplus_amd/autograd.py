@@ -633,6 +633,53 @@ def film_table(renderer, styles, batch=None):
     return torch.stack(rows, 1)
 
 
+class EikonalLossFn(Function):
+    """The eikonal and minimal-surface losses of the SDF head as ONE node whose input is the FiLM table (csrc/nerf_eikonal.hip):
+    the forward runs the whole call -- values and d loss / d film -- and keeps the gradient; the backward only scales it.  The
+    renderer's own weights, the points and the camera are constants of the node.
+
+    weights = None: outputs (eikonal, minimal_surface), the two unweighted means, both differentiable; the caller weights them
+    as it likes.  The kernel then runs twice, with lambda = (1, 0) and (0, 1), and the node keeps two dfilm tensors.
+    weights = (w_e, w_m): outputs (total, eikonal, minimal_surface) with total = w_e eikonal + w_m minimal_surface the only
+    differentiable one; the kernel runs once with lambda = weights (the inversion loop's form, projector.eikonal_regulariser).
+    call: film -> keyword arguments of hip.nerf_eikonal_loss without film and the lambdas (VolumeFeatureRenderer._eikonal_args)."""
+
+    @staticmethod
+    def forward(ctx, film, call, weights):
+        film_c = _c(film.detach().float())
+        kw = call(film_c)
+        if weights is None:
+            ws = hip.nerf_eikonal_workspace(kw["hidden"], kw["depth"], kw["B"], film_c.device)    # (one for both calls)
+            loss, d_e = hip.nerf_eikonal_loss(**kw, lambda_eikonal=1.0, lambda_minimal_surface=0.0, workspace=ws)
+            _, d_m = hip.nerf_eikonal_loss(**kw, lambda_eikonal=0.0, lambda_minimal_surface=1.0, workspace=ws)
+            ctx.save_for_backward(d_e, d_m)
+            ctx.weighted = False
+            vals = loss.float()
+            return vals[0].clone(), vals[1].clone()
+        w_e, w_m = float(weights[0]), float(weights[1])
+        loss, d = hip.nerf_eikonal_loss(**kw, lambda_eikonal=w_e, lambda_minimal_surface=w_m)
+        ctx.save_for_backward(d)
+        ctx.weighted = True
+        vals = loss.float()
+        eik, ms = vals[0].clone(), vals[1].clone()
+        ctx.mark_non_differentiable(eik, ms)
+        return w_e * vals[0] + w_m * vals[1], eik, ms
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if ctx.weighted:
+            (d,) = ctx.saved_tensors
+            return (d * grads[0] if grads[0] is not None else None), None, None
+        d_e, d_m = ctx.saved_tensors
+        g_e, g_m = grads
+        out = None
+        if g_e is not None:
+            out = d_e * g_e
+        if g_m is not None:
+            out = d_m * g_m if out is None else out + d_m * g_m
+        return out, None, None
+
+
 def nerf_named_parameters(renderer):
     """(name, parameter) of the renderer's own weights NerfRenderFn differentiates, in the order it takes them: layer weights
     and biases, the two heads, sigmoid_beta -- everything of VolumeFeatureRenderer except the gamma / beta heads (film_table)."""

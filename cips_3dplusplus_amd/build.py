@@ -18,7 +18,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(PKG, "libcips3d_hip.so")
 ARCH = "gfx950"
 # the four longest compiles first, so that they start in the first wave of the pool's 6 jobs
-SOURCES = ["nerf.hip", "fused_stage.hip", "gemm1x1.hip", "nerf_bwd_fused.hip", "bias_act.hip", "upfirdn2d.hip", "linear.hip", "camera.hip", "camera_free.hip", "nerf_sdf_grad.hip", "nerf_normals.hip", "modulate.hip", "decoder_ops.hip", "chain.hip", "conv3x3.hip", "forward.hip", "decoder_route.hip", "backward.hip", "decoder_grad.hip", "nerf_bwd.hip", "render_ops.hip", "rng.hip", "optim.hip", "mesh.hip", "mesh_raster.hip", "mesh_color.hip", "mesh_texture.hip", "vgg.hip", "vgg_split.hip", "inversion_loss.hip", "metrics.hip", "lpips.hip", "ssim_loss.hip", "frame_resample.hip"]
+SOURCES = ["nerf.hip", "fused_stage.hip", "gemm1x1.hip", "nerf_bwd_fused.hip", "bias_act.hip", "upfirdn2d.hip", "linear.hip", "camera.hip", "camera_free.hip", "nerf_sdf_grad.hip", "nerf_eikonal.hip", "nerf_normals.hip", "modulate.hip", "decoder_ops.hip", "chain.hip", "conv3x3.hip", "forward.hip", "decoder_route.hip", "backward.hip", "decoder_grad.hip", "nerf_bwd.hip", "render_ops.hip", "rng.hip", "optim.hip", "mesh.hip", "mesh_raster.hip", "mesh_color.hip", "mesh_texture.hip", "vgg.hip", "vgg_split.hip", "inversion_loss.hip", "metrics.hip", "lpips.hip", "ssim_loss.hip", "frame_resample.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function", "-fno-gpu-rdc"]
 FLAGS = FLAGS + os.environ.get("CIPS3D_HIPCC_FLAGS", "").split()

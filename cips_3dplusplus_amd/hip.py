@@ -506,6 +506,72 @@ def nerf_sdf_grad(*, near_, far_, w_first, packed32, film, layer_bias, w_sigma, 
     return sdf, grad
 
 
+def nerf_eikonal_supported(hidden, depth):
+    """Host-only: does cips3d_nerf_eikonal_loss implement this trunk (hidden 256, depth 1..64)?"""
+    return bool(_lib.load().cips3d_nerf_eikonal_supported(int(hidden), int(depth)))
+
+
+def nerf_eikonal_workspace_bytes(hidden, depth, workgroups, values_only=False):
+    """Host-only: bytes of cips3d_nerf_eikonal_loss's workspace for a grid of at most `workgroups` workgroups."""
+    return int(_lib.load().cips3d_nerf_eikonal_workspace_bytes(int(hidden), int(depth), int(workgroups), int(bool(values_only))))
+
+
+def nerf_eikonal_workspace(hidden, depth, B, device, values_only=False):
+    """The workspace nerf_eikonal_loss allocates when none is passed: room for compute units + B workgroups, 192 KB x depth each
+    (about 50 MB x depth on 256 compute units).  It comes from torch's caching allocator, so a loop that calls every step reuses
+    one block; a caller that wants to hold it passes it in."""
+    wgs = torch.cuda.get_device_properties(device).multi_processor_count + int(B)
+    return torch.empty(nerf_eikonal_workspace_bytes(hidden, depth, wgs, values_only), device=device, dtype=torch.uint8)
+
+
+def nerf_eikonal_loss(*, near_, far_, w_first, packed32, packed32_t, film, layer_bias, w_sigma, b_sigma, B, n_samples, hidden, depth,
+                      img_size=1, cam_poses=None, focals=None, perturb_u=None, x_pts=None, n_rays=0, lambda_eikonal=1.0,
+                      lambda_minimal_surface=1.0, beta=100.0, values_only=False, dfilm_out=None, workspace=None):
+    """The eikonal loss mean((|d sdf / d pts| - 1)^2) and the minimal-surface loss mean(exp(-beta |sdf|)) over the B R N sample
+    points of a call, with d (lambda_eikonal eik + lambda_minimal_surface ms) / d film (csrc/nerf_eikonal.hip)
+    -> (loss [2] float64: the two UNWEIGHTED means, dfilm [B, depth+1, 2, hidden] or None with values_only).
+    Geometry as nerf_sdf_grad: camera form or explicit form (x_pts [B,R,N,3], n_rays = R).  packed32_t: nerf_pack_weights32 of
+    the transposed hidden matrices in reverse layer order (VolumeFeatureRenderer.packed32_t).  workspace: a uint8 tensor of
+    nerf_eikonal_workspace_bytes(...) bytes, else nerf_eikonal_workspace(...) allocates one; its size decides the grid,
+    and values and dfilm are bit-identical from run to run for one size."""
+    lib = _lib.load()
+    if not lib.cips3d_nerf_eikonal_supported(int(hidden), int(depth)):
+        raise NotImplementedError(f"the eikonal loss kernel is built for hidden_dim = 256 and depth <= 64 (got hidden {hidden}, "
+                                  f"depth {depth})")
+    p = _lib.NerfParams()
+    for f, t in (("near_", near_), ("far_", far_), ("w_first", w_first), ("film", film), ("layer_bias", layer_bias),
+                 ("w_sigma", w_sigma), ("b_sigma", b_sigma)):
+        setattr(p, f, dev_ptr(t, f))
+    p.packed32 = dev_ptr(packed32, "packed32", depth == 1)
+    explicit = x_pts is not None
+    p.cam_poses, p.focals = dev_ptr(cam_poses, "cam_poses", explicit), dev_ptr(focals, "focals", explicit)
+    p.perturb_u = dev_ptr(perturb_u, "perturb_u", True)
+    p.x_pts = dev_ptr(x_pts, "x_pts", True)
+    p.n_rays = int(n_rays) if explicit else 0
+    p.B, p.img_size, p.n_samples, p.hidden, p.depth, p.n_chunks = int(B), int(img_size), int(n_samples), int(hidden), int(depth), 1
+    dev = near_.device
+    if tuple(film.shape) != (p.B, p.depth + 1, 2, p.hidden):
+        raise RuntimeError(f"film must have shape {(p.B, p.depth + 1, 2, p.hidden)}, got {tuple(film.shape)}")
+    values_only = bool(values_only)
+    if workspace is None:
+        workspace = nerf_eikonal_workspace(hidden, depth, p.B, dev, values_only)
+    loss = torch.empty(2, device=dev, dtype=torch.float64)
+    dfilm = None
+    if not values_only:
+        dfilm = torch.empty(p.B, p.depth + 1, 2, p.hidden, device=dev) if dfilm_out is None else dfilm_out
+        if tuple(dfilm.shape) != (p.B, p.depth + 1, 2, p.hidden):
+            raise RuntimeError(f"dfilm_out must have shape {(p.B, p.depth + 1, 2, p.hidden)}")
+    ev = _timed("nerf_eikonal_loss")
+    check(lib.cips3d_nerf_eikonal_loss(C.byref(p), dev_ptr(packed32_t, "packed32_t", depth == 1 or values_only),
+                                       float(lambda_eikonal), float(lambda_minimal_surface), float(beta), int(values_only),
+                                       dev_ptr(workspace, "workspace", dtype=torch.uint8), workspace.numel(),
+                                       dev_ptr(loss, "loss", dtype=torch.float64), dev_ptr(dfilm, "dfilm", values_only),
+                                       stream_ptr()), "cips3d_nerf_eikonal_loss")
+    if ev:
+        ev[1].record()
+    return loss, dfilm
+
+
 PHONG_DEFAULTS = dict(ka=0.1, kd=0.65, ks=0.2, shininess=64.0)     # the reference's create_mesh_renderer; pytorch3d's shininess
 
 

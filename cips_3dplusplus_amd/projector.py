@@ -180,6 +180,18 @@ def silhouette_loss(mask, target_masks, weight):
     return _weighted_mse(mask, 1 - target_masks.detach(), weight)
 
 
+def eikonal_regulariser(renderer, cams, styles, eikonal_weight, minimal_surface_weight, img_size, N_samples, beta=100):
+    """eikonal_weight x mean((|d sdf / d pts| - 1)^2) + minimal_surface_weight x mean(exp(-beta |sdf|)) of the renderer's SDF at the
+    sample points of the cameras `cams` = (cam_poses [B,3,4], focals, near, far [B,1,1]; constants: detached here) on img_size^2
+    rays x N_samples un-jittered samples: the reference's two geometry regularisers (exp/stylesdf/losses.py:13-24), which keep
+    the SDF head a distance field while the image losses move `styles` ([1 | B, D+1, style_dim], the W+ styles of the point
+    network).  One autograd node with one kernel call (VolumeFeatureRenderer.eikonal_loss with `weights`); differentiable with
+    respect to `styles` only -- the renderer's own weights are constants of the node."""
+    extr, focal, near, far = (t.detach() for t in cams[:4])
+    return renderer.eikonal_loss(extr, focal, near, far, styles, img_size, N_samples, beta=beta,
+                                 weights=(float(eikonal_weight), float(minimal_surface_weight)))[0]
+
+
 def perceptual_loss(net, target_images, rgb_weight=1.0, thumb_weight=1.0, img_size=1024):
     """rgb_weight sum (fea(rgb) - fea(target))^2 + thumb_weight sum (fea(thumb) - fea(target_thumb))^2 with `net` a
     perceptual.VGG16ConvLoss (projector_v10.py:1170-1174).  The target features -- of `target_images` [B,3,S,S] in [-1, 1] and of
@@ -258,25 +270,30 @@ class FlipProjector:
             groups.append({"params": noise_bufs, "lr": lr_noise, "initial_lr": lr_noise, "betas": (0.9, 0.999)})
         return w, noise_bufs, _adam(groups) if groups else None
 
+    def _cameras(self, cam_cfg, rot, trans=None, camera="look_at", fov=None, img_size=None):
+        """(cam_poses, focals, near, far) of g_forward's camera arguments, at cam_cfg's img_size or at `img_size`."""
+        cam_cfg = dict(cam_cfg)
+        size = cam_cfg.pop("img_size")
+        if img_size is not None:
+            size = img_size
+        cam_cfg = {k: v for k, v in cam_cfg.items() if k in ("fov_ang", "dist_radius")}
+        if camera == "axis_angle":
+            if fov is not None:
+                cam_cfg["fov_ang"] = fov
+            return Camera.free_camera_params(size, self.device, rot, trans, **cam_cfg)
+        if camera == "look_at":
+            return Camera.generate_camera_params(size, self.device, locations=rot if trans is None else torch.cat([rot, trans], 1),
+                                                 **cam_cfg)[:4]
+        raise ValueError(f"g_forward: camera must be 'look_at' or 'axis_angle', got {camera!r}")
+
     # ---- one generator call of the loop (projector_v10.py:211-277)
     def g_forward(self, G, style_render, style_decoder, noise_bufs, cam_cfg, nerf_cfg, rot, trans=None, flip_w_decoder=False,
                   camera="look_at", fov=None):
         """rot, trans: azimuth and elevation [B, 1] each -- or rot = the [B, 2] locations and trans = None.
         camera="axis_angle" (projector_axis_angle.py:190-203): rot [B, 3] an axis-angle vector, trans [B, 3] a position that is
         normalised onto the unit sphere, fov None (cam_cfg's) or the [B] field of view in degrees."""
-        cam_cfg = dict(cam_cfg)
-        img_size = cam_cfg.pop("img_size")
-        cam_cfg = {k: v for k, v in cam_cfg.items() if k in ("fov_ang", "dist_radius")}
-        if camera == "axis_angle":
-            if fov is not None:
-                cam_cfg["fov_ang"] = fov
-            extr, focal, near, far = Camera.free_camera_params(img_size, self.device, rot, trans, **cam_cfg)
-        elif camera == "look_at":
-            extr, focal, near, far, _ = Camera.generate_camera_params(img_size, self.device,
-                                                                      locations=rot if trans is None else torch.cat([rot, trans], 1),
-                                                                      **cam_cfg)
-        else:
-            raise ValueError(f"g_forward: camera must be 'look_at' or 'axis_angle', got {camera!r}")
+        img_size = cam_cfg["img_size"]
+        extr, focal, near, far = self._cameras(cam_cfg, rot, trans, camera, fov)
         if flip_w_decoder:
             style_decoder = style_decoder.detach().flip(dims=(0,))      # only the decoder parameters are updated
         r = G(zs=[None, None], style_render=style_render, style_decoder=style_decoder, cam_poses=extr, focals=focal,
@@ -290,7 +307,8 @@ class FlipProjector:
                       azim_init=(0.0, 0.0), w_avg_samples=10000, regularize_noise_weight=1e5, on_step=None,
                       mask_background=False, mse_weight=0.0, target_images=None, metrics_every=0, lpips_metric=None,
                       ssim_weight=0.0, silhouette_weight=0.0, target_masks=None, camera="look_at", optim_fov=False, lr_fov=0.05,
-                      rot_init=None, trans_init=None):
+                      rot_init=None, trans_init=None, eikonal_weight=0.0, minimal_surface_weight=0.0, eikonal_img_size=None,
+                      eikonal_every=1):
         """Returns the dict `checkpoint.save_inversion` writes (azim, elev, W+ styles, state dicts, noise).
         `camera`: "look_at" (the default: (azim, elev) of a look-at camera with a fixed up vector and field of view) or
         "axis_angle", the free camera of the reference's projector_axis_angle.py: per view an axis-angle rotation `rot` (start
@@ -318,7 +336,27 @@ class FlipProjector:
         `lpips_metric` (the reference's argument, :694-707, 1267-1280; needs `target_images`): a perceptual.LPIPS instance.  The
         final re-render's LPIPS of view 0 against target_images[0] becomes "lpips" (a float); with `metrics_every` > 0 the logged
         steps' values go to metrics_history["lpips"], enqueued beside the PSNR / SSIM launches (perceptual.LPIPSLog) and read
-        once.  None: no network is built (the reference's default downloads one) and nothing changes."""
+        once.  None: no network is built (the reference's default downloads one) and nothing changes.
+        `eikonal_weight` / `minimal_surface_weight` > 0 add eikonal_weight x mean((|d sdf / d pts| - 1)^2) + minimal_surface_weight
+        x mean(exp(-100 |sdf|)) of the point network's SDF (`eikonal_regulariser`, the reference's two geometry regularisers,
+        exp/stylesdf/losses.py:13-24) in both phases, after the silhouette term and before the noise regulariser: the image
+        losses alone do not keep the SDF head a distance field, which marching cubes, the normal maps and the texture atlas of
+        an inverted subject assume.  The term uses the step's cameras, detached, and the step's `w_render`, on eikonal_img_size^2
+        rays (default: cam_cfg["img_size"]; the focal follows the size, so a smaller value samples the same frustum more
+        coarsely) x nerf_cfg["N_samples"] un-jittered samples, at the steps with step % eikonal_every == 0.  One autograd node,
+        one kernel call; its gradient reaches `w_render` only, so it cannot be combined with `optim_render_params` (the
+        renderer's own weights are constants of the node): ValueError.  Both 0: nothing new runs and the dict is unchanged."""
+        if eikonal_weight < 0 or minimal_surface_weight < 0:
+            raise ValueError(f"project_wplus: eikonal_weight and minimal_surface_weight must be non-negative, got {eikonal_weight}, "
+                             f"{minimal_surface_weight}")
+        if eikonal_every < 1 or int(eikonal_every) != eikonal_every:
+            raise ValueError(f"project_wplus: eikonal_every must be a positive integer, got {eikonal_every}")
+        eikonal_on = eikonal_weight > 0 or minimal_surface_weight > 0
+        if eikonal_on and optim_render_params:
+            raise ValueError("project_wplus: eikonal_weight / minimal_surface_weight > 0 cannot be combined with optim_render_params: "
+                             "the renderer's own weights are constants of the eikonal node (it differentiates the styles only)")
+        if eikonal_on and (eikonal_img_size is not None and (eikonal_img_size < 1 or int(eikonal_img_size) != eikonal_img_size)):
+            raise ValueError(f"project_wplus: eikonal_img_size must be a positive integer, got {eikonal_img_size}")
         if camera not in ("look_at", "axis_angle"):
             raise ValueError(f"project_wplus: camera must be 'look_at' or 'axis_angle', got {camera!r}")
         if optim_fov and camera != "axis_angle":
@@ -415,6 +453,11 @@ class FlipProjector:
                 loss = loss + ssim_loss(rgb, target_images, ssim_weight)
             if silhouette_weight > 0:
                 loss = loss + _weighted_mse(mask, bg_target, silhouette_weight)
+            if eikonal_on and step % eikonal_every == 0:
+                with torch.no_grad():
+                    cams = self._cameras(cam_cfg, img_size=eikonal_img_size, **cam_kw())
+                loss = loss + eikonal_regulariser(G.renderer, cams, w_render, eikonal_weight, minimal_surface_weight,
+                                                  int(eikonal_img_size or cam_cfg["img_size"]), int(nerf_cfg["N_samples"]))
             if optim_noise_bufs and regularize_noise_weight > 0:
                 loss = loss + noise_regulariser(noise_bufs, regularize_noise_weight)
             for o in opts:

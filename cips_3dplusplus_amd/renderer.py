@@ -114,6 +114,7 @@ class VolumeFeatureRenderer(nn.Module):
         self._derived = None      # (key, packed, layer_bias, fence)
         self._packed_t = None     # (transposed stream, fence)
         self._packed32 = None     # (key, exact-fp32 weight stream, fence): built on first use in "fp32_exact" precision
+        self._packed32_t = None   # (key, exact-fp32 stream of the transposed matrices, fence): the eikonal loss's reverse sweep
         self.exact_fp32 = False
         self._tables = {}         # B -> (styles_buf, film_buf, LinearTable)
 
@@ -291,6 +292,130 @@ class VolumeFeatureRenderer(nn.Module):
                                    focals=focals.float().reshape(B).contiguous(),
                                    perturb_u=None if perturb_u is None else perturb_u.float().reshape(B, R).contiguous())
         return sdf.view(B, img_size, img_size, N_samples, 1), grad.view(B, img_size, img_size, N_samples, 3)
+
+    def packed32_t(self):
+        """The exact-fp32 stream of the TRANSPOSED hidden matrices in reverse layer order (cips3d_nerf_eikonal_loss's packed32_t:
+        the reverse sweep multiplies by W_l^T for l = D-1 .. 1), cached beside `packed32` and re-made when a weight changes."""
+        key = self._weights_key()
+        ent = self._packed32_t
+        if ent is None or ent[0] != key:
+            net = self.network
+            D, H = self.N_layers_renderer, self.hidden_dim
+            with torch.no_grad():
+                w_t = torch.stack([l.weight.t() for l in reversed(net.pts_linears[1:])]).contiguous() if D > 1 else None
+                p32 = hip.nerf_pack_weights32(w_t, net.views_linears.weight.detach().contiguous(), H, D)
+            ent = self._packed32_t = (key, p32, hip.BuildFence(p32))
+        ent[2].wait()
+        return ent[1]
+
+    def _eikonal_refusals(self, what):
+        if not self.with_sdf:
+            raise NotImplementedError(f"{what}: with_sdf=False: the network's output is a raw density, not a distance (the reference "
+                                      "applies the eikonal and minimal-surface terms only in its SDF branch)")
+        if not hip.nerf_eikonal_supported(self.hidden_dim, self.N_layers_renderer):
+            raise NotImplementedError(f"{what}: the kernel is built for hidden_dim = 256 and depth <= 64; this renderer has "
+                                      f"hidden_dim = {self.hidden_dim}, depth = {self.N_layers_renderer}")
+
+    def _eikonal_args(self, near, far, B, N, **geom):
+        """film -> the keyword arguments of hip.nerf_eikonal_loss for this renderer's weights (autograd.EikonalLossFn's `call`)."""
+        D, H = self.N_layers_renderer, self.hidden_dim
+        net = self.network
+        _, layer_bias = self._derived_buffers()
+        fixed = dict(near_=near.detach().float().reshape(B).contiguous(), far_=far.detach().float().reshape(B).contiguous(),
+                     w_first=net.pts_linears[0].weight.detach(), packed32=self.packed32(force=True) if D > 1 else None,
+                     packed32_t=self.packed32_t() if D > 1 else None, layer_bias=layer_bias, w_sigma=net.sigma_linear.weight.detach(),
+                     b_sigma=net.sigma_linear.bias.detach(), B=B, n_samples=N, hidden=H, depth=D, **geom)
+        return lambda film: dict(fixed, film=film)
+
+    def _film_torch(self, styles, B):
+        """The FiLM table [B, D+1, 2, H] in torch ops (LinearLayer: std_init (s W^T + b) + bias_init), differentiable."""
+        F = torch.nn.functional
+        net = self.network
+        if styles.shape[0] != B:
+            styles = styles.expand(B, -1, -1)
+        rows = []
+        for l, layer in enumerate(list(net.pts_linears) + [net.views_linears]):
+            st = styles[:, l]
+            gb = [float(h.std_init) * F.linear(st, h.weight.detach().to(st.dtype), h.bias.detach().to(st.dtype)) + float(h.bias_init)
+                  for h in (layer.gamma, layer.beta)]
+            rows.append(torch.stack(gb, 1))
+        return torch.stack(rows, 1)
+
+    def _eikonal_torch(self, film, pts, near, far, beta):
+        """The two losses as a torch expression (the reference's: autograd.grad(sdf, pts, create_graph=True), then
+        exp/stylesdf/losses.py:13-24) of the table `film` and the world points pts [B, P, 3]: the A/B partner of the kernel."""
+        F = torch.nn.functional
+        net = self.network
+        dt = film.dtype
+        B = pts.shape[0]
+        with torch.enable_grad():
+            p = pts.detach().to(dt).clone().requires_grad_(True)
+            h = p * 2 / (far.detach().to(dt) - near.detach().to(dt)).reshape(B, 1, 1)
+            for l, layer in enumerate(net.pts_linears):
+                pre = F.linear(h, layer.weight.detach().to(dt), layer.bias.detach().to(dt))
+                h = torch.sin(film[:, l, 0].unsqueeze(1) * pre + film[:, l, 1].unsqueeze(1))
+            sdf = F.linear(h, net.sigma_linear.weight.detach().to(dt), net.sigma_linear.bias.detach().to(dt))
+            g, = torch.autograd.grad(sdf, p, torch.ones_like(sdf), create_graph=True)
+            eik = ((g.norm(dim=-1) - 1) ** 2).mean()
+            ms = torch.exp(-beta * sdf.abs()).mean()
+        return eik, ms
+
+    @staticmethod
+    def _camera_points(cam_poses, focals, near, far, img_size, N_samples, perturb_u, dt):
+        """The world sample points [B, S*S*N, 3] of `render` for a camera, in torch ops (nerf_utils.py:18-66, 69-121 offset
+        sampling, 136-170), constants."""
+        with torch.no_grad():
+            B, S, N = cam_poses.shape[0], int(img_size), int(N_samples)
+            dev = cam_poses.device
+            c2w, focal = cam_poses.to(dt), focals.to(dt).reshape(B, 1, 1)
+            nr, fr = near.to(dt).reshape(B, 1, 1, 1), far.to(dt).reshape(B, 1, 1, 1)
+            centres = torch.linspace(0.5, S - 0.5, S, dtype=dt, device=dev)
+            y = centres.view(1, S, 1).expand(1, S, S)
+            x = centres.view(1, 1, S).expand(1, S, S)
+            d_cam = torch.stack([(x - S * 0.5) / focal, -(y - S * 0.5) / focal, -torch.ones(B, S, S, dtype=dt, device=dev)], dim=-1)
+            rays_d = (d_cam.unsqueeze(-2) * c2w[:, None, None, :3, :3]).sum(-1)
+            rays_o = c2w[:, None, None, :3, 3].expand_as(rays_d)
+            t = torch.linspace(0.0, 1.0 - 1.0 / N, N, dtype=dt, device=dev).view(1, 1, 1, N)
+            z = (nr * (1.0 - t) + fr * t).expand(B, S, S, N)
+            if perturb_u is not None:
+                upper = torch.cat([z[..., 1:], fr.expand(B, S, S, 1)], dim=-1)
+                z = z + (upper - z) * perturb_u.to(dt).reshape(B, S, S, 1)
+            pts = rays_o.unsqueeze(-2) + rays_d.unsqueeze(-2) * z.unsqueeze(-1)
+            return pts.reshape(B, S * S * N, 3)
+
+    def eikonal_loss(self, cam_poses, focals, near, far, styles, img_size, N_samples, perturb_u=None, film=None, beta=100,
+                     weights=None):
+        """The reference's two SDF regularisers (exp/stylesdf/losses.py:13-24 on autograd.grad(sdf, pts, create_graph=True),
+        nerf_utils.py:221-228) at the sample points `render` evaluates for the same arguments -> (eikonal, minimal_surface) =
+        (mean((|d sdf / d pts| - 1)^2), mean(exp(-beta |sdf|))), two 0-dim fp32 tensors whose graph reaches `styles` through
+        `autograd.film_table` (a [1, D+1, style_dim] latent is broadcast over the B views), or through `film`, a FiLM table
+        [B, D+1, 2, H] the caller computed (styles is then not read).  One node (autograd.EikonalLossFn, csrc/nerf_eikonal.hip):
+        forward-mode pass and reverse sweep in one kernel on the exact-fp32 matrix instruction; the renderer's own weights, the
+        points and the camera are constants.  weights = (w_e, w_m): -> (w_e eikonal + w_m minimal_surface, eikonal,
+        minimal_surface) with only the first differentiable -- one kernel call instead of two.
+        With CIPS3D_FUSED_EIKONAL=0 in the environment, or on CPU tensors, the same losses are a torch expression with
+        create_graph=True (the A/B partner; any float dtype of `styles` / `film`).
+        Raises NotImplementedError for hidden_dim != 256 and for with_sdf=False.  The lane-0 note of `sdf_gradient` applies."""
+        import os
+        from . import autograd as AG
+        self._eikonal_refusals("eikonal_loss")
+        B, S, N = cam_poses.shape[0], int(img_size), int(N_samples)
+        fused = cam_poses.is_cuda and os.environ.get("CIPS3D_FUSED_EIKONAL", "1") != "0"
+        if not fused:
+            if film is None:
+                film = self._film_torch(styles, B)
+            pts = self._camera_points(cam_poses, focals, near, far, S, N, perturb_u, film.dtype)
+            eik, ms = self._eikonal_torch(film, pts, near, far, float(beta))
+            if film.dtype == torch.float32:
+                eik, ms = eik.float(), ms.float()
+            return (eik, ms) if weights is None else (float(weights[0]) * eik + float(weights[1]) * ms, eik.detach(), ms.detach())
+        if film is None:
+            film = AG.film_table(self, styles, batch=B)
+        R = S * S
+        call = self._eikonal_args(near, far, B, N, img_size=S, cam_poses=cam_poses.detach().float().contiguous(),
+                                  focals=focals.detach().float().reshape(B).contiguous(), beta=float(beta),
+                                  perturb_u=None if perturb_u is None else perturb_u.detach().float().reshape(B, R).contiguous())
+        return AG.EikonalLossFn.apply(film, call, weights)
 
     @torch.no_grad()
     def normal_map(self, cam_poses, focals, near, far, styles, img_size, N_samples, perturb_u=None, film=None, shade=None,

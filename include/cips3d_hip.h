@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define CIPS3D_ABI_VERSION 48 /* bumped with every change of an entry point or of a struct layout below */
+#define CIPS3D_ABI_VERSION 49 /* bumped with every change of an entry point or of a struct layout below */
+/* 49: cips3d_nerf_eikonal_loss, cips3d_nerf_eikonal_supported, cips3d_nerf_eikonal_workspace_bytes added; nothing else changed. */
 /* 48: cips3d_nerf_bwd_composite, cips3d_nerf_bwd_camera and cips3d_nerf_bwd_fused CHANGED SIGNATURE (each took the argument list
  * of its former superset, whose name is gone); the per-struct cips3d_sizeof_* functions are gone, cips3d_sizeof_struct covers
  * every struct.  A binding written against 47 must be updated: check cips3d_abi_version() before the first call. */
@@ -274,6 +275,29 @@ int cips3d_nerf_render(const cips3d_nerf_params* p, void* stream);
  * hidden == 256 and depth <= 64, else CIPS3D_E_UNSUPP (cips3d_nerf_sdf_grad_supported: the same answer on the host, no GPU needed). */
 int cips3d_nerf_sdf_grad(const cips3d_nerf_params* p, float* grad, void* stream);
 int cips3d_nerf_sdf_grad_supported(int hidden, int depth);
+
+/* Eikonal and minimal-surface losses of the SDF head over the sample points of a call, with their gradient to the FiLM table
+ * (csrc/nerf_eikonal.hip): the reference's regularisers, exp/stylesdf/losses.py:13-24 on autograd.grad(sdf, pts,
+ * create_graph=True), as the forward-mode pass of cips3d_nerf_sdf_grad followed by a reverse sweep over it in one kernel.
+ *   loss_out [2] (device, fp64): mean((|g| - 1)^2) and mean(exp(-beta_ms |sdf|)) over the M = B R n_samples points, UNWEIGHTED;
+ *   dfilm_out [B, depth + 1, 2, hidden] (device): d (lambda_eikonal loss_out[0] + lambda_minimal_surface loss_out[1]) / d film,
+ *   film the table `p->film` as stored (gamma and beta rows after their affine maps); the view layer's row is written as zeros.
+ *   |g| = 0 gives the eikonal term no gradient and sdf = 0 the minimal-surface term none (torch's conventions for norm and abs).
+ *   values_only != 0: only loss_out is written, the reverse sweep does not run, dfilm_out and packed32_t may be NULL.
+ * Reads of `p`: those of cips3d_nerf_sdf_grad (p->sdf is ignored).  packed32_t: cips3d_nerf_pack_weights32's stream of the
+ * TRANSPOSED hidden matrices in reverse layer order (w_hidden[i] = W_{depth-1-i}^T, i = 0 .. depth-2; may be NULL at depth 1).
+ * workspace: 16-byte aligned device memory of workspace_bytes, private to the call until it has run; it decides the grid: one
+ * workgroup per compute unit, at most cips3d_nerf_eikonal_workspace_bytes(.., workgroups, ..)'s `workgroups`, at least B (fewer:
+ * CIPS3D_E_BADARG).  A good size is workgroups = compute units + B.  No gradient with respect to the points, the camera or the
+ * renderer's own weights.  No floating-point atomics: values and dfilm are bit-identical from run to run for one device and one
+ * workspace size.  All products on v_mfma_f32_16x16x4_f32.  Never synchronises.  B >= 1.
+ * hidden == 256 and depth <= 64, else CIPS3D_E_UNSUPP (cips3d_nerf_eikonal_supported: host only).
+ * cips3d_nerf_eikonal_workspace_bytes: host only; 0 for an unsupported trunk. */
+int cips3d_nerf_eikonal_loss(const cips3d_nerf_params* p, const float* packed32_t, float lambda_eikonal,
+                             float lambda_minimal_surface, float beta_ms, int values_only, void* workspace, int64_t workspace_bytes,
+                             double* loss_out, float* dfilm_out, void* stream);
+int cips3d_nerf_eikonal_supported(int hidden, int depth);
+int64_t cips3d_nerf_eikonal_workspace_bytes(int hidden, int depth, int workgroups, int values_only);
 
 /* Composited surface normals of a rendered view and its Phong-shaded geometry frame (csrc/nerf_normals.hip): the render's
  * compositing weights applied to the SDF gradient instead of the sample points.

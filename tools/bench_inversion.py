@@ -5,6 +5,7 @@
                                      [--optim-noise-bufs] [--mask-background] [--mse-weight W] [--metrics-every K]
                                      [--lpips random] [--ssim-weight W] [--silhouette-weight W]
                                      [--camera look_at|axis_angle] [--optim-fov]
+                                     [--eikonal-weight W] [--minimal-surface-weight W] [--eikonal-img-size S] [--eikonal-every K]
 
 One step = forward (batch 2: image + mirrored view) + backward + three Adam steps over {azim, elev}, the NeRF W+ style and
 (with lr 0 in this phase, as projector_v10.py:1074-1075 sets it) the decoder W+ / parameters.  Surrogate loss
@@ -28,7 +29,11 @@ mean latent).  Its gradient goes through the mask map into the NeRF backward.  0
 --camera axis_angle: the free camera (project_wplus's `camera`: an axis-angle rotation and a position on the unit sphere per
 view, csrc/camera_free.hip, instead of (azim, elev)); --optim-fov also optimises the field of view through the render's focal
 gradient (the camera chain's second instantiation).  The JSON line's config gains "camera" (and "optim_fov") in that mode;
-look_at (default): the run is what it was."""
+look_at (default): the run is what it was.
+--eikonal-weight W / --minimal-surface-weight W: the SDF regularisers of the point network are added (project_wplus's
+`eikonal_weight`, `minimal_surface_weight`: csrc/nerf_eikonal.hip, one node on --eikonal-img-size^2 rays (default: the render's
+64) every --eikonal-every steps; CIPS3D_FUSED_EIKONAL=0 runs the torch double backward instead, A/B).  Both 0: the run is what
+it was."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -53,6 +58,10 @@ ap.add_argument("--ssim-weight", type=float, default=0.0)
 ap.add_argument("--silhouette-weight", type=float, default=0.0)
 ap.add_argument("--camera", choices=("look_at", "axis_angle"), default="look_at")
 ap.add_argument("--optim-fov", action="store_true")
+ap.add_argument("--eikonal-weight", type=float, default=0.0)
+ap.add_argument("--minimal-surface-weight", type=float, default=0.0)
+ap.add_argument("--eikonal-img-size", type=int, default=None)
+ap.add_argument("--eikonal-every", type=int, default=1)
 a = ap.parse_args()
 dev = "cuda"
 cfg = configs.ffhq_G_cfg(a.res, a.depth)
@@ -113,12 +122,19 @@ if a.camera != "look_at" or a.optim_fov:
     knobs["camera"] = a.camera
     if a.optim_fov:
         knobs["optim_fov"] = True
+if a.eikonal_weight > 0 or a.minimal_surface_weight > 0:
+    extra.update(eikonal_weight=a.eikonal_weight, minimal_surface_weight=a.minimal_surface_weight,
+                 eikonal_img_size=a.eikonal_img_size, eikonal_every=a.eikonal_every)
+    knobs.update(eikonal_weight=a.eikonal_weight, minimal_surface_weight=a.minimal_surface_weight,
+                 eikonal_img_size=a.eikonal_img_size or 64, eikonal_every=a.eikonal_every,
+                 fused_eikonal=os.environ.get("CIPS3D_FUSED_EIKONAL", "1") != "0")
 n_pose, n_app = a.steps, a.app_steps
 if a.mask_background:                   # the blend runs from the appearance phase on: time appearance steps
     extra.update(mask_background=True)
     knobs["mask_background"] = True
     n_pose, n_app = 0, a.steps + a.app_steps
-if set(knobs) - {"metrics_every", "lpips", "ssim_weight", "fused_ssim", "silhouette_weight", "camera", "optim_fov"}:
+if set(knobs) - {"metrics_every", "lpips", "ssim_weight", "fused_ssim", "silhouette_weight", "camera", "optim_fov", "eikonal_weight",
+                   "minimal_surface_weight", "eikonal_img_size", "eikonal_every", "fused_eikonal"}:
     from cips_3dplusplus_amd import projector as _P
     knobs["fused_noise_reg"], knobs["fused_mask_blend"] = _P.FUSED_NOISE_REG, _P.FUSED_MASK_BLEND
 out = proj.project_wplus(cam_cfg, ncfg, loss_fn, N_steps_pose=n_pose, N_steps_app=n_app,
